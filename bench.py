@@ -12,6 +12,7 @@ as `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`.
 Prints ONE JSON line with the throughput, a `roofline` object for the dominant conv kernel
 (algorithmic FLOPs / live HIP-event time of its launches in one instrumented step) and, at
 N=1, a `cpu_baseline` object (the CPU oracle timed on this host's cores on a bounded sample).
+`--dump-outputs DIR` also writes what the last timed step computed as DIR/*.npy (see dump_outputs).
 """
 import argparse
 import subprocess
@@ -130,6 +131,51 @@ def cpu_baseline(backbone, n, h, w, full_hw, reps=3):
                       (f", images/s scaled by the pixel ratio {scale:.4f} to {full_hw[0]}x{full_hw[1]}" if scale != 1.0 else
                        ", the full resolution: per-image rate of a batch-2 step, nothing scaled (BASELINE.md section 3)"),
             "step_s": times}
+
+
+DUMP_SEED = 12345
+DUMP_PER_TENSOR = 4096          # elements kept of a larger tensor (every element of a smaller one)
+DUMP_MAX_BYTES = 64 * 2**20
+
+
+def dump_outputs(out_dir, loss, model, eic):
+    """--dump-outputs: what the last timed step handed its caller, as out_dir/<name>.npy, so that two builds can be
+    compared output for output on the same seeded inputs.  loss.npy (float64): the step's loss.  eic.npy: the importance
+    scores of every scored BatchNorm, in dcfp_pruning's order.  params.npy / grads.npy: the parameters after the SGD
+    step and the step's gradients, bn_running.npy: the BatchNorm running statistics (float32).  Of each tensor those
+    three keep every element when it has at most DUMP_PER_TENSOR of them, else DUMP_PER_TENSOR elements at positions
+    drawn once from a generator seeded with DUMP_SEED (the same positions from run to run and from build to build)."""
+    import numpy as np
+
+    def positions(tensors):
+        rng = np.random.default_rng(DUMP_SEED)
+        return [torch.from_numpy(np.sort(rng.choice(t.numel(), DUMP_PER_TENSOR, replace=False)))
+                if t.numel() > DUMP_PER_TENSOR else None for t in tensors]
+
+    def sample(tensors, pos):
+        parts = []
+        for t, idx in zip(tensors, pos):
+            flat = t.detach().reshape(-1)
+            if idx is not None:
+                flat = flat[idx.to(flat.device)]
+            parts.append(flat.float().cpu().numpy())
+        return np.concatenate(parts)
+
+    params = [p for _, p in model.named_parameters()]
+    grads = [p.grad if p.grad is not None else torch.zeros_like(p) for p in params]
+    running = [b for n, b in model.named_buffers() if n.endswith(("running_mean", "running_var"))]
+    ppos = positions(params)            # the gradients are sampled where the parameters are
+    arrays = {"loss": np.array([loss], dtype=np.float64),
+              "eic": np.concatenate([v.detach().reshape(-1).float().cpu().numpy() for v in eic.values()]),
+              "params": sample(params, ppos), "grads": sample(grads, ppos),
+              "bn_running": sample(running, positions(running))}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_MAX_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
 
 
 def roofline_from_profile(recs, images_per_step, step_s):
@@ -332,7 +378,12 @@ def main():
     ap.add_argument("--syncbn-p2p", action="store_true",
                     help="data-parallel runs: SyncBN statistics through the peer-to-peer exchange kernel "
                          "(dcfp_amd/syncbn_p2p.py) instead of one RCCL collective per layer; off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them computed (loss, EIC scores, a fixed seeded "
+                         "sample of the updated parameters, gradients and BatchNorm running statistics) as DIR/<name>.npy")
     args, _ = ap.parse_known_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and (args.gpus or 1) > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:], timeout_s=args.rank_timeout))   # parent: no GPU call before this point
@@ -421,6 +472,8 @@ def main():
     global_batch = args.batch * world
     value = global_batch * args.steps / dt
     step_s = dt / args.steps
+    if args.dump_outputs and rank == 0:     # before the instrumented step below changes the state again
+        dump_outputs(args.dump_outputs, last, seg_model, train_pruning.get_eic()["eic"])
 
     roof, extra, comm = None, None, None
     reducer = getattr(model, "reducer", None) if ddp else None

@@ -21,6 +21,8 @@ def _worker(rank, world, port, ret):
     from dcfp_amd.engine import Engine
     from dcfp_amd import ops
     sys.argv = ["x"]
+    # the host path only, also on a machine with a GPU (Engine would bind rank r to device r, which a 1-GPU machine lacks)
+    torch.cuda.is_available = lambda: False
     eng = Engine(custom_parser=argparse.ArgumentParser(), backend="gloo")
     assert eng.distributed and eng.world_size == world and eng.local_rank == rank
     # loss all-reduce
