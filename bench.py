@@ -9,9 +9,11 @@ dcfp_pruning.step (EIC) -> SGD step.  Synthetic data (images N(0,1), labels unif
 5 % ignore=255, seed 12345+rank), default-init weights.  One process per GPU; launched for N>1
 as `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`.
 
-Prints ONE JSON line with the throughput, a `roofline` object for the dominant conv kernel
-(algorithmic FLOPs / live HIP-event time of its launches in one instrumented step) and, at
-N=1, a `cpu_baseline` object (the CPU oracle timed on this host's cores on a bounded sample).
+Prints ONE JSON line with the throughput.  A plain run does only what that needs: set up, warm up, time the
+steps, write the outputs if asked, print.  `--full` also measures the rest: a `roofline` object for the dominant
+conv kernel (algorithmic FLOPs / live HIP-event time of its launches in one instrumented step; with it the
+`detail` and data-parallel `comm` objects), at N=1 a `cpu_baseline` object (the CPU oracle timed on this host's
+cores on a bounded sample), and with `--alt-legs` the `direct_conv` / `alt_math` legs.
 `--dump-outputs DIR` also writes what the last timed step computed as DIR/*.npy (see dump_outputs).
 """
 import argparse
@@ -360,16 +362,20 @@ def main():
     ap.add_argument("--backbone", default="resnet101")
     ap.add_argument("--batch", type=int, default=4, help="images per GPU")
     ap.add_argument("--size", default="1024,2048")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure the roofline of one instrumented step (and the comm object of "
+                         "a data-parallel run), the CPU baseline and, with --alt-legs, the alternative conv legs; "
+                         "off by default")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the instrumented step")
     ap.add_argument("--cpu-sample", default="auto",
                     help="n,h,w of the CPU baseline sample; auto = batch 2 at the full resolution when host RAM >= 150 GiB, "
                          "else 2,512,1024 scaled by the pixel ratio")
     ap.add_argument("--channel-cfg", default=None,
                     help="time the slim model described by this channel_cfg.pth instead (not the headline config)")
     ap.add_argument("--alt-legs", action="store_true",
-                    help="also re-time the step in child processes with DCFP_CONV_WINOGRAD=0 (direct kernels only) and "
-                         "with the opt-in DCFP_CONV_MATH=bf16x3 (off-contract: narrower multiplicands); off by default")
+                    help="with --full: also re-time the step in child processes with DCFP_CONV_WINOGRAD=0 (direct kernels "
+                         "only) and with the opt-in DCFP_CONV_MATH=bf16x3 (off-contract: narrower multiplicands)")
     ap.add_argument("--no-alt", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--rank-timeout", type=float, default=480.0,
                     help="seconds the --gpus N parent waits for its ranks before it stops them and reports")
@@ -384,6 +390,8 @@ def main():
     args, _ = ap.parse_known_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.alt_legs and not args.full:
+        ap.error("--alt-legs is part of a --full run")
 
     if "WORLD_SIZE" not in os.environ and (args.gpus or 1) > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:], timeout_s=args.rank_timeout))   # parent: no GPU call before this point
@@ -477,7 +485,7 @@ def main():
 
     roof, extra, comm = None, None, None
     reducer = getattr(model, "reducer", None) if ddp else None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         if reducer is not None:
             reducer.timing = True
         ops.profile_start()
@@ -509,7 +517,7 @@ def main():
     sgd_rebuilds = getattr(optimizer, "table_rebuilds", None)   # pointer-table uploads (2 = built once per group)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         if args.cpu_sample == "auto":
             # batch 2 per image; at the FULL resolution when the host has the memory for it
             # (R101 batch 2 at 1024x2048 keeps ~40 GB of activations in fp32), else at 512x1024 scaled by the pixel ratio
@@ -532,8 +540,7 @@ def main():
         gc.collect()
         torch.cuda.empty_cache()
         cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(args.steps), "--warmup",
-               str(args.warmup), "--backbone", args.backbone, "--batch", str(args.batch), "--size", args.size,
-               "--no-cpu-baseline", "--no-roofline"]
+               str(args.warmup), "--backbone", args.backbone, "--batch", str(args.batch), "--size", args.size]
 
         def leg(env_extra, what):
             try:

@@ -53,3 +53,11 @@ def test_steps_must_be_positive():
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv, env=env, capture_output=True,
                            text=True, timeout=300)
         assert r.returncode == 2 and "--steps must be at least 1" in r.stderr and r.stdout.strip() == "", argv
+
+
+def test_alt_legs_need_full():
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--alt-legs"], env=env, capture_output=True,
+                       text=True, timeout=300)
+    assert r.returncode == 2 and "--alt-legs is part of a --full run" in r.stderr and r.stdout.strip() == ""

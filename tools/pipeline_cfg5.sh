@@ -12,5 +12,5 @@ python tools/prune.py --model deeplabv3 --backbone resnet101 --backbone-para "$b
     --model-path $out/train/CS_scenes_$steps.pth --score-path $out/train/score.pth --prune-ratio 0.6
 python tools/train.py "${common[@]}" --num-steps $steps --loss-type gsrl --channel-cfg $out/prune/channel_cfg.pth \
     --resume $out/prune/pruned.pth --snapshot-dir $out/finetune --learning-rate 1e-3
-python bench.py --channel-cfg $out/prune/channel_cfg.pth --no-cpu-baseline --steps 3 --warmup 1 > $out/bench_pruned.json
+python bench.py --channel-cfg $out/prune/channel_cfg.pth --full --no-cpu-baseline --steps 3 --warmup 1 > $out/bench_pruned.json
 rm -f $out/train/*.pth $out/prune/pruned.pth $out/finetune/CS_scenes_*.pth   # keep the scratch dir small
