@@ -597,6 +597,8 @@ def bn_apply(x, mean, var, gamma, beta, eps, residual=None, relu=False, out=None
         y = out
         st = y.stride()
         ypitch = _pitch_of(y)
+        if not ypitch and st[3] == 1 and st[2] > W and st[2] % 4 == 0 and st[1] == H * st[2]:
+            ypitch = st[2]      # a channel slice of a row-pitched buffer (the DeepLabv3+ concat)
         if tuple(y.shape) != tuple(x.shape) or (not ypitch and (st[3] != 1 or st[2] != W or st[1] != H * W)):
             raise RuntimeError("bn_apply: out must have dense images or be a row-pitched buffer")
         yns = st[0]
@@ -1294,6 +1296,122 @@ class AsppFn(torch.autograd.Function):
 
 def aspp_branches(x, cfg, tensors):
     return AsppFn.apply(x, cfg, *tensors)
+
+
+def _rows(t):
+    """(batch stride, row pitch) of a [N,C,H,W] tensor with dense rows whose channels are H rows apart - a channel slice
+    of a dense or row-pitched tensor (pitch 0: dense rows) - or None."""
+    N, Cc, H, W = t.shape
+    st = t.stride()
+    if st[3] != 1 or st[2] < W or st[1] != H * st[2] or (st[2] != W and st[2] % 4) or (N > 1 and st[0] < Cc * H * st[2]):
+        return None
+    return (st[0] if N > 1 else Cc * H * st[2]), (st[2] if st[2] != W else 0)
+
+
+def resize_bilinear_into(x, out, align_corners):
+    """out[...] = F.interpolate(x, out.shape[2:], mode='bilinear', align_corners); `out` may be a channel slice of a
+    batch-strided, row-pitched buffer (only its live floats are written)."""
+    _require(x, "x"); _require(out, "out")
+    x, xns = _batch_strided(x)
+    N, Cc, h, w = x.shape
+    H, W = out.shape[2], out.shape[3]
+    r = _rows(out)
+    if r is None or out.shape[0] != N or out.shape[1] != Cc:
+        raise RuntimeError("resize_bilinear_into: out must be [N,C,H,W] with dense rows (a channel slice is fine)")
+    _timed("resize_fwd", None, 4.0 * (x.numel() + out.numel()), lambda: check(
+        _lib.lib().dcfp_resize_bilinear_into_f32(_p(x), xns, N, Cc, h, w, _p(out), r[0], r[1], H, W,
+                                                 int(bool(align_corners)), _stream()), "resize_bilinear_into"))
+    return out
+
+
+def resize_bilinear_adjoint(dy, size, align_corners, out=None, accumulate=False):
+    """dx (+)= interpolate^T(dy) for an input of spatial `size`; dy may be a channel slice of a batch-strided (row-pitched)
+    tensor, read in place.  Deterministic (gather form, fixed summation order)."""
+    _require(dy, "dy")
+    r = _rows(dy)
+    if r is None:
+        dy = dy.contiguous()
+        r = _rows(dy)
+    N, Cc, H, W = dy.shape
+    h, w = int(size[0]), int(size[1])
+    if out is None:
+        dx = torch.empty((N, Cc, h, w), dtype=torch.float32, device=dy.device)
+        accumulate = False
+    else:
+        dx = out
+        if tuple(dx.shape) != (N, Cc, h, w) or not dx.is_contiguous():
+            raise RuntimeError("resize_bilinear_adjoint: out must be a contiguous [N,C,h,w] tensor")
+    _timed("resize_adjoint", None, 4.0 * (dy.numel() + dx.numel()), lambda: check(
+        _lib.lib().dcfp_resize_bilinear_adjoint_f32(_p(dy), r[0], r[1], N, Cc, H, W, _p(dx), Cc * h * w, h, w,
+                                                    int(bool(align_corners)), int(bool(accumulate)), _stream()),
+        "resize_bilinear_adjoint"))
+    return dx
+
+
+class DecoderConcatFn(torch.autograd.Function):
+    """The DeepLabv3+ decoder's concat (networks/deeplabv3p.py:31-38) as ONE autograd node:
+    cat(interpolate(x, size of low), relu(bn1(conv1(low)))) written into one buffer - row-pitched for the 3x3 conv that
+    reads it (ops.conv_pitch) - by its two producers: the resize kernel into channels [0, Cx), the BatchNorm apply of the
+    1x1 conv's output into channels [Cx, Cx + C1).  No torch.cat, no copy.  Backward: both slices of the incoming
+    gradient are read in place; the resize adjoint runs between the BatchNorm reduction and its dx (hides the SyncBN
+    exchange), then conv1's dgrad (d low) and weight gradient."""
+
+    @staticmethod
+    def forward(ctx, x, low, cfg, w1, g1, b1):
+        _require(x, "x"); _require(low, "low")
+        low = low.contiguous()
+        N, Cx, h, w = x.shape
+        _, Cl, H, W = low.shape
+        C1 = w1.shape[0]
+        rm, rv, training, momentum, eps, sync, nbt = cfg["bn"]
+        shape = (N, Cx + C1, H, W)
+        pitch = cfg["pitch"]           # (decided by the caller: grad mode is off inside forward)
+        ctx.pitch_slot = None
+        if pitch:
+            cat, ctx.pitch_slot = owner_pitched(cfg["owner"], shape, pitch, x.device)
+        else:
+            cat = torch.empty(shape, dtype=torch.float32, device=x.device)
+        align = cfg["align"]
+        resize_bilinear_into(x, cat[:, :Cx], align)
+        kp = {} if ctx.needs_input_grad[3] else None
+        stats = None
+        if FUSE_BN_STATS and training:
+            run = _bn_run(rm, rv, momentum, nbt) if _sync_group(sync) is None else None
+            c, stats = conv2d_fwd(low, w1, None, 1, 0, 1, want_stats=True, bn_run=run, keep=kp)
+        else:
+            c = conv2d_fwd(low, w1, None, 1, 0, 1, keep=kp)
+        _, st = bn_forward_impl(c, g1, b1, rm, rv, None, True, training, momentum, eps, sync, nbt=nbt, stats=stats,
+                                out=cat[:, Cx:])
+        mean, var, count, group = st[:4]
+        is_t = isinstance(count, torch.Tensor)
+        ctx.save_for_backward(low, c, mean, var, count if is_t else None)
+        ctx.keep = kp
+        ctx.params = (w1, g1, b1)
+        ctx.cfg = (training, eps, None if is_t else count, group, Cx, (h, w), align)
+        return cat
+
+    @staticmethod
+    def backward(ctx, dcat):
+        low, c, mean, var, count_t = ctx.saved_tensors
+        w1, g1, b1 = ctx.params
+        training, eps, count, group, Cx, hw, align = ctx.cfg
+        state = (mean, var, count_t if count_t is not None else count, group)
+        dx = [None]
+
+        def adjoint():
+            if ctx.needs_input_grad[0]:
+                dx[0] = resize_bilinear_adjoint(dcat[:, :Cx], hw, align)
+        res = bn_backward_impl(dcat[:, Cx:], c, None, g1, b1, state, True, training, eps, False, between=adjoint)
+        d_c, dg, db = res[0], res[1], res[2]
+        dlow = conv2d_dgrad(d_c, w1, tuple(low.shape), 1, 0, 1) if ctx.needs_input_grad[1] else None
+        dw = wgrad_into_param(d_c, low, w1, None, 1, 0, 1, keep=ctx.keep)[0] if ctx.needs_input_grad[3] else None
+        if ctx.pitch_slot is not None:
+            ctx.pitch_slot.release()
+        return dx[0], dlow, None, dw, dg, db
+
+
+def decoder_concat(x, low, cfg, w1, g1, b1):
+    return DecoderConcatFn.apply(x, low, cfg, w1, g1, b1)
 
 
 class ForkFn(torch.autograd.Function):

@@ -95,7 +95,7 @@ def _walk_sequential(g, prefix, seq, prov):
 
 def build_graph(model):
     """Static restatement of what channel_pruner.py:190-253 traces, for
-    dcfp_amd.networks.{deeplabv3,simple}.Seg_Model."""
+    dcfp_amd.networks.{deeplabv3,deeplabv3p,simple}.Seg_Model."""
     g = _Graph()
     bb = model.backbone
     prov = _walk_sequential(g, "backbone.conv1", bb.conv1, [])
@@ -128,7 +128,13 @@ def build_graph(model):
         if a.outplanes is not None:
             x = g.conv("aspp.conv1", x)
             g.norm("aspp.bn1", x)
-    _walk_sequential(g, "last_conv", model.last_conv, x)
+    if hasattr(model, "decoder"):      # DeepLabv3+ (networks/deeplabv3p.py:31-38): cat(resized ASPP output, low)
+        low = g.conv("decoder.conv1", feats[1])
+        g.norm("decoder.bn1", low)
+        x = g.concat([x, low])
+        _walk_sequential(g, "decoder.last_conv", model.decoder.last_conv, x)
+    else:
+        _walk_sequential(g, "last_conv", model.last_conv, x)
     if getattr(model, "deepsup", False) and hasattr(model, "conv_deepsup"):
         _walk_sequential(g, "conv_deepsup", model.conv_deepsup, feats[3])
     return g

@@ -127,7 +127,13 @@ def _count(model, input_shape, deepsup=False):
         x = (outs, x[1], x[2])
         if a.outplanes is not None:
             x = c.conv("aspp.conv1", a.conv1, x); x = c.norm("aspp.bn1", a.bn1, x); x = c.relu("aspp.relu", x)
-    c.sequential("last_conv", model.last_conv, x)
+    if hasattr(model, "decoder"):      # DeepLabv3+: 1x1 conv + BN + ReLU on layer1, concat, then the head
+        d = model.decoder
+        low = c.conv("decoder.conv1", d.conv1, feats[1]); low = c.norm("decoder.bn1", d.bn1, low)
+        low = c.relu("decoder.relu", low)
+        c.sequential("decoder.last_conv", d.last_conv, (x[0] + low[0], low[1], low[2]))
+    else:
+        c.sequential("last_conv", model.last_conv, x)
     if deepsup and getattr(model, "deepsup", False):
         c.sequential("conv_deepsup", model.conv_deepsup, feats[3])
     return c

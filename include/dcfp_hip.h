@@ -372,6 +372,19 @@ int dcfp_upsample_bilinear_fwd_f32(const float* x, float* y, int N, int C,
 int dcfp_upsample_bilinear_bwd_f32(const float* dy, float* dx, int N, int C,
                                    int h, int w, int H, int W, int align_corners,
                                    dcfp_stream_t stream);
+/* y[:, c, :H, :W] = F.interpolate(x, (H, W), mode='bilinear', align_corners) into a channel slice of a
+ * batch-strided, row-pitched destination (y_pitch 0: dense rows).  Writes only the W live floats of a row.
+ * x: [N, C, h, w] with dense images, x_nstride elements apart (0: C*h*w); y_nstride 0: C*H*pitch.  On dense
+ * operands the same bits as dcfp_upsample_bilinear_fwd_f32 (networks/deeplabv3p.py:37, the DeepLabv3+ decoder). */
+int dcfp_resize_bilinear_into_f32(const float* x, int64_t x_nstride, int N, int C, int h, int w,
+                                  float* y, int64_t y_nstride, int y_pitch, int H, int W,
+                                  int align_corners, dcfp_stream_t stream);
+/* dx (+)= interpolate^T(dy): dy is a channel slice of a batch-strided (optionally row-pitched) tensor.
+ * Gather form, fixed summation order, no atomics; accumulate = 1 adds into dx.  dx: [N, C, h, w] with dense
+ * images, dx_nstride elements apart (0: C*h*w). */
+int dcfp_resize_bilinear_adjoint_f32(const float* dy, int64_t dy_nstride, int dy_pitch, int N, int C, int H, int W,
+                                     float* dx, int64_t dx_nstride, int h, int w, int align_corners,
+                                     int accumulate, dcfp_stream_t stream);
 /* Fused  F.interpolate -> nn.CrossEntropyLoss(ignore_index, 'mean')
  * (deeplabv3.py:47,50 + loss/criterion.py:60,65-67): never materialises the
  * full-resolution logits.  labels: int64 [N,H,W].
