@@ -110,6 +110,9 @@ SIGNATURES = {
     "dcfp_upsample_bilinear_bwd_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "dcfp_resize_bilinear_into_f32": (_I, [_P, _L, _I, _I, _I, _I, _P, _L, _I, _I, _I, _I, _P]),
     "dcfp_resize_bilinear_adjoint_f32": (_I, [_P, _L, _I, _I, _I, _I, _I, _P, _L, _I, _I, _I, _I, _P]),
+    "dcfp_ppm_pool_f32": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _L, _I, _P]),
+    "dcfp_ppm_pool_adjoint_f32": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _L, _I, _P, _P]),
+    "dcfp_ppm_resize_adjoint_f32": (_I, [_P, _L, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
     "dcfp_upsample_ce_workspace_bytes": (_Z, [_I, _I, _I]),
     "dcfp_upsample_ce_fwd_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P,
                                       _Z, _P]),

@@ -152,7 +152,11 @@ def run_sequential(seq, x, tail_conv=None):
         elif isinstance(m, nn.Dropout2d):
             x = ops.dropout2d(x, m.p, m.training, getattr(m, "fixed_mask", None))
         elif isinstance(m, nn.AdaptiveAvgPool2d):
-            x = ops.global_avg_pool(x)
+            size = m.output_size
+            size = (size, size) if isinstance(size, int) else tuple(size)
+            if None in size:
+                raise RuntimeError(f"dcfp_amd: no HIP path for {m} (a None output size)")
+            x = ops.global_avg_pool(x) if size == (1, 1) else ops.adaptive_avg_pool(x, size)
         elif isinstance(m, nn.Identity):
             pass
         else:

@@ -1414,6 +1414,202 @@ def decoder_concat(x, low, cfg, w1, g1, b1):
     return DecoderConcatFn.apply(x, low, cfg, w1, g1, b1)
 
 
+def _int_array(vals):
+    vals = [int(v) for v in vals]
+    return (C.c_int * len(vals))(*vals)
+
+
+def _pool_levels(levels):
+    levels = [(int(a), int(b)) for a, b in levels]
+    if not 1 <= len(levels) <= 4 or any(not (1 <= a <= 8 and 1 <= b <= 8) for a, b in levels):
+        raise RuntimeError(f"dcfp_amd: the pyramid pooling kernels take 1 to 4 levels of sizes 1..8, got {levels}")
+    return levels
+
+
+def _level_views(buf, N, widths, levels):
+    out, off = [], 0
+    for Cc, (a, b) in zip(widths, levels):
+        n = N * Cc * a * b
+        out.append(buf[off:off + n].view(N, Cc, a, b))
+        off += n
+    return out
+
+
+def ppm_pool(x, levels, mean=True, dst=None):
+    """F.adaptive_avg_pool2d(x, (sh, sw)) for every (sh, sw) of `levels` (1 to 4, sizes <= 8; sums when not `mean`) in
+    one sweep over x: [N, C, sh, sw] views of one level-major buffer.  dst: optionally also copies x into it (a channel
+    slice of a batch-strided, row-pitched tensor; only the live floats are written)."""
+    _require(x, "x")
+    levels = _pool_levels(levels)
+    x = x.contiguous()
+    N, Cc, H, W = x.shape
+    buf = torch.empty(sum(N * Cc * a * b for a, b in levels), dtype=torch.float32, device=x.device)
+    dns, dpitch = 0, 0
+    if dst is not None:
+        _require(dst, "dst")
+        r = _rows(dst)
+        if r is None or tuple(dst.shape) != (N, Cc, H, W):
+            raise RuntimeError("ppm_pool: dst must be [N,C,H,W] with dense rows (a channel slice is fine)")
+        dns, dpitch = r
+    _timed("ppm_pool", None, 4.0 * x.numel() * (2 if dst is not None else 1), lambda: check(
+        _lib.lib().dcfp_ppm_pool_f32(_p(x), N, Cc, H, W, len(levels), _int_array(v for hw in levels for v in hw),
+                                     _p(buf), int(bool(mean)), _p(dst), dns, dpitch, _stream()), "ppm_pool"))
+    return _level_views(buf, N, [Cc] * len(levels), levels)
+
+
+def ppm_pool_adjoint(dp, levels, shape, g=None):
+    """dx = g + the adjoint of ppm_pool(mean=True): dp is the flat level-major buffer of the levels' [N,C,sh,sw]
+    gradients; g (optional) is read in place, dense or a row-pitched channel slice."""
+    levels = _pool_levels(levels)
+    N, Cc, H, W = [int(v) for v in shape]
+    _require(dp, "dp")
+    if dp.numel() != sum(N * Cc * a * b for a, b in levels) or not dp.is_contiguous():
+        raise RuntimeError("ppm_pool_adjoint: dp must hold the level-major [N,C,sh,sw] blocks of every level")
+    gns, gpitch = 0, 0
+    if g is not None:
+        _require(g, "g")
+        r = _rows(g)
+        if r is None:
+            g = g.contiguous()
+            r = _rows(g)
+        if tuple(g.shape) != (N, Cc, H, W):
+            raise RuntimeError("ppm_pool_adjoint: g must be [N,C,H,W]")
+        gns, gpitch = r
+    dx = torch.empty((N, Cc, H, W), dtype=torch.float32, device=dp.device)
+    _timed("ppm_pool_adjoint", None, 4.0 * dx.numel() * (2 if g is not None else 1), lambda: check(
+        _lib.lib().dcfp_ppm_pool_adjoint_f32(_p(dp), N, Cc, H, W, len(levels),
+                                             _int_array(v for hw in levels for v in hw), _p(g), gns, gpitch, _p(dx),
+                                             _stream()), "ppm_pool_adjoint"))
+    return dx
+
+
+def ppm_resize_adjoint(dy, widths, levels, align_corners):
+    """The adjoint of F.interpolate(bilinear) from small grids, for every level at once: dy [N, sum(widths), H, W] holds
+    the levels' channel slices in order (read in place, dense or a row-pitched slice); returns the [N, C_l, sh, sw]
+    gradients, views of one level-major buffer.  Deterministic (fixed summation order)."""
+    _require(dy, "dy")
+    levels = _pool_levels(levels)
+    r = _rows(dy)
+    if r is None:
+        dy = dy.contiguous()
+        r = _rows(dy)
+    N, Ct, H, W = dy.shape
+    if Ct != sum(widths) or len(widths) != len(levels):
+        raise RuntimeError("ppm_resize_adjoint: dy must hold the levels' channels in order")
+    buf = torch.empty(sum(N * c * a * b for c, (a, b) in zip(widths, levels)), dtype=torch.float32, device=dy.device)
+    chw = [v for c, (a, b) in zip(widths, levels) for v in (c, a, b)]
+    _timed("ppm_resize_adjoint", None, 4.0 * (dy.numel() + buf.numel()), lambda: check(
+        _lib.lib().dcfp_ppm_resize_adjoint_f32(_p(dy), r[0], r[1], N, H, W, len(levels), _int_array(chw), _p(buf),
+                                               int(bool(align_corners)), _stream()), "ppm_resize_adjoint"))
+    return _level_views(buf, N, widths, levels)
+
+
+class AdaptiveAvgPoolFn(torch.autograd.Function):
+    """nn.AdaptiveAvgPool2d((sh, sw)) for output sizes up to 8 (the PSPNet pyramid, networks/tools/ppm.py:27)."""
+
+    @staticmethod
+    def forward(ctx, x, sh, sw):
+        _require(x, "x")
+        ctx.shape = tuple(x.shape)
+        ctx.hw = (sh, sw)
+        return ppm_pool(x, [(sh, sw)])[0]
+
+    @staticmethod
+    def backward(ctx, dy):
+        return ppm_pool_adjoint(dy.contiguous().reshape(-1), [ctx.hw], ctx.shape), None, None
+
+
+def adaptive_avg_pool(x, size):
+    sh, sw = (size, size) if isinstance(size, int) else size
+    return AdaptiveAvgPoolFn.apply(x, int(sh), int(sw))
+
+
+class PyramidPoolingFn(torch.autograd.Function):
+    """The pyramid pooling module of PSPNet (networks/tools/ppm.py:33-37) up to its concat, as ONE autograd node:
+    cat([interpolate(relu(bn_k(conv_k(adaptive_avg_pool(feats, s_k))))) for each stage k] + [feats]) written into one
+    buffer - row-pitched for the 3x3 conv that reads it (ops.conv_pitch) - with no torch.cat.  One sweep over feats pools
+    every level and copies feats into its slice; each stage's 1x1 conv -> BatchNorm -> ReLU runs on its s x s map and is
+    resized into its slice.  Backward: both regions of the incoming gradient are read in place: the small-grid bilinear
+    adjoint of all stages in one launch, per stage the BatchNorm backward, dgrad and weight gradient (the weight gradient
+    of one stage runs between the next stage's BatchNorm reduction and its dx: hides the SyncBN exchange), then the pool
+    adjoint adds the stages' pooled gradients to the feats slice."""
+
+    @staticmethod
+    def forward(ctx, feats, cfg, *tensors):
+        _require(feats, "feats")
+        feats = feats.contiguous()
+        N, Cf, H, W = feats.shape
+        nst = len(tensors) // 3
+        widths = [int(t.shape[0]) for t in tensors[0::3]]
+        levels = [(int(s), int(s)) for s in cfg["sizes"]]
+        offs = [sum(widths[:k]) for k in range(nst + 1)]
+        shape = (N, offs[nst] + Cf, H, W)
+        pitch = cfg["pitch"]           # (decided by the caller: grad mode is off inside forward)
+        ctx.pitch_slot = None
+        if pitch:
+            cat, ctx.pitch_slot = owner_pitched(cfg["owner"], shape, pitch, feats.device)
+        else:
+            cat = torch.empty(shape, dtype=torch.float32, device=feats.device)
+        align = cfg["align"]
+        pooled = ppm_pool(feats, levels, True, dst=cat[:, offs[nst]:])
+        cs, flat, meta = [], [], []
+        for k in range(nst):
+            w, g, b = tensors[3 * k:3 * k + 3]
+            rm, rv, training, momentum, eps, sync, nbt = cfg["bn"][k]
+            c = conv2d_fwd(pooled[k], w, None, 1, 0, 1)
+            y, st = bn_forward_impl(c, g, b, rm, rv, None, True, training, momentum, eps, sync, nbt=nbt)
+            resize_bilinear_into(y, cat[:, offs[k]:offs[k + 1]], align)
+            cs.append(c)
+            mean, var, count, group = st[:4]
+            is_t = isinstance(count, torch.Tensor)
+            meta.append((len(flat), is_t, None if is_t else count, group))
+            flat += [mean, var] + ([count] if is_t else [])
+        ctx.meta = meta
+        ctx.params = tensors
+        ctx.cfg = (levels, widths, offs, (N, Cf, H, W), align, [a[2] for a in cfg["bn"]], [a[4] for a in cfg["bn"]])
+        ctx.save_for_backward(*pooled, *cs, *flat)
+        return cat
+
+    @staticmethod
+    def backward(ctx, dcat):
+        levels, widths, offs, fshape, align, training, eps = ctx.cfg
+        nst = len(widths)
+        saved = ctx.saved_tensors
+        pooled, cs, flat = saved[:nst], saved[nst:2 * nst], saved[2 * nst:]
+        tensors = ctx.params
+        N, Cf, H, W = fshape
+
+        def state(k):
+            pos, is_t, count, group = ctx.meta[k]
+            return (flat[pos], flat[pos + 1], flat[pos + 2] if is_t else count, group)
+        need_dx = ctx.needs_input_grad[0]
+        grads = [None] * (3 * nst)
+        dys = ppm_resize_adjoint(dcat[:, :offs[nst]], widths, levels, align)
+        dp = torch.empty(sum(N * Cf * a * b for a, b in levels), dtype=torch.float32, device=dcat.device) \
+            if need_dx else None
+        dps = _level_views(dp, N, [Cf] * nst, levels) if need_dx else None
+        pending = None             # the previous stage's weight gradient, run inside the next BatchNorm backward
+        for k in range(nst):
+            w, g, b = tensors[3 * k:3 * k + 3]
+            res = bn_backward_impl(dys[k], cs[k], None, g, b, state(k), True, training[k], eps[k], False,
+                                   between=pending)
+            d_c, grads[3 * k + 1], grads[3 * k + 2] = res[0], res[1], res[2]
+            if pending is not None:
+                grads[3 * (k - 1)] = res[4]
+            if need_dx:
+                conv2d_dgrad(d_c, w, tuple(pooled[k].shape), 1, 0, 1, out=dps[k])
+            pending = (lambda d_c=d_c, w=w, x=pooled[k]: wgrad_into_param(d_c, x, w, None, 1, 0, 1)[0])
+        grads[3 * (nst - 1)] = pending()
+        dfeats = ppm_pool_adjoint(dp, levels, fshape, g=dcat[:, offs[nst]:]) if need_dx else None
+        if ctx.pitch_slot is not None:
+            ctx.pitch_slot.release()
+        return (dfeats, None) + tuple(grads)
+
+
+def pyramid_pooling(feats, cfg, tensors):
+    return PyramidPoolingFn.apply(feats, cfg, *tensors)
+
+
 class ForkFn(torch.autograd.Function):
     """x -> (x, x) for a tensor with two consumers (layer3's output feeds layer4 and the deep-supervision
     head, networks/deeplabv3.py:44-50): the two incoming gradients are summed by dcfp_add_f32."""

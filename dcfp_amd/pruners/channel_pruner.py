@@ -72,15 +72,24 @@ class _Graph:
         return prov
 
     def concat(self, provs):
+        """A channel concat of `provs`.  An item that is a residual sum (several convs sharing their channels: the
+        layer4 output in PSPNet's pyramid concat) becomes a node `concat_k_item_i` of its own, as in the reference
+        (channel_pruner.py:701-728): its convs form one group, and its channel space is that of its first parent."""
         node = f"concat_{self._n_concat}"
         self._n_concat += 1
         parents = []
-        for p in provs:
+        for i, p in enumerate(provs):
             if len(p) != 1:
-                raise RuntimeError("concat of a residual sum is not on the DCFP models")
+                item = f"{node}_item_{i}"
+                self.node2parents[item] = list(dict.fromkeys(p))
+                p = [item]
             parents.append(p[0])
         self.node2parents[node] = parents
         return [node]
+
+
+def _is_item(node):
+    return node.startswith("concat_") and "_item_" in node
 
 
 def _walk_sequential(g, prefix, seq, prov):
@@ -95,7 +104,7 @@ def _walk_sequential(g, prefix, seq, prov):
 
 def build_graph(model):
     """Static restatement of what channel_pruner.py:190-253 traces, for
-    dcfp_amd.networks.{deeplabv3,deeplabv3p,simple}.Seg_Model."""
+    dcfp_amd.networks.{deeplabv3,deeplabv3p,psp,simple}.Seg_Model."""
     g = _Graph()
     bb = model.backbone
     prov = _walk_sequential(g, "backbone.conv1", bb.conv1, [])
@@ -128,11 +137,21 @@ def build_graph(model):
         if a.outplanes is not None:
             x = g.conv("aspp.conv1", x)
             g.norm("aspp.bn1", x)
+    if hasattr(model, "ppm"):          # PSPNet (networks/tools/ppm.py:33-37): cat(stage priors, layer4 output)
+        priors = []
+        for k in range(len(model.ppm.stages)):
+            q = g.conv(f"ppm.stages.{k}.1", x)
+            g.norm(f"ppm.stages.{k}.2", q)
+            priors.append(q)
+        x = g.concat(priors + [x])
+        x = _walk_sequential(g, "ppm.bottleneck", model.ppm.bottleneck, x)
     if hasattr(model, "decoder"):      # DeepLabv3+ (networks/deeplabv3p.py:31-38): cat(resized ASPP output, low)
         low = g.conv("decoder.conv1", feats[1])
         g.norm("decoder.bn1", low)
         x = g.concat([x, low])
         _walk_sequential(g, "decoder.last_conv", model.decoder.last_conv, x)
+    elif isinstance(model.last_conv, nn.Conv2d):     # PSPNet's classifier is a bare conv (networks/psp.py:24)
+        g.conv("last_conv", x)
     else:
         _walk_sequential(g, "last_conv", model.last_conv, x)
     if getattr(model, "deepsup", False) and hasattr(model, "conv_deepsup"):
@@ -191,7 +210,7 @@ class ChannelPruner():
         (channel_pruner.py:314-373)."""
         same_in, same_out, idx = {}, {}, -1
         for node, parents in node2parents.items():
-            if node.startswith("concat_"):
+            if node.startswith("concat_") and not _is_item(node):
                 continue
             pset = list(parents)
             added = False
@@ -214,6 +233,8 @@ class ChannelPruner():
         return groups
 
     def get_space_id(self, module_name):
+        if _is_item(module_name) and module_name not in self.name2module:
+            return self.get_space_id(self.node2parents[module_name][0])
         if module_name.startswith("concat_") and module_name not in self.name2module:
             return dict(concat=[self.get_space_id(p) for p in self.node2parents[module_name]])
         if module_name not in self.modules_have_child:

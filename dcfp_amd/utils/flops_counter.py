@@ -127,11 +127,24 @@ def _count(model, input_shape, deepsup=False):
         x = (outs, x[1], x[2])
         if a.outplanes is not None:
             x = c.conv("aspp.conv1", a.conv1, x); x = c.norm("aspp.bn1", a.bn1, x); x = c.relu("aspp.relu", x)
+    if hasattr(model, "ppm"):          # PSPNet: per stage pool (numel of its input) + 1x1 conv + BN + ReLU on s x s
+        outs = 0
+        for k, st in enumerate(model.ppm.stages):
+            size = st[0].output_size
+            sh, sw = (size, size) if isinstance(size, int) else size
+            c.pool_in(f"ppm.stages.{k}.0", x)
+            s = c.conv(f"ppm.stages.{k}.1", st[1], (x[0], sh, sw))
+            s = c.norm(f"ppm.stages.{k}.2", st[2], s)
+            s = c.relu(f"ppm.stages.{k}.3", s)
+            outs += s[0]
+        x = c.sequential("ppm.bottleneck", model.ppm.bottleneck, (outs + x[0], x[1], x[2]))
     if hasattr(model, "decoder"):      # DeepLabv3+: 1x1 conv + BN + ReLU on layer1, concat, then the head
         d = model.decoder
         low = c.conv("decoder.conv1", d.conv1, feats[1]); low = c.norm("decoder.bn1", d.bn1, low)
         low = c.relu("decoder.relu", low)
         c.sequential("decoder.last_conv", d.last_conv, (x[0] + low[0], low[1], low[2]))
+    elif isinstance(model.last_conv, nn.Conv2d):
+        c.conv("last_conv", model.last_conv, x)
     else:
         c.sequential("last_conv", model.last_conv, x)
     if deepsup and getattr(model, "deepsup", False):

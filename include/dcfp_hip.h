@@ -385,6 +385,31 @@ int dcfp_resize_bilinear_into_f32(const float* x, int64_t x_nstride, int N, int 
 int dcfp_resize_bilinear_adjoint_f32(const float* dy, int64_t dy_nstride, int dy_pitch, int N, int C, int H, int W,
                                      float* dx, int64_t dx_nstride, int h, int w, int align_corners,
                                      int accumulate, dcfp_stream_t stream);
+/* ------------------------------------------------ pyramid pooling (PSPNet, networks/tools/ppm.py)
+ * Levels: nlev (1..4) pairs (sh, sw), 1 <= sh, sw <= 8, in host memory (level_hw).  The pooled maps / their
+ * gradients are one buffer of level-major blocks [N, C, sh, sw].  Windows are PyTorch's adaptive ones
+ * (start = floor(i*H/s), end = ceil((i+1)*H/s)): they overlap where s does not divide H, s > H included.
+ * Fixed summation orders, no atomics: every run gives the same bits.
+ *
+ * out = the sums (mean = 0) or means (mean = 1) of every level of x [N, C, H, W] (dense), and, with dst,
+ * dst[:, c, :H, :W] = x: a copy into a channel slice of a batch-strided, row-pitched destination (dst_pitch 0:
+ * dense rows; dst_nstride 0: C*H*pitch) that writes only the W live floats of a row.  x is read once. */
+int dcfp_ppm_pool_f32(const float* x, int N, int C, int H, int W, int nlev, const int* level_hw,
+                      float* out, int mean, float* dst, int64_t dst_nstride, int dst_pitch,
+                      dcfp_stream_t stream);
+/* dx = g + sum over levels (as given), bins i ascending, j ascending of dp[bin] / area[bin] over the bins whose
+ * window holds (y, x).  g (nullable: zero) is read in place, dense or row-pitched (g_nstride 0: C*H*pitch);
+ * dx [N, C, H, W] is dense. */
+int dcfp_ppm_pool_adjoint_f32(const float* dp, int N, int C, int H, int W, int nlev, const int* level_hw,
+                              const float* g, int64_t g_nstride, int g_pitch, float* dx, dcfp_stream_t stream);
+/* The adjoint of F.interpolate(bilinear, align_corners) from small grids: dp[n, c, i, j] =
+ * sum_Y sum_X wy(Y, i) * wx(X, j) * g[n, c, Y, X] (Y ascending, X ascending) for nlev levels of level_chw
+ * triples (C_l, sh, sw), 1 <= sh, sw <= 8.  g: the sum C_l channels of the levels, in order, read in place from a
+ * batch-strided (g_nstride 0: sum C_l * H * pitch), optionally row-pitched tensor; W <= 2048.  dp: level-major
+ * blocks [N, C_l, sh, sw]. */
+int dcfp_ppm_resize_adjoint_f32(const float* g, int64_t g_nstride, int g_pitch, int N, int H, int W,
+                                int nlev, const int* level_chw, float* dp, int align_corners,
+                                dcfp_stream_t stream);
 /* Fused  F.interpolate -> nn.CrossEntropyLoss(ignore_index, 'mean')
  * (deeplabv3.py:47,50 + loss/criterion.py:60,65-67): never materialises the
  * full-resolution logits.  labels: int64 [N,H,W].
