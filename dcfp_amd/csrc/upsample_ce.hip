@@ -923,8 +923,9 @@ extern "C" int dcfp_upsample_argmax_f32(const float* logits, int N, int C, int h
 
 extern "C" int dcfp_confusion_matrix_i64(const int32_t* pred, const int64_t* gt, int ignore_index,
                                          int64_t n_pixels, int C, int64_t* conf, dcfp_stream_t stream) {
-    if (!pred || !gt || !conf || n_pixels < 0 || C <= 0 || C > 1024) return DCFP_E_BADDESC;
-    if (n_pixels == 0) return DCFP_OK;
+    if (!conf || n_pixels < 0 || C <= 0 || C > 1024) return DCFP_E_BADDESC;
+    if (n_pixels == 0) return DCFP_OK;     // an empty tensor has no storage: its pointers are null
+    if (!pred || !gt) return DCFP_E_BADDESC;
     long long b = (n_pixels + kThreads - 1) / kThreads;
     if (b > 1024) b = 1024;
     if (C <= 64)
