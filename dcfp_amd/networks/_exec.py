@@ -2,6 +2,8 @@
 nn.Dropout2d / nn.AdaptiveAvgPool2d — kept as plain torch modules so names, state_dict keys
 and `isinstance` checks in pruners/flops counters stay valid) through the HIP kernels.
 The leaf modules are parameter holders only: their own forward() is never called here."""
+import os
+
 import torch
 import torch.nn as nn
 
@@ -17,8 +19,6 @@ def conv(m, x):
         raise RuntimeError(f"dcfp_amd: unsupported conv configuration {m}")
     return ops.conv2d(x, m.weight, m.bias, m.stride[0], m.padding[0], m.dilation[0])
 
-
-import os
 
 FUSE_BLOCKS = os.environ.get("DCFP_NO_BLOCK_FUSION") is None
 

@@ -898,11 +898,9 @@ def bn_forward_impl(x, gamma, beta, running_mean, running_var, residual, relu, t
     return y, (mean, var, count, group)
 
 
-def bn_backward_reduce(dy, x, y, gamma, beta, state, relu, training, gparam=None, bparam=None, eps=1e-5, pre=None):
-    """First half of the BN backward: the two per-channel sums, dgamma / dbeta written to the parameters'
-    gradient slots, and (SyncBN) the exchange of the sums started asynchronously.  Returns a tuple for
-    bn_backward_apply; independent kernels enqueued between the two overlap the exchange."""
-    mean, var, count, group = state[:4]
+def _bn_bwd_preface(relu, y, state, gamma, beta, gparam, bparam):
+    """What both forms of the BN backward start with: the kernels' relu mode and the tensor it reads (bn_bwd_reduce), and
+    the parameters that receive dgamma / dbeta with their gradient targets: (relu, y, gp, tg, kg, bp, tb, kb)."""
     mask = state[4] if len(state) > 4 else None
     if relu and mask is not None:      # residual BN whose forward kept the ReLU mask as bits
         relu, y = 3, mask
@@ -910,8 +908,15 @@ def bn_backward_reduce(dy, x, y, gamma, beta, state, relu, training, gparam=None
         relu = (1 if y is not None else 2) if relu else 0
     gp = gparam if gparam is not None else gamma
     bp = bparam if bparam is not None else beta
-    tg, kg = arena.grad_target(gp)
-    tb, kb = arena.grad_target(bp)
+    return (relu, y, gp) + tuple(arena.grad_target(gp)) + (bp,) + tuple(arena.grad_target(bp))
+
+
+def bn_backward_reduce(dy, x, y, gamma, beta, state, relu, training, gparam=None, bparam=None, eps=1e-5, pre=None):
+    """First half of the BN backward: the two per-channel sums, dgamma / dbeta written to the parameters'
+    gradient slots, and (SyncBN) the exchange of the sums started asynchronously.  Returns a tuple for
+    bn_backward_apply; independent kernels enqueued between the two overlap the exchange."""
+    mean, var, count, group = state[:4]
+    relu, y, gp, tg, kg, bp, tb, kb = _bn_bwd_preface(relu, y, state, gamma, beta, gparam, bparam)
     if pre is not None:     # the producer of dy already reduced it per 128 pixels (conv2d_dgrad_fanin_red): finish the sums
         s1, s2, _ = bn_bwd_sums_from_partials(pre, var, eps, dgamma=tg, dbeta=tb)
     else:
@@ -948,15 +953,7 @@ def bn_backward_impl(dy, x, y, gamma, beta, state, relu, training, eps, want_res
     that hides the exchange."""
     if BN_BWD_FUSED and training and pre is None and state[3] is None and not isinstance(state[2], torch.Tensor):
         # no exchange between the two stages: one launch, dy and x read once
-        mask = state[4] if len(state) > 4 else None
-        if relu and mask is not None:
-            frelu, fy = 3, mask
-        else:
-            frelu, fy = ((1 if y is not None else 2) if relu else 0), y
-        gp = gparam if gparam is not None else gamma
-        bp = bparam if bparam is not None else beta
-        tg, kg = arena.grad_target(gp)
-        tb, kb = arena.grad_target(bp)
+        frelu, fy, gp, tg, kg, bp, tb, kb = _bn_bwd_preface(relu, y, state, gamma, beta, gparam, bparam)
         out = bn_bwd_fused(dy, x, fy, state[0], state[1], gamma, beta, eps, state[2], frelu, want_res, dx_out,
                            dgamma=tg, dbeta=tb)
         if out is not None:
@@ -968,6 +965,65 @@ def bn_backward_impl(dy, x, y, gamma, beta, state, relu, training, eps, want_res
     mid = between() if between is not None else None
     out = bn_backward_apply(dy, x, gamma, beta, state, red, eps, want_res, dx_out)
     return out + ((mid,) if between is not None else ())
+
+
+def _conv_bn_fwd(inp, w, bnargs, g, b, stride=1, pad=0, dil=1, relu=True, res=None, want_mask=False, out=None, keep=None):
+    """conv -> BatchNorm (+residual) (+ReLU) of the fused nodes: (conv output, y, BN state).  bnargs: the BatchNorm's
+    (running_mean, running_var, training, momentum, eps, sync, nbt).  With FUSE_BN_STATS the conv hands the batch
+    statistics of its output to the BatchNorm behind it."""
+    rm, rv, training, momentum, eps, sync, nbt = bnargs
+    stats = None
+    if FUSE_BN_STATS and training:
+        # the kernel finalising the statistics also does the running-stat bookkeeping, unless the
+        # statistics still have to be pooled over the ranks first (SyncBN)
+        run = _bn_run(rm, rv, momentum, nbt) if _sync_group(sync) is None else None
+        c, stats = conv2d_fwd(inp, w, None, stride, pad, dil, want_stats=True, bn_run=run, keep=keep)
+    else:
+        c = conv2d_fwd(inp, w, None, stride, pad, dil, keep=keep)
+    y, state = bn_forward_impl(c, g, b, rm, rv, res, relu, training, momentum, eps, sync, nbt=nbt,
+                               stats=stats, want_mask=want_mask, out=out)
+    return c, y, state
+
+
+def _pack_bn_states(states):
+    """Per-BN backward states (bn_forward_impl; None entries allowed) -> (flat, meta): the tensors (mean, var, a
+    device-side SyncBN count, the ReLU bit mask) go through save_for_backward (version checks), the rest stays python."""
+    flat, meta = [], []
+    for st in states:
+        if st is None:
+            meta.append(None)
+            continue
+        mean, var, count, group = st[:4]
+        mask = st[4] if len(st) > 4 else None
+        is_t = isinstance(count, torch.Tensor)
+        meta.append((len(flat), is_t, None if is_t else count, group, mask is not None))
+        flat += [mean, var] + ([count] if is_t else []) + ([mask] if mask is not None else [])
+    return flat, meta
+
+
+def _bn_state(meta, flat, i):
+    """State i as bn_forward_impl returned it, from _pack_bn_states' meta and the saved tensors."""
+    if meta[i] is None:
+        return None
+    pos, is_t, count, group, has_mask = meta[i]
+    st = (flat[pos], flat[pos + 1], flat[pos + 2] if is_t else count, group)
+    return st + ((flat[pos + 2 + is_t],) if has_mask else ())
+
+
+def _concat_buffer(ctx, cfg, shape, device):
+    """The output of a concat node: the persistent row-pitched buffer of cfg["owner"] (its lease kept on ctx) where
+    cfg["pitch"] asks for one - decided by the caller: grad mode is off inside forward - else a dense tensor."""
+    ctx.pitch_slot = None
+    if cfg["pitch"]:
+        cat, ctx.pitch_slot = owner_pitched(cfg["owner"], shape, cfg["pitch"], device)
+        return cat
+    return torch.empty(shape, dtype=torch.float32, device=device)
+
+
+def _release_pitch(ctx):
+    """End of a node's backward: its pitched buffer may be reused by the next forward of its owner."""
+    if ctx.pitch_slot is not None:
+        ctx.pitch_slot.release()
 
 
 class BatchNormActFn(torch.autograd.Function):
@@ -994,27 +1050,24 @@ class BatchNormActFn(torch.autograd.Function):
                                                     track=torch.is_grad_enabled())
         y, state = bn_forward_impl(x, gamma, beta, running_mean, running_var, residual, relu,
                                    training, momentum, eps, sync, nbt=nbt, out=out)
-        mean, var, count, group = state[:4]
+        flat, ctx.meta = _pack_bn_states([state])
         # y is saved only where the ReLU mask cannot be re-derived from x (residual input)
-        ctx.save_for_backward(x, y if (relu and residual is not None) else None, mean, var,
-                              count if isinstance(count, torch.Tensor) else None)
+        ctx.save_for_backward(x, y if (relu and residual is not None) else None, *flat)
         ctx.params = (gamma, beta)
-        ctx.cfg = (relu, training, eps, None if isinstance(count, torch.Tensor) else count, group,
-                   residual is not None)
+        ctx.cfg = (relu, training, eps, residual is not None)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, y, mean, var, count_t = ctx.saved_tensors
+        x, y = ctx.saved_tensors[:2]
         gamma, beta = ctx.params
-        relu, training, eps, count, group, has_res = ctx.cfg
-        state = (mean, var, count_t if count_t is not None else count, group)
+        relu, training, eps, has_res = ctx.cfg
+        state = _bn_state(ctx.meta, ctx.saved_tensors[2:], 0)
         need_res = has_res and ctx.needs_input_grad[5]
         dx_out = pitched_buffer(tuple(x.shape), ctx.dx_pitch, ctx.dx_key, x.device) if ctx.dx_pitch else None
         dx, dgamma, dbeta, dres = bn_backward_impl(dy, x, y, gamma, beta, state, relu, training, eps, need_res,
                                                    dx_out=dx_out)
-        if ctx.pitch_slot is not None:
-            ctx.pitch_slot.release()
+        _release_pitch(ctx)
         return dx, dgamma, dbeta, None, None, dres, None, None, None, None, None, None, None
 
 
@@ -1038,21 +1091,6 @@ class BottleneckFn(torch.autograd.Function):
         w1, g1, b1, w2, g2, b2, w3, g3, b3 = tensors[:9]
         bnargs = cfg["bn"]   # per BN: (running_mean, running_var, training, momentum, eps, sync, nbt)
         stride, dil = cfg["stride"], cfg["dil"]
-        fuse = FUSE_BN_STATS   # each conv hands the batch statistics of its output to the BatchNorm behind it
-
-        def conv_bn(inp, wgt, a, g, b, st=1, pd=0, dl=1, relu=True, res=None, want_mask=False, out=None, keep=None):
-            rm, rv, training, momentum, eps, sync, nbt = a
-            stats = None
-            if fuse and training:
-                # the kernel finalising the statistics also does the running-stat bookkeeping, unless the
-                # statistics still have to be pooled over the ranks first (SyncBN)
-                run = _bn_run(rm, rv, momentum, nbt) if _sync_group(sync) is None else None
-                c, stats = conv2d_fwd(inp, wgt, None, st, pd, dl, want_stats=True, bn_run=run, keep=keep)
-            else:
-                c = conv2d_fwd(inp, wgt, None, st, pd, dl, keep=keep)
-            y, state = bn_forward_impl(c, g, b, rm, rv, res, relu, training, momentum, eps, sync, nbt=nbt,
-                                       stats=stats, want_mask=want_mask, out=out)
-            return c, y, state
 
         # conv2 with dilation 1 / 2: its input y1 (and, in backward, the gradient of its output) are kept
         # row-pitched with a zero tail, so the 3x3 kernels copy every shifted quad without border handling.
@@ -1065,31 +1103,20 @@ class BottleneckFn(torch.autograd.Function):
         if pitch:
             y1_out, ctx.pitch_slot = owner_pitched(cfg.get("owner"), y1_shape, pitch, x.device)
         ctx.pitch = pitch
-        c1, y1, st1 = conv_bn(x, w1, bnargs[0], g1, b1, out=y1_out)
+        c1, y1, st1 = _conv_bn_fwd(x, w1, bnargs[0], g1, b1, out=y1_out)
         # (conv2's Winograd input transform is kept for its weight gradient: 4x the size of y1, until this block's backward)
         ctx.keep2 = {} if ctx.needs_input_grad[5] else None      # inputs: x, cfg, w1, g1, b1, w2, ...
-        c2, y2, st2 = conv_bn(y1, w2, bnargs[1], g2, b2, stride, dil, dil, keep=ctx.keep2)
+        c2, y2, st2 = _conv_bn_fwd(y1, w2, bnargs[1], g2, b2, stride, dil, dil, keep=ctx.keep2)
         if has_ds:
             wd, gd, bd = tensors[9:]
-            cd, res, std = conv_bn(x, wd, bnargs[3], gd, bd, stride, 0, 1, relu=False)
+            cd, res, std = _conv_bn_fwd(x, wd, bnargs[3], gd, bd, stride, 0, 1, relu=False)
         else:
             cd, res, std = None, x, None
-        c3, out, st3 = conv_bn(y2, w3, bnargs[2], g3, b3, res=res, want_mask=True)
+        c3, out, st3 = _conv_bn_fwd(y2, w3, bnargs[2], g3, b3, res=res, want_mask=True)
         ctx.has_ds = has_ds
         ctx.cfg = (stride, dil, [a[2] for a in bnargs], [a[4] for a in bnargs])
         ctx.params = tensors
-        # per-BN backward state: tensors go through save_for_backward (version checks), the rest stays python
-        flat, meta = [], []
-        for st in (st1, st2, st3, std):
-            if st is None:
-                meta.append(None)
-                continue
-            mean, var, count, group = st[:4]
-            mask = st[4] if len(st) > 4 else None
-            meta.append((len(flat), isinstance(count, torch.Tensor), None if isinstance(count, torch.Tensor) else count,
-                         group, mask is not None))
-            flat += [mean, var] + ([count] if isinstance(count, torch.Tensor) else []) + ([mask] if mask is not None else [])
-        ctx.meta = meta
+        flat, ctx.meta = _pack_bn_states((st1, st2, st3, std))
         # with the 1-bit mask the block output is not needed by its own backward
         keep_out = out if len(st3) <= 4 else None
         ctx.save_for_backward(x, c1, y1, c2, y2, c3, keep_out, cd, *flat)
@@ -1112,19 +1139,7 @@ class BottleneckFn(torch.autograd.Function):
         tensors = ctx.params
         w1, g1, b1, w2, g2, b2, w3, g3, b3 = tensors[:9]
         stride, dil, training, eps = ctx.cfg
-
-        def state(i):
-            m = ctx.meta[i]
-            if m is None:
-                return None
-            pos, count_is_t, count, group, has_mask = m
-            mean, var = flat[pos], flat[pos + 1]
-            pos += 2
-            if count_is_t:
-                count = flat[pos]; pos += 1
-            st = (mean, var, count, group)
-            return st + ((flat[pos],) if has_mask else ())
-        st1, st2, st3, std = state(0), state(1), state(2), state(3)
+        st1, st2, st3, std = (_bn_state(ctx.meta, flat, i) for i in range(4))
 
         def wg(dy, inp, w, st=1, pd=0, dl=1, keep=None):
             return lambda: wgrad_into_param(dy, inp, w, None, st, pd, dl, keep=keep)[0]
@@ -1186,8 +1201,7 @@ class BottleneckFn(torch.autograd.Function):
         else:
             dx = None
         ctx.prev_rec = None
-        if ctx.pitch_slot is not None:
-            ctx.pitch_slot.release()            # y1's buffer may be reused by the next forward of this block
+        _release_pitch(ctx)            # y1's buffer
         return (dx, None) + tuple(grads)
 
 
@@ -1221,17 +1235,10 @@ class AsppFn(torch.autograd.Function):
         for k in range(4):
             w, g, b = tensors[3 * k:3 * k + 3]
             pad, dil = cfg["convs"][k]
-            rm, rv, training, momentum, eps, sync, nbt = cfg["bn"][k]
-            stats = None
             kp = {} if ctx.needs_input_grad[2 + 3 * k] else None      # inputs: x, cfg, then (w, gamma, beta) per branch
             keeps.append(kp)
-            if FUSE_BN_STATS and training:
-                run = _bn_run(rm, rv, momentum, nbt) if _sync_group(sync) is None else None
-                c, stats = conv2d_fwd(x, w, None, 1, pad, dil, want_stats=True, bn_run=run, keep=kp)
-            else:
-                c = conv2d_fwd(x, w, None, 1, pad, dil, keep=kp)
-            _, st = bn_forward_impl(c, g, b, rm, rv, None, True, training, momentum, eps, sync, nbt=nbt, stats=stats,
-                                    out=cat[:, offs[k]:offs[k] + widths[k]])
+            c, _, st = _conv_bn_fwd(x, w, cfg["bn"][k], g, b, 1, pad, dil, out=cat[:, offs[k]:offs[k] + widths[k]],
+                                    keep=kp)
             cs.append(c); states.append(st)
         w5, g5, b5 = tensors[12:15]
         rm, rv, training, momentum, eps, sync, nbt = cfg["bn"][4]
@@ -1243,13 +1250,7 @@ class AsppFn(torch.autograd.Function):
         ctx.keeps = keeps        # the branches' kept Winograd input transforms (released by their weight gradients)
         ctx.cfg = (cfg["convs"], [a[2] for a in cfg["bn"]], [a[4] for a in cfg["bn"]], offs, widths)
         ctx.params = tensors
-        flat, meta = [], []
-        for st in states:
-            mean, var, count, group = st[:4]
-            is_t = isinstance(count, torch.Tensor)
-            meta.append((len(flat), is_t, None if is_t else count, group))
-            flat += [mean, var] + ([count] if is_t else [])
-        ctx.meta = meta
+        flat, ctx.meta = _pack_bn_states(states)
         ctx.save_for_backward(x, pooled, c5, *cs, *flat)
         return cat
 
@@ -1261,10 +1262,6 @@ class AsppFn(torch.autograd.Function):
         tensors = ctx.params
         convs, training, eps, offs, widths = ctx.cfg
         N, Cin, H, W = x.shape
-
-        def state(i):
-            pos, is_t, count, group = ctx.meta[i]
-            return (flat[pos], flat[pos + 1], flat[pos + 2] if is_t else count, group)
         need_dx = ctx.needs_input_grad[0]
         grads = [None] * 15
         dx = None
@@ -1273,7 +1270,7 @@ class AsppFn(torch.autograd.Function):
             w, g, b = tensors[3 * k:3 * k + 3]
             pad, dil = convs[k]
             dslice = dcat[:, offs[k]:offs[k] + widths[k]]
-            res = bn_backward_impl(dslice, cs[k], None, g, b, state(k), True, training[k], eps[k], False,
+            res = bn_backward_impl(dslice, cs[k], None, g, b, _bn_state(ctx.meta, flat, k), True, training[k], eps[k], False,
                                    between=pending)
             d_c, grads[3 * k + 1], grads[3 * k + 2] = res[0], res[1], res[2]
             if pending is not None:
@@ -1285,7 +1282,7 @@ class AsppFn(torch.autograd.Function):
         # image-pooling branch: broadcast^T = sum over pixels, then BN / 1x1 conv on N x C x 1 x 1
         w5, g5, b5 = tensors[12:15]
         g_y5 = rowsum(dcat[:, offs[4]:offs[4] + widths[4]], 1.0)
-        res = bn_backward_impl(g_y5, c5, None, g5, b5, state(4), True, training[4], eps[4], False, between=pending)
+        res = bn_backward_impl(g_y5, c5, None, g5, b5, _bn_state(ctx.meta, flat, 4), True, training[4], eps[4], False, between=pending)
         d_c5, grads[13], grads[14], grads[9] = res[0], res[1], res[2], res[4]
         grads[12], _ = wgrad_into_param(d_c5, pooled, w5, None, 1, 0, 1)
         if need_dx:
@@ -1308,6 +1305,15 @@ def _rows(t):
     return (st[0] if N > 1 else Cc * H * st[2]), (st[2] if st[2] != W else 0)
 
 
+def _rows_or_copy(t):
+    """(t, batch stride, row pitch): t read in place where _rows describes it, else a contiguous copy of it."""
+    r = _rows(t)
+    if r is None:
+        t = t.contiguous()
+        r = _rows(t)
+    return (t,) + r
+
+
 def resize_bilinear_into(x, out, align_corners):
     """out[...] = F.interpolate(x, out.shape[2:], mode='bilinear', align_corners); `out` may be a channel slice of a
     batch-strided, row-pitched buffer (only its live floats are written)."""
@@ -1328,10 +1334,7 @@ def resize_bilinear_adjoint(dy, size, align_corners, out=None, accumulate=False)
     """dx (+)= interpolate^T(dy) for an input of spatial `size`; dy may be a channel slice of a batch-strided (row-pitched)
     tensor, read in place.  Deterministic (gather form, fixed summation order)."""
     _require(dy, "dy")
-    r = _rows(dy)
-    if r is None:
-        dy = dy.contiguous()
-        r = _rows(dy)
+    dy, dns, dpitch = _rows_or_copy(dy)
     N, Cc, H, W = dy.shape
     h, w = int(size[0]), int(size[1])
     if out is None:
@@ -1342,7 +1345,7 @@ def resize_bilinear_adjoint(dy, size, align_corners, out=None, accumulate=False)
         if tuple(dx.shape) != (N, Cc, h, w) or not dx.is_contiguous():
             raise RuntimeError("resize_bilinear_adjoint: out must be a contiguous [N,C,h,w] tensor")
     _timed("resize_adjoint", None, 4.0 * (dy.numel() + dx.numel()), lambda: check(
-        _lib.lib().dcfp_resize_bilinear_adjoint_f32(_p(dy), r[0], r[1], N, Cc, H, W, _p(dx), Cc * h * w, h, w,
+        _lib.lib().dcfp_resize_bilinear_adjoint_f32(_p(dy), dns, dpitch, N, Cc, H, W, _p(dx), Cc * h * w, h, w,
                                                     int(bool(align_corners)), int(bool(accumulate)), _stream()),
         "resize_bilinear_adjoint"))
     return dx
@@ -1363,39 +1366,23 @@ class DecoderConcatFn(torch.autograd.Function):
         N, Cx, h, w = x.shape
         _, Cl, H, W = low.shape
         C1 = w1.shape[0]
-        rm, rv, training, momentum, eps, sync, nbt = cfg["bn"]
-        shape = (N, Cx + C1, H, W)
-        pitch = cfg["pitch"]           # (decided by the caller: grad mode is off inside forward)
-        ctx.pitch_slot = None
-        if pitch:
-            cat, ctx.pitch_slot = owner_pitched(cfg["owner"], shape, pitch, x.device)
-        else:
-            cat = torch.empty(shape, dtype=torch.float32, device=x.device)
+        cat = _concat_buffer(ctx, cfg, (N, Cx + C1, H, W), x.device)
         align = cfg["align"]
         resize_bilinear_into(x, cat[:, :Cx], align)
-        kp = {} if ctx.needs_input_grad[3] else None
-        stats = None
-        if FUSE_BN_STATS and training:
-            run = _bn_run(rm, rv, momentum, nbt) if _sync_group(sync) is None else None
-            c, stats = conv2d_fwd(low, w1, None, 1, 0, 1, want_stats=True, bn_run=run, keep=kp)
-        else:
-            c = conv2d_fwd(low, w1, None, 1, 0, 1, keep=kp)
-        _, st = bn_forward_impl(c, g1, b1, rm, rv, None, True, training, momentum, eps, sync, nbt=nbt, stats=stats,
-                                out=cat[:, Cx:])
-        mean, var, count, group = st[:4]
-        is_t = isinstance(count, torch.Tensor)
-        ctx.save_for_backward(low, c, mean, var, count if is_t else None)
-        ctx.keep = kp
+        ctx.keep = {} if ctx.needs_input_grad[3] else None
+        c, _, st = _conv_bn_fwd(low, w1, cfg["bn"], g1, b1, out=cat[:, Cx:], keep=ctx.keep)
+        flat, ctx.meta = _pack_bn_states([st])
+        ctx.save_for_backward(low, c, *flat)
         ctx.params = (w1, g1, b1)
-        ctx.cfg = (training, eps, None if is_t else count, group, Cx, (h, w), align)
+        ctx.cfg = (cfg["bn"][2], cfg["bn"][4], Cx, (h, w), align)
         return cat
 
     @staticmethod
     def backward(ctx, dcat):
-        low, c, mean, var, count_t = ctx.saved_tensors
+        low, c = ctx.saved_tensors[:2]
         w1, g1, b1 = ctx.params
-        training, eps, count, group, Cx, hw, align = ctx.cfg
-        state = (mean, var, count_t if count_t is not None else count, group)
+        training, eps, Cx, hw, align = ctx.cfg
+        state = _bn_state(ctx.meta, ctx.saved_tensors[2:], 0)
         dx = [None]
 
         def adjoint():
@@ -1405,8 +1392,7 @@ class DecoderConcatFn(torch.autograd.Function):
         d_c, dg, db = res[0], res[1], res[2]
         dlow = conv2d_dgrad(d_c, w1, tuple(low.shape), 1, 0, 1) if ctx.needs_input_grad[1] else None
         dw = wgrad_into_param(d_c, low, w1, None, 1, 0, 1, keep=ctx.keep)[0] if ctx.needs_input_grad[3] else None
-        if ctx.pitch_slot is not None:
-            ctx.pitch_slot.release()
+        _release_pitch(ctx)
         return dx[0], dlow, None, dw, dg, db
 
 
@@ -1468,13 +1454,9 @@ def ppm_pool_adjoint(dp, levels, shape, g=None):
     gns, gpitch = 0, 0
     if g is not None:
         _require(g, "g")
-        r = _rows(g)
-        if r is None:
-            g = g.contiguous()
-            r = _rows(g)
+        g, gns, gpitch = _rows_or_copy(g)
         if tuple(g.shape) != (N, Cc, H, W):
             raise RuntimeError("ppm_pool_adjoint: g must be [N,C,H,W]")
-        gns, gpitch = r
     dx = torch.empty((N, Cc, H, W), dtype=torch.float32, device=dp.device)
     _timed("ppm_pool_adjoint", None, 4.0 * dx.numel() * (2 if g is not None else 1), lambda: check(
         _lib.lib().dcfp_ppm_pool_adjoint_f32(_p(dp), N, Cc, H, W, len(levels),
@@ -1489,17 +1471,14 @@ def ppm_resize_adjoint(dy, widths, levels, align_corners):
     gradients, views of one level-major buffer.  Deterministic (fixed summation order)."""
     _require(dy, "dy")
     levels = _pool_levels(levels)
-    r = _rows(dy)
-    if r is None:
-        dy = dy.contiguous()
-        r = _rows(dy)
+    dy, dns, dpitch = _rows_or_copy(dy)
     N, Ct, H, W = dy.shape
     if Ct != sum(widths) or len(widths) != len(levels):
         raise RuntimeError("ppm_resize_adjoint: dy must hold the levels' channels in order")
     buf = torch.empty(sum(N * c * a * b for c, (a, b) in zip(widths, levels)), dtype=torch.float32, device=dy.device)
     chw = [v for c, (a, b) in zip(widths, levels) for v in (c, a, b)]
     _timed("ppm_resize_adjoint", None, 4.0 * (dy.numel() + buf.numel()), lambda: check(
-        _lib.lib().dcfp_ppm_resize_adjoint_f32(_p(dy), r[0], r[1], N, H, W, len(levels), _int_array(chw), _p(buf),
+        _lib.lib().dcfp_ppm_resize_adjoint_f32(_p(dy), dns, dpitch, N, H, W, len(levels), _int_array(chw), _p(buf),
                                                int(bool(align_corners)), _stream()), "ppm_resize_adjoint"))
     return _level_views(buf, N, widths, levels)
 
@@ -1543,28 +1522,18 @@ class PyramidPoolingFn(torch.autograd.Function):
         widths = [int(t.shape[0]) for t in tensors[0::3]]
         levels = [(int(s), int(s)) for s in cfg["sizes"]]
         offs = [sum(widths[:k]) for k in range(nst + 1)]
-        shape = (N, offs[nst] + Cf, H, W)
-        pitch = cfg["pitch"]           # (decided by the caller: grad mode is off inside forward)
-        ctx.pitch_slot = None
-        if pitch:
-            cat, ctx.pitch_slot = owner_pitched(cfg["owner"], shape, pitch, feats.device)
-        else:
-            cat = torch.empty(shape, dtype=torch.float32, device=feats.device)
+        cat = _concat_buffer(ctx, cfg, (N, offs[nst] + Cf, H, W), feats.device)
         align = cfg["align"]
         pooled = ppm_pool(feats, levels, True, dst=cat[:, offs[nst]:])
-        cs, flat, meta = [], [], []
+        cs, states = [], []
         for k in range(nst):
             w, g, b = tensors[3 * k:3 * k + 3]
             rm, rv, training, momentum, eps, sync, nbt = cfg["bn"][k]
             c = conv2d_fwd(pooled[k], w, None, 1, 0, 1)
             y, st = bn_forward_impl(c, g, b, rm, rv, None, True, training, momentum, eps, sync, nbt=nbt)
             resize_bilinear_into(y, cat[:, offs[k]:offs[k + 1]], align)
-            cs.append(c)
-            mean, var, count, group = st[:4]
-            is_t = isinstance(count, torch.Tensor)
-            meta.append((len(flat), is_t, None if is_t else count, group))
-            flat += [mean, var] + ([count] if is_t else [])
-        ctx.meta = meta
+            cs.append(c); states.append(st)
+        flat, ctx.meta = _pack_bn_states(states)
         ctx.params = tensors
         ctx.cfg = (levels, widths, offs, (N, Cf, H, W), align, [a[2] for a in cfg["bn"]], [a[4] for a in cfg["bn"]])
         ctx.save_for_backward(*pooled, *cs, *flat)
@@ -1578,10 +1547,6 @@ class PyramidPoolingFn(torch.autograd.Function):
         pooled, cs, flat = saved[:nst], saved[nst:2 * nst], saved[2 * nst:]
         tensors = ctx.params
         N, Cf, H, W = fshape
-
-        def state(k):
-            pos, is_t, count, group = ctx.meta[k]
-            return (flat[pos], flat[pos + 1], flat[pos + 2] if is_t else count, group)
         need_dx = ctx.needs_input_grad[0]
         grads = [None] * (3 * nst)
         dys = ppm_resize_adjoint(dcat[:, :offs[nst]], widths, levels, align)
@@ -1591,7 +1556,7 @@ class PyramidPoolingFn(torch.autograd.Function):
         pending = None             # the previous stage's weight gradient, run inside the next BatchNorm backward
         for k in range(nst):
             w, g, b = tensors[3 * k:3 * k + 3]
-            res = bn_backward_impl(dys[k], cs[k], None, g, b, state(k), True, training[k], eps[k], False,
+            res = bn_backward_impl(dys[k], cs[k], None, g, b, _bn_state(ctx.meta, flat, k), True, training[k], eps[k], False,
                                    between=pending)
             d_c, grads[3 * k + 1], grads[3 * k + 2] = res[0], res[1], res[2]
             if pending is not None:
@@ -1601,8 +1566,7 @@ class PyramidPoolingFn(torch.autograd.Function):
             pending = (lambda d_c=d_c, w=w, x=pooled[k]: wgrad_into_param(d_c, x, w, None, 1, 0, 1)[0])
         grads[3 * (nst - 1)] = pending()
         dfeats = ppm_pool_adjoint(dp, levels, fshape, g=dcat[:, offs[nst]:]) if need_dx else None
-        if ctx.pitch_slot is not None:
-            ctx.pitch_slot.release()
+        _release_pitch(ctx)
         return (dfeats, None) + tuple(grads)
 
 

@@ -1,7 +1,9 @@
 """Generate tests/golden/*.npz by IMPORTING THE REAL REFERENCE (/root/reference) on CPU.
 
 Dev-container only (the reference never travels to the GPU box).  Run:
-    cd /tmp && PYTHONDONTWRITEBYTECODE=1 python /root/repo/oracle/make_golden.py
+    PYTHONDONTWRITEBYTECODE=1 python oracle/make_golden.py [--out DIR] [KEY ...]
+KEYs: see the bottom of this file (`v3p` / `psp`: the whole-model, prune and flops fixtures of that head; `v3p:model`
+etc. for one of them).  --out: write there instead of tests/golden/ (to compare a recipe change with the fixtures).
 Accommodations — none of them touches a reference file:
   * `ordered_set` (third-party, un-vendored) -> an insertion-ordered list stand-in;
   * torch 2.x names conv's autograd node 'ConvolutionBackward0' -> registered at run time;
@@ -79,7 +81,24 @@ def build_ref(model, backbone, align, dtype):
     return m.to(dtype)
 
 
-def whole_model(tag, model, backbone, N, H, W, align):
+def _grad_summaries(m, res, sfx):
+    """Every parameter gradient, compactly: L2 norm and a projection on a fixed cos vector.  Returns the names."""
+    grads = {k: p.grad.detach() for k, p in m.named_parameters()}
+    res["grad_l2:" + sfx] = np.array([float(g.double().norm()) for g in grads.values()])
+    res["grad_proj:" + sfx] = np.array([
+        float((g.double().reshape(-1) * torch.cos(0.37 * torch.arange(g.numel(), dtype=torch.float64))).sum())
+        for g in grads.values()])
+    return list(grads)
+
+
+def whole_model(tag, model, backbone, N, H, W, align, cls="last_conv.6",
+                convs=("backbone.conv1.0", "backbone.layer1.0.conv1", "backbone.layer2.0.conv2"),
+                running=("backbone.bn1",), logit_step=2, compact=False):
+    """cls: the classifier conv (weight and bias gradient stored); convs: further convs whose weight gradient is stored
+    whole; running: BatchNorms whose running statistics are stored; logits are stored at every logit_step-th pixel
+    (fixture size; recorded as `logit_step` unless 2).  compact: the fp64 gradient arrays are kept as float32
+    differences to the fp32 run (key suffix d64m32 instead of 64: a test rebuilds fp64 as fp32 + difference), which
+    keeps the files of the heads added later under 1 MiB."""
     res = {}
     for dtype, sfx in ((torch.float32, "32"), (torch.float64, "64")):
         torch.manual_seed(0)
@@ -87,48 +106,48 @@ def whole_model(tag, model, backbone, N, H, W, align):
         m.train()
         x = fill.closed_form_input(N, H, W, dtype)
         lab = fill.closed_form_labels(N, H, W)
-        out = m(x, lab, deepsup=True)
-        loss = out["loss"]
+        loss = m(x, lab, deepsup=True)["loss"]
         loss.backward()
         grads = {k: p.grad.detach() for k, p in m.named_parameters()}
         bn_names = [n for n, mod in m.named_modules() if isinstance(mod, torch.nn.BatchNorm2d)]
         res["loss" + sfx] = np.array(loss.item(), dtype=np.float64)
-        res["bn_wgrad" + sfx] = torch.cat([grads[n + ".weight"].reshape(-1) for n in bn_names]).numpy()
-        res["bn_bgrad" + sfx] = torch.cat([grads[n + ".bias"].reshape(-1) for n in bn_names]).numpy()
-        for cname in ("backbone.conv1.0", "backbone.layer1.0.conv1", "backbone.layer2.0.conv2", "last_conv.6"):
-            res["wgrad:" + cname + ":" + sfx] = grads[cname + ".weight"].numpy()
-        res["bgrad:last_conv.6:" + sfx] = grads["last_conv.6.bias"].numpy()
-        # every parameter gradient, compactly: L2 norm and a projection on a fixed cos vector
-        pnames = [k for k, _ in m.named_parameters()]
-        res["grad_l2:" + sfx] = np.array([float(grads[k].double().norm()) for k in pnames])
-        res["grad_proj:" + sfx] = np.array([
-            float((grads[k].double().reshape(-1) * torch.cos(0.37 * torch.arange(grads[k].numel(), dtype=torch.float64))).sum())
-            for k in pnames])
+        flat = {"bn_wgrad": torch.cat([grads[n + ".weight"].reshape(-1) for n in bn_names]),
+                "bn_bgrad": torch.cat([grads[n + ".bias"].reshape(-1) for n in bn_names])}
+        for cname in tuple(convs) + (cls,):
+            flat["wgrad:" + cname + ":"] = grads[cname + ".weight"]
+        flat["bgrad:" + cls + ":"] = grads[cls + ".bias"]
+        for k, v in flat.items():
+            if compact and sfx == "64":
+                res[k + "d64m32"] = (v - torch.from_numpy(res[k + "32"]).double()).float().numpy()
+            else:
+                res[k + sfx] = v.numpy()
+        pnames = _grad_summaries(m, res, sfx)
         if sfx == "32":
             res["param_names"] = np.array(pnames)
         # running stats after the training-mode forward
         sd = m.state_dict()
-        res["rm:backbone.bn1:" + sfx] = sd["backbone.bn1.running_mean"].numpy()
-        res["rv:backbone.bn1:" + sfx] = sd["backbone.bn1.running_var"].numpy()
+        for bn in running:
+            res[f"rm:{bn}:" + sfx] = sd[bn + ".running_mean"].numpy()
+            res[f"rv:{bn}:" + sfx] = sd[bn + ".running_var"].numpy()
         # logits of both heads: second (eval-free) pass in train mode would re-update stats, so
         # take them from a fresh identical model
         m2 = build_ref(model, backbone, align, dtype)
         m2.train()
         with torch.no_grad():
             outs = m2(x, None, deepsup=True)
-        # stored at every 2nd pixel (fixture size); fp64 kept as the difference to fp32
+        # stored sub-sampled; fp64 kept as the difference to fp32
+        s = logit_step
         if sfx == "32":
-            l32 = [o[:, :, ::2, ::2].clone() for o in outs]
+            l32 = [o[:, :, ::s, ::s].clone() for o in outs]
             res["logits32"] = l32[0].numpy()
             res["logits_ds32"] = l32[1].numpy()
-        else:
-            res["logits_d64m32"] = (outs[0][:, :, ::2, ::2] - l32[0].double()).float().numpy()
-            res["logits_ds_d64m32"] = (outs[1][:, :, ::2, ::2] - l32[1].double()).float().numpy()
-        if sfx == "32":
             res["bn_names"] = np.array(bn_names)
             res["state_keys"] = np.array(list(sd.keys()))
             res["state_shapes"] = np.array([str(tuple(v.shape)) for v in sd.values()])
             res["ignore_prune_layer"] = np.array(m.ignore_prune_layer)
+        else:
+            res["logits_d64m32"] = (outs[0][:, :, ::s, ::s] - l32[0].double()).float().numpy()
+            res["logits_ds_d64m32"] = (outs[1][:, :, ::s, ::s] - l32[1].double()).float().numpy()
     # Round 4: the SAME fp32 reference code in four more summation orders (1 / 2 / 4 threads, oneDNN off) - only the two
     # per-tensor gradient summaries.  One fp32 run is one draw of a tensor's fp32-vs-fp64 error (which near-zero
     # pre-activations get the other ReLU mask); the per-tensor bound of tests/_parity.py takes the tensor's error as the
@@ -143,16 +162,13 @@ def whole_model(tag, model, backbone, N, H, W, align):
         x = fill.closed_form_input(N, H, W, torch.float32)
         lab = fill.closed_form_labels(N, H, W)
         m(x, lab, deepsup=True)["loss"].backward()
-        grads = {k: p.grad.detach() for k, p in m.named_parameters()}
-        pnames = [k for k, _ in m.named_parameters()]
-        res["grad_l2:" + sfx] = np.array([float(grads[k].double().norm()) for k in pnames])
-        res["grad_proj:" + sfx] = np.array([
-            float((grads[k].double().reshape(-1) * torch.cos(0.37 * torch.arange(grads[k].numel(), dtype=torch.float64))).sum())
-            for k in pnames])
+        _grad_summaries(m, res, sfx)
     torch.set_num_threads(8)
     torch.backends.mkldnn.enabled = True
     res["fp32_variants"] = np.array(["32"] + [v[0] for v in variants])
     res["meta"] = np.array([N, H, W, int(align)])
+    if logit_step != 2:
+        res["logit_step"] = np.array(logit_step)
     np.savez_compressed(os.path.join(OUT, f"model_{tag}.npz"), **res)
     print("wrote", tag, "loss32", res["loss32"], "loss64", res["loss64"])
 
@@ -195,8 +211,20 @@ PRUNE_CASES = [("v3r50", "deeplabv3", "resnet50", True, 0.5), ("v3r50", "deeplab
                ("v3r101", "deeplabv3", "resnet101", True, 0.5), ("simple_r50", "simple", "resnet50", False, 0.5)]
 
 
-def masks_and_surgery(only=None):
-    for tag, model, backbone, align, gp in PRUNE_CASES:
+# the heads added after DeepLabv3: command-line key -> what their whole-model, prune and flops fixtures are made from
+HEADS = {
+    "v3p": dict(model="deeplabv3p", tag="v3p_r50_2x65x65", prune_tag="v3pr50", flops_file="flops_v3p.npz",
+                cls="decoder.last_conv.6", convs=("backbone.conv1.0", "backbone.layer1.0.conv1", "decoder.conv1"),
+                running=("backbone.bn1", "decoder.bn1")),
+    # (the running statistics of the first pyramid stage's BatchNorm - N values per channel - and of the bottleneck's)
+    "psp": dict(model="psp", tag="psp_r50_2x65x65", prune_tag="pspr50", flops_file="flops_psp.npz",
+                cls="last_conv", convs=("backbone.conv1.0", "backbone.layer1.0.conv1"),
+                running=("backbone.bn1", "ppm.stages.0.2", "ppm.bottleneck.1")),
+}
+
+
+def masks_and_surgery(only=None, cases=None):
+    for tag, model, backbone, align, gp in (PRUNE_CASES if cases is None else cases):
         if only is not None and tag not in only:
             continue
         torch.manual_seed(0)
@@ -267,14 +295,15 @@ def ohem_cases():
     np.savez_compressed(os.path.join(OUT, "ohem_threshold.npz"), **rec)
 
 
-def flops_golden():
-    """utils/flops_counter.get_model_complexity_info on the full and the pruned v3-R50
+def flops_golden(model="deeplabv3", short="v3", backbones=("resnet50", "resnet101"), fname="flops.npz"):
+    """utils/flops_counter.get_model_complexity_info on the full models and on the R50 pruned at global_percent 0.5
     (prune.py:77-78,112-113), input (3,257,257) to keep the CPU forward short."""
     from utils.flops_counter import get_model_complexity_info
     import copy
+    cls = getattr(networks, model).Seg_Model
     rec = {}
-    for tag, bb in (("v3_r50", "resnet50"), ("v3_r101", "resnet101")):
-        cls = networks.deeplabv3.Seg_Model
+    for bb in backbones:
+        tag = short + "_" + bb.replace("resnet", "r")
         m = cls(backbone=bb, backbone_para=dict(BB_PARA), model_para={}, num_classes=19, align_corner=True,
                 criterion=None, deepsup=False)
         f, pcount = get_model_complexity_info(m, (3, 257, 257), print_per_layer_stat=False, as_strings=False)
@@ -282,18 +311,18 @@ def flops_golden():
         rec[f"flops:{tag}"] = np.array(float(f)); rec[f"params:{tag}"] = np.array(float(pcount))
         rec[f"str:{tag}"] = np.array([fs, ps])
     # pruned model at global_percent 0.5
-    m = build_ref("deeplabv3", "resnet50", True, torch.float32)
+    m = build_ref(model, "resnet50", True, torch.float32)
     m.criterion = None
     torch.save({"eic": synthetic_scores(m)}, "/tmp/_golden_score.pth")
     pruner = dp.DCFPPruner(global_percent=0.5, layer_keep=0.02, score_file="/tmp/_golden_score.pth")
     pruned, channel_cfg = pruner.prune_model(copy.deepcopy(m), except_start_keys=["conv_deepsup"])
-    slim = networks.deeplabv3.Seg_Model(backbone="resnet50", backbone_para=dict(BB_PARA), model_para={},
-                                        num_classes=19, align_corner=True, criterion=None, deepsup=False)
+    slim = cls(backbone="resnet50", backbone_para=dict(BB_PARA), model_para={},
+               num_classes=19, align_corner=True, criterion=None, deepsup=False)
     pruners.init_pruned_model(slim, channel_cfg)
     f, pcount = get_model_complexity_info(slim, (3, 257, 257), print_per_layer_stat=False, as_strings=False)
-    rec["flops:v3_r50_gp50"] = np.array(float(f)); rec["params:v3_r50_gp50"] = np.array(float(pcount))
-    np.savez_compressed(os.path.join(OUT, "flops.npz"), **rec)
-    print("wrote flops golden", {k: (v.tolist() if v.dtype.kind != "U" else v.tolist()) for k, v in rec.items()})
+    rec[f"flops:{short}_r50_gp50"] = np.array(float(f)); rec[f"params:{short}_r50_gp50"] = np.array(float(pcount))
+    np.savez_compressed(os.path.join(OUT, fname), **rec)
+    print("wrote", fname, {k: v.tolist() for k, v in rec.items()})
 
 
 def gsrl_golden():
@@ -428,9 +457,14 @@ def trajectory_golden(steps=30):
 
 
 if __name__ == "__main__":
+    args = sys.argv[1:]
+    if "--out" in args:
+        i = args.index("--out")
+        OUT = os.path.abspath(args[i + 1])
+        del args[i:i + 2]
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
-    which = sys.argv[1:] or ["eic", "lr", "ohem", "simple", "v3r50", "v3r101", "prune", "flops", "gsrl"]
+    which = args or ["eic", "lr", "ohem", "simple", "v3r50", "v3r101", "prune", "flops", "gsrl"]
     if "eic" in which:
         eic_trajectory()
     if "lr" in which:
@@ -455,3 +489,11 @@ if __name__ == "__main__":
         eval_golden()
     if "trajectory" in which:    # added in round 4 (likewise)
         trajectory_golden()
+    for key, h in HEADS.items():     # `v3p`, `psp`: all three fixtures of the head; `v3p:model` etc.: one of them
+        if key in which or key + ":model" in which:
+            whole_model(h["tag"], h["model"], "resnet50", 2, 65, 65, True, cls=h["cls"], convs=h["convs"],
+                        running=h["running"], logit_step=4, compact=True)
+        if key in which or key + ":prune" in which:
+            masks_and_surgery(cases=[(h["prune_tag"], h["model"], "resnet50", True, 0.5)])
+        if key in which or key + ":flops" in which:
+            flops_golden(h["model"], key, ("resnet50",), h["flops_file"])

@@ -1,0 +1,385 @@
+"""What the whole-model tests of every head share (tests/test_model_gpu.py, test_deeplabv3p_*.py, test_psp_*.py):
+one record per whole-model fixture (CASES), the fixture reader that hides its two fp64 encodings (load_golden), the
+comparison against it (compare_to_golden: numpy only, tests/test_model_cases_cpu.py runs it without a GPU) and the
+bodies of the tests every head has - slim model, data-parallel child, train -> prune tools, and the host-side trio
+(module tree, prune_model, flops counter).  A plain helper module like tests/_parity.py: no fixtures, no tests.
+What is specific to a head stays in that head's test file and comes in as a parameter."""
+import collections
+import copy
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:         # (also imported by the data-parallel child, which runs as a script)
+    sys.path.insert(0, ROOT)
+
+from oracle import fill  # noqa: E402
+from oracle.make_scores import synthetic_scores  # noqa: E402
+from _parity import check_per_tensor, check_rankwise  # noqa: E402
+
+G = os.path.join(os.path.dirname(__file__), "golden")
+BB = {"os": 8, "mg_unit": [1, 2, 4], "inplanes": 128, "pretrained": False}
+
+# convs: those whose whole weight gradient the fixture stores (the classifier last); running: the BatchNorms whose
+# running statistics it stores; running_rel: False - max|mine - fp64| < 1e-5; True - <= max(1e-5, 3 max|fp32 - fp64|)
+# (PSPNet: the first pyramid stage's BatchNorm sees N values per channel, the bottleneck's a 4096-channel 3x3 sum - the
+# reference's own fp32 run is up to 3.7e-5 from fp64 there)
+Case = collections.namedtuple("Case", "tag model backbone classifier convs running running_rel")
+_V3_CONVS = ("backbone.conv1.0", "backbone.layer1.0.conv1", "backbone.layer2.0.conv2", "last_conv.6")
+CASES = {c.tag: c for c in (
+    Case("simple_r50_4x64x64", "simple", "resnet50", "last_conv.6", _V3_CONVS, ("backbone.bn1",), False),
+    Case("v3_r50_2x65x65", "deeplabv3", "resnet50", "last_conv.6", _V3_CONVS, ("backbone.bn1",), False),
+    Case("v3_r101_2x65x65", "deeplabv3", "resnet101", "last_conv.6", _V3_CONVS, ("backbone.bn1",), False),
+    Case("v3p_r50_2x65x65", "deeplabv3p", "resnet50", "decoder.last_conv.6",
+         ("backbone.conv1.0", "backbone.layer1.0.conv1", "decoder.conv1", "decoder.last_conv.6"),
+         ("backbone.bn1", "decoder.bn1"), False),
+    Case("psp_r50_2x65x65", "psp", "resnet50", "last_conv",
+         ("backbone.conv1.0", "backbone.layer1.0.conv1", "last_conv"),
+         ("backbone.bn1", "ppm.stages.0.2", "ppm.bottleneck.1"), True),
+)}
+
+
+class _DS:
+    ignore_label = 255
+    num_classes = 19
+    class_weights = None
+
+
+def build_model(name, backbone, align, device, criterion=True, deepsup=True):
+    """The product Seg_Model `name` with the closed-form weights, in training mode on `device`."""
+    from dcfp_amd import networks
+    from dcfp_amd.loss.criterion import build_criterions
+    crit = build_criterions("ce", _DS(), {"ds_weight": 0.4}) if criterion else None
+    m = getattr(networks, name).Seg_Model(backbone=backbone, backbone_para=dict(BB), num_classes=19, align_corner=align,
+                                          criterion=crit, deepsup=deepsup)
+    m.load_state_dict(fill.closed_form_state(m.state_dict()))
+    if deepsup:
+        m.conv_deepsup[3].p = 0.0
+    return m.to(device).train()
+
+
+class Golden:
+    """A whole-model fixture (oracle/make_golden.py whole_model).  f32(k) / f64(k): the reference's fp32 / fp64 array
+    `k` as float64, whichever way the file holds fp64 - under k + "64", or as the float32 difference k + "d64m32" to the
+    fp32 array (logits are always kept that way).  Everything else is read with [] as from the npz."""
+
+    def __init__(self, tag):
+        self.tag = tag
+        self.g = np.load(os.path.join(G, f"model_{tag}.npz"))
+        self.N, self.H, self.W, self.align = [int(v) for v in self.g["meta"]]
+        self.logit_step = int(self.g["logit_step"]) if "logit_step" in self.g.files else 2
+        self.variants = [str(v) for v in self.g["fp32_variants"]]
+
+    def __getitem__(self, k):
+        return self.g[k]
+
+    def f32(self, k):
+        return self.g[k + "32"].astype(np.float64)
+
+    def f64(self, k):
+        if k + "64" in self.g.files:
+            return self.g[k + "64"].astype(np.float64)
+        return self.f32(k) + self.g[k + "d64m32"]
+
+
+def load_golden(tag):
+    return Golden(tag)
+
+
+def compare_to_golden(rec, gold, case, capsys=None):
+    """The acceptance of a whole-model run against its fixture.  rec: "loss"; "out_shapes" (both heads' full logits
+    shapes); "logits" / "logits_ds" at every gold.logit_step-th pixel; "bn_wgrad" / "bn_bgrad" (the BatchNorm gamma /
+    beta gradients concatenated in gold["bn_names"] order); "grad_l2" / "grad_proj" (per parameter of
+    gold["param_names"]: the gradient's L2 norm and its projection on cos(0.37 i)); "wgrad" {conv: weight gradient} for
+    case.convs; "rm" / "rv" {BatchNorm: running mean / var} for case.running.  All numpy / float."""
+    g = gold
+    ref64, ref32 = float(g["loss64"]), float(g["loss32"])
+    assert abs(rec["loss"] - ref64) <= max(1e-5 * abs(ref64), 3 * abs(ref32 - ref64)), (rec["loss"], ref32, ref64)
+
+    assert [tuple(s) for s in rec["out_shapes"]] == [(g.N, 19, g.H, g.W)] * 2, rec["out_shapes"]
+    for key in ("logits", "logits_ds"):
+        l64 = g.f32(key) + g[key + "_d64m32"]
+        err = np.abs(np.asarray(rec[key], dtype=np.float64) - l64).max()
+        ref_err = np.abs(g[key + "_d64m32"]).max()
+        assert err <= max(1e-3, 3 * ref_err), (key, err, ref_err)
+
+    def rel_l2(what, mine):
+        # bounded by the reference's own fp32-vs-fp64 noise only (no fixed 5e-2 floor)
+        r32, r64 = g.f32(what), g.f64(what)
+        rel = np.linalg.norm(np.asarray(mine, dtype=np.float64) - r64) / np.linalg.norm(r64)
+        ref_rel = np.linalg.norm(r32 - r64) / np.linalg.norm(r64)
+        assert rel <= max(1e-3, 3 * ref_rel), (what, rel, ref_rel)
+    # BN gamma / beta gradients: the statistic that feeds the EIC score
+    for what in ("bn_wgrad", "bn_bgrad"):
+        rel_l2(what, rec[what])
+
+    # every parameter gradient through its L2 norm (the fixture holds norms for all ~160-310 tensors).  The reference's
+    # own fp32-vs-fp64 error of a tensor: the largest over its five fp32 summation orders (8 / 4 / 2 / 1 threads, oneDNN
+    # off - oracle/make_golden.py); one fp32 run is a single draw of that error
+    pn = g["param_names"].tolist()
+    l64 = g["grad_l2:64"]
+    rel = np.abs(rec["grad_l2"] - l64) / (np.abs(l64) + 1e-12)
+    ref_rel = np.max([np.abs(g["grad_l2:" + v] - l64) for v in g.variants], axis=0) / (np.abs(l64) + 1e-12)
+    # PER TENSOR (tests/_parity.py): a tensor passes iff its error is within max(floor, 3x the reference's own fp32-vs-fp64
+    # error on that tensor); floor = min(5e-2, 3x the reference's worst tensor) - 1.5e-2 on `simple`, 5e-2 on v3
+    check_per_tensor(rel, ref_rel, pn, f"{g.tag} gradient norms", capsys)
+    # ... and through a fixed-cosine projection, which (unlike a norm) sees permuted / transposed gradients:
+    # a random error of relative size e moves the projection by ~ e * |g| / sqrt(2)
+    p64 = g["grad_proj:64"]
+    perr = np.abs(rec["grad_proj"] - p64) / (np.abs(l64) + 1e-12)
+    pref = np.max([np.abs(g["grad_proj:" + v] - p64) for v in g.variants], axis=0) / (np.abs(l64) + 1e-12)
+    check_rankwise(perr, pref, pn, f"{g.tag} gradient projections", capsys)     # (why rank-wise: tests/_parity.py)
+    for key in case.convs:
+        rel_l2(f"wgrad:{key}:", rec["wgrad"][key])
+    for bn in case.running:
+        for what in ("rm", "rv"):
+            mine, r64 = np.asarray(rec[what][bn], dtype=np.float64), g[f"{what}:{bn}:64"]
+            err = np.abs(mine - r64).max()
+            if case.running_rel:
+                assert err <= max(1e-5, 3 * np.abs(g[f"{what}:{bn}:32"] - r64).max()), (bn, what, err)
+            else:
+                assert err < 1e-5, (bn, what, err)
+
+
+def collect_record(model, fresh_model, x, lab, gold, case):
+    """The GPU half: one training-mode forward + backward of `model`, and the logits of `fresh_model` (an identical
+    model, so that the BatchNorm running statistics match the fixture's) -> the record compare_to_golden takes."""
+    loss = model(x, lab, deepsup=True)["loss"]
+    loss.backward()
+    torch.cuda.synchronize()
+    with torch.no_grad():
+        outs = fresh_model(x, None, deepsup=True)
+    s = gold.logit_step
+    rec = {"loss": loss.item(), "out_shapes": [tuple(o.shape) for o in outs[:2]],
+           "logits": outs[0][:, :, ::s, ::s].double().cpu().numpy(),
+           "logits_ds": outs[1][:, :, ::s, ::s].double().cpu().numpy()}
+    mods = dict(model.named_modules())
+    for what, attr in (("bn_wgrad", "weight"), ("bn_bgrad", "bias")):
+        rec[what] = torch.cat([getattr(mods[n], attr).grad.reshape(-1)
+                               for n in gold["bn_names"].tolist()]).double().cpu().numpy()
+    params = dict(model.named_parameters())
+    pn = gold["param_names"].tolist()
+    rec["grad_l2"] = np.array([float(params[k].grad.double().norm()) for k in pn])
+    rec["grad_proj"] = np.array([float((params[k].grad.double().reshape(-1) * torch.cos(
+        0.37 * torch.arange(params[k].numel(), dtype=torch.float64, device=x.device))).sum()) for k in pn])
+    rec["wgrad"] = {k: params[k + ".weight"].grad.double().cpu().numpy() for k in case.convs}
+    sd = model.state_dict()
+    rec["rm"] = {bn: sd[bn + ".running_mean"].double().cpu().numpy() for bn in case.running}
+    rec["rv"] = {bn: sd[bn + ".running_var"].double().cpu().numpy() for bn in case.running}
+    return rec
+
+
+def forward_backward_vs_golden(tag, device, capsys):
+    """test_forward_backward_vs_reference_golden of every head."""
+    case, gold = CASES[tag], load_golden(tag)
+    x = fill.closed_form_input(gold.N, gold.H, gold.W).to(device)
+    lab = fill.closed_form_labels(gold.N, gold.H, gold.W).to(device)
+    m, m2 = (build_model(case.model, case.backbone, bool(gold.align), device) for _ in range(2))
+    compare_to_golden(collect_record(m, m2, x, lab, gold, case), gold, case, capsys)
+
+
+def _prune_gp50(m, score_path):
+    """The reference's global_percent 0.5 pruning of `m` on the synthetic scores: (pruner, pruned model, channel_cfg)."""
+    from dcfp_amd.pruners.dcfp_pruner import DCFPPruner
+    torch.save({"eic": synthetic_scores(m)}, score_path)
+    pruner = DCFPPruner(global_percent=0.5, layer_keep=0.02, score_file=score_path)
+    pruned, cfg = pruner.prune_model(copy.deepcopy(m), except_start_keys=["conv_deepsup"])
+    return pruner, pruned, cfg
+
+
+def slim_model_logits_check(model_name, prune_tag, device, tmp_path, check_slim):
+    """init_pruned_model from the reference-identical channel_cfg (the head's host test holds it to the golden bit for
+    bit), the pruned weights loaded, eval mode at 2x3x33x33: the reference's slim logits.  check_slim(slim): the head's
+    own assertions on the slim model's ragged widths."""
+    from dcfp_amd import pruners
+    g = np.load(os.path.join(G, f"prune_{prune_tag}_gp50.npz"))
+    cpu = torch.device("cpu")
+    m = build_model(model_name, "resnet50", True, cpu, criterion=False)
+    _, pruned, cfg = _prune_gp50(m, str(tmp_path / "score.pth"))
+    assert list(cfg.keys()) == g["names"].tolist()
+    slim = build_model(model_name, "resnet50", True, cpu, criterion=False)
+    pruners.init_pruned_model(slim, cfg)
+    slim.load_state_dict(pruned.state_dict())
+    check_slim(slim)
+    slim = slim.to(device).eval()
+    with torch.no_grad():
+        y = slim(fill.closed_form_input(2, 33, 33).to(device), None, deepsup=True)
+    err = np.abs(y[0].double().cpu().numpy() - g["slim_logits"]).max()
+    assert err <= 1e-3, err
+
+
+def ddp_child(model_name, port, syncbn_probe):
+    """The child process of data_parallel_bit_identical: one plain step and one through Engine.data_parallel at world
+    size 1 (SyncBN exchange rehearsed), compared bit for bit; prints DDP_RESULT + json.  syncbn_probe(model): a
+    BatchNorm of the head that must have become a SyncBatchNorm."""
+    import argparse
+    import torch.distributed as dist
+    from dcfp_amd import pruners, optimizer as opt
+    from dcfp_amd.engine import Engine, DataParallel
+
+    class A:
+        no_decay = "bn"; optim = "sgd"; momentum = 0.9; learning_rate = 1e-3; weight_decay = 5e-4
+    dev = torch.device("cuda:0")
+    x = fill.closed_form_input(2, 129, 129).to(dev)
+    lab = fill.closed_form_labels(2, 129, 129).to(dev)
+
+    def run(ddp):
+        torch.manual_seed(12345)
+        m = build_model(model_name, "resnet50", True, dev)
+        optimizer = opt.build_optimizer(A, m)
+        optimizer.zero_grad()
+        tp = pruners.dcfp_pruning(m, 0.999)
+        if ddp:
+            sys.argv = ["x"]
+            eng = Engine(custom_parser=argparse.ArgumentParser())
+            eng.distributed = True
+            model = eng.data_parallel(m)
+            assert isinstance(model, DataParallel)
+            assert isinstance(syncbn_probe(m), torch.nn.SyncBatchNorm)
+        else:
+            model = m
+        loss = model(x, lab, deepsup=True)["loss"]
+        lv = (eng.all_reduce_tensor(loss) if ddp else loss).item()
+        loss.backward()
+        tp.step(m)
+        grads = {k: p.grad.detach().clone() for k, p in m.named_parameters()}
+        eic = torch.cat([tp.get_eic()["eic"][n].reshape(-1) for n in tp._names]).clone()
+        optimizer.step()
+        torch.cuda.synchronize()
+        bufs = {k: v.detach().clone() for k, v in m.state_dict().items()}
+        return lv, grads, eic, bufs
+
+    plain = run(False)
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), DCFP_FORCE_SYNCBN="1")
+    dist.init_process_group("nccl", rank=0, world_size=1)
+    ddp = run(True)
+    dist.destroy_process_group()
+    out = {"loss": [plain[0], ddp[0]], "grad_diff": [k for k in plain[1] if not torch.equal(plain[1][k], ddp[1][k])],
+           "eic_equal": bool(torch.equal(plain[2], ddp[2])),
+           "state_diff": [k for k in plain[3] if not torch.equal(plain[3][k], ddp[3][k])], "n_params": len(plain[1])}
+    print("DDP_RESULT " + json.dumps(out))
+
+
+def data_parallel_bit_identical(test_file):
+    """Parent side: starts `test_file --ddp-child` (which calls ddp_child) as a fresh process and asserts its result."""
+    env = dict(os.environ, DCFP_FANIN_BN_SUMS="2")
+    env.pop("DCFP_FORCE_SYNCBN", None)
+    r = subprocess.run([sys.executable, os.path.abspath(test_file), "--ddp-child"], env=env, capture_output=True,
+                       text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    rec = json.loads([l for l in r.stdout.splitlines() if l.startswith("DDP_RESULT ")][-1][len("DDP_RESULT "):])
+    assert rec["loss"][0] == rec["loss"][1], rec["loss"]
+    assert rec["grad_diff"] == [], rec["grad_diff"][:8]
+    assert rec["eic_equal"]
+    assert rec["state_diff"] == [], rec["state_diff"][:8]
+    assert rec["n_params"] > 150
+
+
+def train_then_prune(tag, expect_cfg_keys, tmp_path):
+    """tools/train.py (3 steps, dcfp scores) -> score.pth -> tools/prune.py with --model of the case `tag`;
+    expect_cfg_keys: convs of the head that must appear in the channel_cfg."""
+    g = np.load(os.path.join(G, f"model_{tag}.npz"))
+    model_name = CASES[tag].model
+    snap = str(tmp_path / "snap")
+    bb = json.dumps({"pretrained": False})
+    cmd = [sys.executable, os.path.join(ROOT, "tools", "train.py"), "--model", model_name, "--ddp", "False",
+           "--prune-type", "dcfp", "--input-size", "129,129", "--batch-size", "2", "--num-steps", "3",
+           "--snapshot-dir", snap, "--backbone-para", bb, "--learning-rate", "1e-3"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    losses = [float(l.split("loss=")[1]) for l in r.stdout.splitlines() if "loss=" in l]
+    assert len(losses) == 3 and all(np.isfinite(losses)), r.stdout[-2000:]
+    score = torch.load(os.path.join(snap, "score.pth"), weights_only=False)
+    ign = set(g["ignore_prune_layer"].tolist())
+    assert list(score["eic"].keys()) == [n for n in g["bn_names"].tolist() if n not in ign]
+    ckpt = os.path.join(snap, "CS_scenes_3.pth")
+    out = str(tmp_path / "pruned")
+    cmd = [sys.executable, os.path.join(ROOT, "tools", "prune.py"), "--model", model_name, "--model-path", ckpt,
+           "--score-path", os.path.join(snap, "score.pth"), "--save-path", out, "--backbone-para", bb]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    cfg = torch.load(os.path.join(out, "channel_cfg.pth"), weights_only=False)
+    assert all(k in cfg for k in expect_cfg_keys), [k for k in expect_cfg_keys if k not in cfg]
+
+
+# ---- host side (no GPU)
+def host_model(model_name, deepsup=True):
+    return build_model(model_name, "resnet50", True, torch.device("cpu"), criterion=False, deepsup=deepsup)
+
+
+def module_tree_check(tag):
+    """Module tree, state_dict, ignore_prune_layer, parameter and BatchNorm names against the whole-model fixture.
+    Returns (model, fixture) for the head's own assertions."""
+    g = np.load(os.path.join(G, f"model_{tag}.npz"))
+    m = host_model(CASES[tag].model)
+    sd = m.state_dict()
+    assert list(sd.keys()) == g["state_keys"].tolist()
+    assert [str(tuple(v.shape)) for v in sd.values()] == g["state_shapes"].tolist()
+    assert m.ignore_prune_layer == g["ignore_prune_layer"].tolist()
+    assert [n for n, p in m.named_parameters()] == g["param_names"].tolist()
+    bns = [n for n, mod in m.named_modules() if isinstance(mod, torch.nn.BatchNorm2d)]
+    assert bns == g["bn_names"].tolist()
+    return m, g
+
+
+def prune_model_check(model_name, prune_tag, tmp_path):
+    """prune_model at global_percent 0.5 against the prune fixture: the static graph, the thresholds, every mask bit,
+    the pruned weights and init_pruned_model's slim shapes.  Returns the channel_cfg for the head's own assertions."""
+    from dcfp_amd import pruners
+    g = np.load(os.path.join(G, f"prune_{prune_tag}_gp50.npz"))
+    m = host_model(model_name)
+    pruner, pruned, cfg = _prune_gp50(m, str(tmp_path / "score.pth"))
+
+    assert dict(zip(g["norm_conv_bn"].tolist(), g["norm_conv_conv"].tolist())) == pruner.norm_conv_links
+    assert sorted(g["except_layers"].tolist()) == sorted(pruner.except_layers)
+    assert sorted(g["groups"].tolist()) == sorted(",".join(sorted(v)) for v in pruner.same_out_channel_groups.values())
+    th = pruner.get_thresh()
+    assert np.array_equal(np.array([float(th[0]), float(th[1])], dtype=np.float32), g["thresh"])
+
+    assert list(cfg.keys()) == g["names"].tolist()
+    for name, c in cfg.items():
+        for kind in ("in", "out"):
+            if kind + "_mask" in c:
+                ref = np.unpackbits(g[f"{kind}:{name}"])[:c[f"raw_{kind}_channels"]]
+                assert np.array_equal(c[kind + "_mask"].reshape(-1).astype(np.uint8), ref), (name, kind)
+                assert [c[kind + "_channels"], c[f"raw_{kind}_channels"]] == g[f"{kind}_n:{name}"].tolist()
+
+    sd = pruned.state_dict()
+    assert list(sd.keys()) == g["pruned_keys"].tolist()
+    assert [str(tuple(v.shape)) for v in sd.values()] == g["pruned_shapes"].tolist()
+    sums = np.array([float(v.double().sum()) for v in sd.values()])
+    abss = np.array([float(v.double().abs().sum()) for v in sd.values()])
+    assert np.allclose(sums, g["pruned_sum"], rtol=1e-9, atol=1e-9)
+    assert np.allclose(abss, g["pruned_abs"], rtol=1e-9, atol=1e-9)
+
+    slim = host_model(model_name)
+    pruners.init_pruned_model(slim, cfg)
+    assert [str(tuple(v.shape)) for v in slim.state_dict().values()] == g["slim_shapes"].tolist()
+    slim.load_state_dict(sd)
+    return cfg
+
+
+def flops_counter_check(model_name, flops_file, key, tmp_path):
+    """get_model_complexity_info on the full and the global_percent 0.5 model at (3, 257, 257) against the flops
+    fixture's entries `key` and `key`_gp50."""
+    from dcfp_amd import networks, pruners
+    from dcfp_amd.utils.flops_counter import get_model_complexity_info
+    g = np.load(os.path.join(G, flops_file))
+
+    def bare():
+        return getattr(networks, model_name).Seg_Model(backbone="resnet50", backbone_para=dict(BB), num_classes=19,
+                                                       align_corner=True, deepsup=False)
+    m = bare()
+    f, p = get_model_complexity_info(m, (3, 257, 257), print_per_layer_stat=False, as_strings=False)
+    assert float(f) == float(g[f"flops:{key}"]) and float(p) == float(g[f"params:{key}"])
+    assert list(get_model_complexity_info(m, (3, 257, 257), print_per_layer_stat=False)) == g[f"str:{key}"].tolist()
+    _, _, cfg = _prune_gp50(host_model(model_name), str(tmp_path / "score.pth"))
+    slim = bare()
+    pruners.init_pruned_model(slim, cfg)
+    f, p = get_model_complexity_info(slim, (3, 257, 257), print_per_layer_stat=False, as_strings=False)
+    assert float(f) == float(g[f"flops:{key}_gp50"]) and float(p) == float(g[f"params:{key}_gp50"])

@@ -11,100 +11,15 @@ import torch
 
 from oracle import fill, model as omodel, scoring
 from oracle.train_step import CpuTrainer
-from _parity import check_per_tensor, check_rankwise
+from _model_cases import CASES as MODEL_CASES, G, build_model as build, forward_backward_vs_golden
 
 pytestmark = pytest.mark.gpu
-G = os.path.join(os.path.dirname(__file__), "golden")
-BB = {"os": 8, "mg_unit": [1, 2, 4], "inplanes": 128, "pretrained": False}
-
-
-class _DS:
-    ignore_label = 255
-    num_classes = 19
-    class_weights = None
-
-
-def build(model_name, backbone, align, device):
-    from dcfp_amd import networks
-    from dcfp_amd.loss.criterion import build_criterions
-    crit = build_criterions("ce", _DS(), {"ds_weight": 0.4})
-    m = getattr(networks, model_name).Seg_Model(backbone=backbone, backbone_para=dict(BB), num_classes=19,
-                                                align_corner=align, criterion=crit, deepsup=True)
-    m.load_state_dict(fill.closed_form_state(m.state_dict()))
-    m.conv_deepsup[3].p = 0.0
-    return m.to(device).train()
-
-
-CASES = [("simple_r50_4x64x64", "simple", "resnet50"), ("v3_r50_2x65x65", "deeplabv3", "resnet50"),
-         ("v3_r101_2x65x65", "deeplabv3", "resnet101")]
+CASES = [(c.tag, c.model, c.backbone) for c in MODEL_CASES.values() if c.model in ("simple", "deeplabv3")]
 
 
 @pytest.mark.parametrize("tag,model_name,backbone", CASES)
 def test_forward_backward_vs_reference_golden(cuda, capsys, tag, model_name, backbone):
-    g = np.load(os.path.join(G, f"model_{tag}.npz"))
-    N, H, W, align = [int(v) for v in g["meta"]]
-    m = build(model_name, backbone, bool(align), cuda)
-    x = fill.closed_form_input(N, H, W).to(cuda)
-    lab = fill.closed_form_labels(N, H, W).to(cuda)
-    out = m(x, lab, deepsup=True)
-    loss = out["loss"]
-    loss.backward()
-    torch.cuda.synchronize()
-
-    ref64 = float(g["loss64"]); ref32 = float(g["loss32"])
-    assert abs(loss.item() - ref64) <= max(1e-5 * abs(ref64), 3 * abs(ref32 - ref64)), (loss.item(), ref32, ref64)
-
-    # logits (inference-style call on a fresh model so BN running stats match the golden's)
-    m2 = build(model_name, backbone, bool(align), cuda)
-    with torch.no_grad():
-        outs = m2(x, None, deepsup=True)
-    for o, key, dkey in ((outs[0], "logits32", "logits_d64m32"), (outs[1], "logits_ds32", "logits_ds_d64m32")):
-        l64 = g[key].astype(np.float64) + g[dkey]
-        err = np.abs(o[:, :, ::2, ::2].double().cpu().numpy() - l64).max()
-        ref_err = np.abs(g[dkey]).max()
-        assert err <= max(1e-3, 3 * ref_err), (key, err, ref_err)
-
-    # BN gamma / beta gradients: the statistic that feeds the EIC score
-    names = g["bn_names"].tolist()
-    mods = dict(m.named_modules())
-    for what, attr in (("bn_wgrad", "weight"), ("bn_bgrad", "bias")):
-        mine = torch.cat([getattr(mods[n], attr).grad.reshape(-1) for n in names]).double().cpu().numpy()
-        r64, r32 = g[what + "64"], g[what + "32"]
-        rel = np.linalg.norm(mine - r64) / np.linalg.norm(r64)
-        ref_rel = np.linalg.norm(r32 - r64) / np.linalg.norm(r64)
-        # bounded by the reference's own fp32-vs-fp64 noise only (no fixed 5e-2 floor)
-        assert rel <= max(1e-3, 3 * ref_rel), (what, rel, ref_rel)
-
-    # every parameter gradient through its L2 norm (fixture holds norms for all ~160-310 tensors)
-    pn = g["param_names"].tolist()
-    params = dict(m.named_parameters())
-    mine = np.array([float(params[k].grad.double().norm()) for k in pn])
-    l64 = g["grad_l2:64"]
-    rel = np.abs(mine - l64) / (np.abs(l64) + 1e-12)
-    # the reference's own fp32-vs-fp64 error of a tensor: the largest over its five fp32 summation orders (8 / 4 / 2 / 1
-    # threads, oneDNN off - oracle/make_golden.py); one fp32 run is a single draw of that error
-    variants = [str(v) for v in g["fp32_variants"]]
-    ref_rel = np.max([np.abs(g["grad_l2:" + v] - l64) for v in variants], axis=0) / (np.abs(l64) + 1e-12)
-    # PER TENSOR (tests/_parity.py): a tensor passes iff its error is within max(floor, 3x the reference's own fp32-vs-fp64
-    # error on that tensor); floor = min(5e-2, 3x the reference's worst tensor) - 1.5e-2 on `simple`, 5e-2 on v3
-    check_per_tensor(rel, ref_rel, pn, f"{tag} gradient norms", capsys)
-    # ... and through a fixed-cosine projection, which (unlike a norm) sees permuted / transposed gradients:
-    # a random error of relative size e moves the projection by ~ e * |g| / sqrt(2)
-    proj = np.array([float((params[k].grad.double().reshape(-1) *
-                            torch.cos(0.37 * torch.arange(params[k].numel(), dtype=torch.float64, device=cuda))).sum())
-                     for k in pn])
-    p64 = g["grad_proj:64"]
-    perr = np.abs(proj - p64) / (np.abs(l64) + 1e-12)
-    pref = np.max([np.abs(g["grad_proj:" + v] - p64) for v in variants], axis=0) / (np.abs(l64) + 1e-12)
-    check_rankwise(perr, pref, pn, f"{tag} gradient projections", capsys)     # (why rank-wise: tests/_parity.py)
-    for key in ("backbone.conv1.0", "backbone.layer1.0.conv1", "backbone.layer2.0.conv2", "last_conv.6"):
-        a = params[key + ".weight"].grad.double().cpu().numpy(); b = g[f"wgrad:{key}:64"]
-        rel = np.linalg.norm(a - b) / np.linalg.norm(b)
-        ref_rel = np.linalg.norm(g[f"wgrad:{key}:32"] - b) / np.linalg.norm(b)
-        assert rel <= max(1e-3, 3 * ref_rel), (key, rel, ref_rel)
-    sd = m.state_dict()
-    assert np.abs(sd["backbone.bn1.running_mean"].cpu().numpy() - g["rm:backbone.bn1:64"]).max() < 1e-5
-    assert np.abs(sd["backbone.bn1.running_var"].cpu().numpy() - g["rv:backbone.bn1:64"]).max() < 1e-5
+    forward_backward_vs_golden(tag, cuda, capsys)
 
 
 def test_eic_kernel_bit_exact_vs_golden(cuda):

@@ -13,46 +13,17 @@
 * the data-parallel path at world size 1 bit-identical to the plain step;
 * tools/train.py -> score.pth -> tools/prune.py with --model psp."""
 import copy
-import json
-import os
-import subprocess
 import sys
 
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:         # (also run as a script: the data-parallel child)
-    sys.path.insert(0, ROOT)
-
-from oracle import fill  # noqa: E402
-from oracle.make_scores import synthetic_scores  # noqa: E402
-from _parity import check_per_tensor, check_rankwise  # noqa: E402
+import _model_cases as mc       # (run as a script - the data-parallel child - this file's directory is on sys.path)
 
 pytestmark = pytest.mark.gpu
-G = os.path.join(os.path.dirname(__file__), "golden")
-BB = {"os": 8, "mg_unit": [1, 2, 4], "inplanes": 128, "pretrained": False}
+TAG = "psp_r50_2x65x65"
 SIZES = (1, 2, 3, 6)
-
-
-class _DS:
-    ignore_label = 255
-    num_classes = 19
-    class_weights = None
-
-
-def build(device, criterion=True, deepsup=True):
-    from dcfp_amd import networks
-    from dcfp_amd.loss.criterion import build_criterions
-    crit = build_criterions("ce", _DS(), {"ds_weight": 0.4}) if criterion else None
-    m = networks.psp.Seg_Model(backbone="resnet50", backbone_para=dict(BB), num_classes=19, align_corner=True,
-                               criterion=crit, deepsup=deepsup)
-    m.load_state_dict(fill.closed_form_state(m.state_dict()))
-    if deepsup:
-        m.conv_deepsup[3].p = 0.0
-    return m.to(device).train()
 
 
 def _rel(a, b):
@@ -249,181 +220,23 @@ def test_pyramid_pooling_vs_fp64_composite(cuda, train, widths, HW):
 
 
 def test_forward_backward_vs_reference_golden(cuda, capsys):
-    g = np.load(os.path.join(G, "model_psp_r50_2x65x65.npz"))
-    N, H, W, align = [int(v) for v in g["meta"]]
-    s = int(g["logit_step"])
-    m = build(cuda)
-    x = fill.closed_form_input(N, H, W).to(cuda)
-    lab = fill.closed_form_labels(N, H, W).to(cuda)
-    loss = m(x, lab, deepsup=True)["loss"]
-    loss.backward()
-    torch.cuda.synchronize()
-    ref64 = float(g["loss64"]); ref32 = float(g["loss32"])
-    assert abs(loss.item() - ref64) <= max(1e-5 * abs(ref64), 3 * abs(ref32 - ref64)), (loss.item(), ref32, ref64)
-
-    m2 = build(cuda)
-    with torch.no_grad():
-        outs = m2(x, None, deepsup=True)
-    assert tuple(outs[0].shape) == (N, 19, H, W) and tuple(outs[1].shape) == (N, 19, H, W)
-    for o, key, dkey in ((outs[0], "logits32", "logits_d64m32"), (outs[1], "logits_ds32", "logits_ds_d64m32")):
-        l64 = g[key].astype(np.float64) + g[dkey]
-        err = np.abs(o[:, :, ::s, ::s].double().cpu().numpy() - l64).max()
-        ref_err = np.abs(g[dkey]).max()
-        assert err <= max(1e-3, 3 * ref_err), (key, err, ref_err)
-
-    names = g["bn_names"].tolist()
-    mods = dict(m.named_modules())
-    for what, attr in (("bn_wgrad", "weight"), ("bn_bgrad", "bias")):
-        mine = torch.cat([getattr(mods[n], attr).grad.reshape(-1) for n in names]).double().cpu().numpy()
-        r32 = g[what + "32"].astype(np.float64)
-        r64 = r32 + g[what + "d64m32"]
-        rel = np.linalg.norm(mine - r64) / np.linalg.norm(r64)
-        ref_rel = np.linalg.norm(r32 - r64) / np.linalg.norm(r64)
-        assert rel <= max(1e-3, 3 * ref_rel), (what, rel, ref_rel)
-
-    pn = g["param_names"].tolist()
-    params = dict(m.named_parameters())
-    mine = np.array([float(params[k].grad.double().norm()) for k in pn])
-    l64 = g["grad_l2:64"]
-    rel = np.abs(mine - l64) / (np.abs(l64) + 1e-12)
-    variants = [str(v) for v in g["fp32_variants"]]
-    ref_rel = np.max([np.abs(g["grad_l2:" + v] - l64) for v in variants], axis=0) / (np.abs(l64) + 1e-12)
-    check_per_tensor(rel, ref_rel, pn, "psp_r50_2x65x65 gradient norms", capsys)
-    proj = np.array([float((params[k].grad.double().reshape(-1) *
-                            torch.cos(0.37 * torch.arange(params[k].numel(), dtype=torch.float64, device=cuda))).sum())
-                     for k in pn])
-    p64 = g["grad_proj:64"]
-    perr = np.abs(proj - p64) / (np.abs(l64) + 1e-12)
-    pref = np.max([np.abs(g["grad_proj:" + v] - p64) for v in variants], axis=0) / (np.abs(l64) + 1e-12)
-    check_rankwise(perr, pref, pn, "psp_r50_2x65x65 gradient projections", capsys)
-    for key in ("backbone.conv1.0", "backbone.layer1.0.conv1", "last_conv"):
-        a = params[key + ".weight"].grad.double().cpu().numpy()
-        b32 = g[f"wgrad:{key}:32"].astype(np.float64)
-        b = b32 + g[f"wgrad:{key}:d64m32"]
-        rel = np.linalg.norm(a - b) / np.linalg.norm(b)
-        ref_rel = np.linalg.norm(b32 - b) / np.linalg.norm(b)
-        assert rel <= max(1e-3, 3 * ref_rel), (key, rel, ref_rel)
-    sd = m.state_dict()
-    for bn in ("backbone.bn1", "ppm.stages.0.2", "ppm.bottleneck.1"):
-        for what in ("rm", "rv"):
-            key = "running_mean" if what == "rm" else "running_var"
-            mine, r32, r64 = sd[f"{bn}.{key}"].double().cpu().numpy(), g[f"{what}:{bn}:32"], g[f"{what}:{bn}:64"]
-            assert np.abs(mine - r64).max() <= max(1e-5, 3 * np.abs(r32 - r64).max()), (bn, what)
+    mc.forward_backward_vs_golden(TAG, cuda, capsys)
 
 
 def test_slim_model_matches_reference(cuda, tmp_path):
-    """init_pruned_model from the reference-identical channel_cfg (tests/test_psp_host_cpu.py holds it to the golden
-    bit for bit), the pruned weights loaded, eval mode at 2x3x33x33 (feats 5x5: the 6x6 stage pools with s > H)."""
-    g = np.load(os.path.join(G, "prune_pspr50_gp50.npz"))
-    from dcfp_amd import pruners
-    from dcfp_amd.pruners.dcfp_pruner import DCFPPruner
-    m = build(torch.device("cpu"), criterion=False)
-    torch.save({"eic": synthetic_scores(m)}, str(tmp_path / "score.pth"))
-    pruner = DCFPPruner(global_percent=0.5, layer_keep=0.02, score_file=str(tmp_path / "score.pth"))
-    pruned, cfg = pruner.prune_model(copy.deepcopy(m), except_start_keys=["conv_deepsup"])
-    assert list(cfg.keys()) == g["names"].tolist()
-    slim = build(torch.device("cpu"), criterion=False)
-    pruners.init_pruned_model(slim, cfg)
-    slim.load_state_dict(pruned.state_dict())
-    assert slim.ppm.bottleneck[0].weight.shape[1] == 3327
-    slim = slim.to(cuda).eval()
-    with torch.no_grad():
-        y = slim(fill.closed_form_input(2, 33, 33).to(cuda), None, deepsup=True)
-    err = np.abs(y[0].double().cpu().numpy() - g["slim_logits"]).max()
-    assert err <= 1e-3, err
-
-
-def _ddp_child():
-    import argparse
-    import torch.distributed as dist
-    from dcfp_amd import networks, pruners, optimizer as opt
-    from dcfp_amd.engine import Engine, DataParallel
-    from dcfp_amd.loss.criterion import build_criterions
-
-    class A:
-        no_decay = "bn"; optim = "sgd"; momentum = 0.9; learning_rate = 1e-3; weight_decay = 5e-4
-    dev = torch.device("cuda:0")
-    x = fill.closed_form_input(2, 129, 129).to(dev)
-    lab = fill.closed_form_labels(2, 129, 129).to(dev)
-
-    def run(ddp):
-        torch.manual_seed(12345)
-        m = networks.psp.Seg_Model(backbone="resnet50", backbone_para=dict(BB), num_classes=19, align_corner=True,
-                                   criterion=build_criterions("ce", _DS(), {"ds_weight": 0.4}), deepsup=True)
-        m.load_state_dict(fill.closed_form_state(m.state_dict()))
-        m.conv_deepsup[3].p = 0.0
-        m = m.to(dev).train()
-        optimizer = opt.build_optimizer(A, m)
-        optimizer.zero_grad()
-        tp = pruners.dcfp_pruning(m, 0.999)
-        if ddp:
-            sys.argv = ["x"]
-            eng = Engine(custom_parser=argparse.ArgumentParser())
-            eng.distributed = True
-            model = eng.data_parallel(m)
-            assert isinstance(model, DataParallel)
-            assert isinstance(m.ppm.stages[0][2], torch.nn.SyncBatchNorm)
-        else:
-            model = m
-        loss = model(x, lab, deepsup=True)["loss"]
-        lv = (eng.all_reduce_tensor(loss) if ddp else loss).item()
-        loss.backward()
-        tp.step(m)
-        grads = {k: p.grad.detach().clone() for k, p in m.named_parameters()}
-        eic = torch.cat([tp.get_eic()["eic"][n].reshape(-1) for n in tp._names]).clone()
-        optimizer.step()
-        torch.cuda.synchronize()
-        bufs = {k: v.detach().clone() for k, v in m.state_dict().items()}
-        return lv, grads, eic, bufs
-
-    plain = run(False)
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT="29547", DCFP_FORCE_SYNCBN="1")
-    dist.init_process_group("nccl", rank=0, world_size=1)
-    ddp = run(True)
-    dist.destroy_process_group()
-    out = {"loss": [plain[0], ddp[0]], "grad_diff": [k for k in plain[1] if not torch.equal(plain[1][k], ddp[1][k])],
-           "eic_equal": bool(torch.equal(plain[2], ddp[2])),
-           "state_diff": [k for k in plain[3] if not torch.equal(plain[3][k], ddp[3][k])], "n_params": len(plain[1])}
-    print("DDP_RESULT " + json.dumps(out))
+    """(at 2x3x33x33 feats is 5x5: the 6x6 stage pools with s > H)"""
+    def ragged_width(slim):
+        assert slim.ppm.bottleneck[0].weight.shape[1] == 3327
+    mc.slim_model_logits_check("psp", "pspr50", cuda, tmp_path, ragged_width)
 
 
 def test_data_parallel_bit_identical_to_plain(cuda):
-    env = dict(os.environ, DCFP_FANIN_BN_SUMS="2")
-    env.pop("DCFP_FORCE_SYNCBN", None)
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--ddp-child"], env=env, capture_output=True,
-                       text=True, timeout=600, cwd=ROOT)
-    assert r.returncode == 0, r.stderr[-3000:]
-    rec = json.loads([l for l in r.stdout.splitlines() if l.startswith("DDP_RESULT ")][-1][len("DDP_RESULT "):])
-    assert rec["loss"][0] == rec["loss"][1], rec["loss"]
-    assert rec["grad_diff"] == [], rec["grad_diff"][:8]
-    assert rec["eic_equal"]
-    assert rec["state_diff"] == [], rec["state_diff"][:8]
-    assert rec["n_params"] > 150
+    mc.data_parallel_bit_identical(__file__)
 
 
 def test_train_then_prune_tools(cuda, tmp_path):
-    g = np.load(os.path.join(G, "model_psp_r50_2x65x65.npz"))
-    snap = str(tmp_path / "snap")
-    bb = json.dumps({"pretrained": False})
-    cmd = [sys.executable, os.path.join(ROOT, "tools", "train.py"), "--model", "psp", "--ddp", "False",
-           "--prune-type", "dcfp", "--input-size", "129,129", "--batch-size", "2", "--num-steps", "3",
-           "--snapshot-dir", snap, "--backbone-para", bb, "--learning-rate", "1e-3"]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
-    assert r.returncode == 0, r.stderr[-3000:]
-    losses = [float(l.split("loss=")[1]) for l in r.stdout.splitlines() if "loss=" in l]
-    assert len(losses) == 3 and all(np.isfinite(losses)), r.stdout[-2000:]
-    score = torch.load(os.path.join(snap, "score.pth"), weights_only=False)
-    ign = set(g["ignore_prune_layer"].tolist())
-    assert list(score["eic"].keys()) == [n for n in g["bn_names"].tolist() if n not in ign]
-    ckpt = os.path.join(snap, "CS_scenes_3.pth")
-    out = str(tmp_path / "pruned")
-    cmd = [sys.executable, os.path.join(ROOT, "tools", "prune.py"), "--model", "psp", "--model-path", ckpt,
-           "--score-path", os.path.join(snap, "score.pth"), "--save-path", out, "--backbone-para", bb]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
-    assert r.returncode == 0, r.stderr[-3000:]
-    cfg = torch.load(os.path.join(out, "channel_cfg.pth"), weights_only=False)
-    assert "ppm.bottleneck.0" in cfg and "ppm.stages.3.1" in cfg
+    mc.train_then_prune(TAG, ("ppm.bottleneck.0", "ppm.stages.3.1"), tmp_path)
 
 
 if __name__ == "__main__" and "--ddp-child" in sys.argv:
-    _ddp_child()
+    mc.ddp_child("psp", 29547, lambda m: m.ppm.stages[0][2])
