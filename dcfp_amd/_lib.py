@@ -23,6 +23,13 @@ class ConvDesc(C.Structure):
                  "x_pitch", "dy_pitch")]
 
 
+class ConvF16Desc(C.Structure):
+    """DcfpConvF16Desc: one conv of the fp16 deployment engine (NHWC fp16, packed weights)."""
+    _fields_ = [(n, C.c_int32) for n in
+                ("N", "H", "W", "Cin8", "x_pitch", "Cout", "K", "stride", "pad", "dil", "Hout", "Wout",
+                 "y_pitch", "y_off", "res_pitch", "res_off", "relu")]
+
+
 class EicEntry(C.Structure):
     _fields_ = [("gamma", C.c_void_p), ("grad", C.c_void_p), ("eic", C.c_void_p),
                 ("n", C.c_int32), ("pad_", C.c_int32)]
@@ -53,6 +60,7 @@ E_BADDESC, E_UNSUPPORTED, E_WORKSPACE = -1, -2, -3   # DCFP_E_* of include/dcfp_
 _P, _I, _L, _F, _Z = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
 _D = C.POINTER(ConvDesc)
 _R = C.POINTER(BnRunning)
+_H = C.POINTER(ConvF16Desc)
 
 # name -> (restype, argtypes); mirrors include/dcfp_hip.h one to one
 SIGNATURES = {
@@ -129,6 +137,13 @@ SIGNATURES = {
     "dcfp_confusion_matrix_i64": (_I, [_P, _P, _I, _L, _I, _P, _P]),
     "dcfp_eic_update_f32": (_I, [_P, _I, _F, _F, _P]),
     "dcfp_sgd_momentum_f32": (_I, [_P, _I, _L, _F, _F, _I, _P]),
+    "dcfp_conv2d_fwd_f16_nhwc": (_I, [_H, _P, _P, _P, _P, _P, _P]),
+    "dcfp_conv2d_fwd_f16_nhwc_to_f32_nchw": (_I, [_H, _P, _P, _P, _P, _P]),
+    "dcfp_maxpool3x3s2_nhwc_f16": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "dcfp_avgpool_nhwc_f16_workspace_bytes": (_Z, [_I, _I, _L]),
+    "dcfp_avgpool_nhwc_f16": (_I, [_P, _P, _I, _L, _I, _I, _I, _P, _Z, _P]),
+    "dcfp_broadcast_nhwc_f16": (_I, [_P, _I, _P, _I, _L, _I, _I, _I, _P]),
+    "dcfp_nchw_f32_to_nhwc_f16": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
 }
 
 

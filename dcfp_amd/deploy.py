@@ -1,0 +1,403 @@
+"""Half-precision deployment engine — the fourth stage of the reference's pipeline (totrt.py / scripts/cs/trt.sh:
+freeze the fine-tuned, pruned network into an FP16 engine, save it, time it, evaluate through it).
+
+`freeze(model)` walks an eval-mode DeepLabv3 / `simple` Seg_Model (full width or slimmed by
+pruners.init_pruned_model) once and returns an `Engine`: a flat plan of layer records over numbered activation
+buffers plus the packed tensors.  Planning and packing are plain torch on the CPU; running the plan needs the device
+and goes through the kernels of csrc/conv_f16.hip only:
+
+  * activations NHWC fp16, channels padded to a multiple of 8 (the padding holds exact zeros);
+  * weights [Cout8][kh][kw][Cin8] fp16 with the eval-mode BatchNorm scale folded in (in fp64, one rounding), the
+    BatchNorm shift (and a conv bias) as an fp32 vector added in the conv's epilogue, with the residual add and ReLU;
+  * the ASPP branches write their channel slice of the concat buffer (no cat), the image-pool branch is a global
+    average pool, a 1x1 conv on N pixels and a broadcast; the classifier writes fp32 NCHW logits.
+
+An Engine offers what evaluate.predict_whole / predict_sliding / predict_multiscale / predict_labels ask of a net:
+engine(image) -> [logits], engine.lowres_logits(image) -> [lowres], engine.align_corner.
+"""
+import ctypes as C
+
+import torch
+import torch.nn as nn
+
+from . import _lib, ops
+from ._lib import check
+
+FORMAT = 1
+_POOL_OPS = ("maxpool", "avgpool", "broadcast")
+
+
+def _r8(c):
+    return (int(c) + 7) // 8 * 8
+
+
+def fold_bn(conv, bn):
+    """(scale, shift) in fp64 of eval-mode `bn` after `conv` (bn None: the conv's own bias, scale 1)."""
+    cout = conv.weight.shape[0]
+    bias = conv.bias.detach().double().cpu() if conv.bias is not None else torch.zeros(cout, dtype=torch.float64)
+    if bn is None:
+        return torch.ones(cout, dtype=torch.float64), bias
+    scale = bn.weight.detach().double().cpu() / torch.sqrt(bn.running_var.detach().double().cpu() + bn.eps)
+    shift = bn.bias.detach().double().cpu() + (bias - bn.running_mean.detach().double().cpu()) * scale
+    return scale, shift
+
+
+def pack_weight(w, scale, segments, cin8):
+    """[Cout, Cin, k, k] * scale[co] (fp64) -> fp16 [Cout8, k, k, cin8]; input channel block (offset, count) of
+    `segments` (in the conv's channel order) lands at columns offset .. offset + count - 1, everything else is zero."""
+    cout, cin, kh, kw = w.shape
+    ws = (w.detach().double().cpu() * scale.view(-1, 1, 1, 1)).to(torch.float16)
+    out = torch.zeros((_r8(cout), kh, kw, cin8), dtype=torch.float16)
+    s = 0
+    for off, cnt in segments:
+        out[:cout, :, :, off:off + cnt] = ws[:, s:s + cnt].permute(0, 2, 3, 1)
+        s += cnt
+    assert s == cin, (s, cin)
+    return out.contiguous()
+
+
+def unpack_weight(packed, cout, segments):
+    """The inverse of pack_weight: fp16 [cout, Cin, k, k]."""
+    parts = [packed[:cout, :, :, off:off + cnt] for off, cnt in segments]
+    return torch.cat(parts, dim=3).permute(0, 3, 1, 2).contiguous()
+
+
+class _Planner:
+    def __init__(self):
+        self.records, self.tensors, self.pitch, self.segments = [], [], [], []
+
+    def buffer(self, segments, pitch=None):
+        self.pitch.append(pitch if pitch is not None else _r8(sum(c for _, c in segments)))
+        self.segments.append(list(segments))
+        return len(self.pitch) - 1
+
+    def tensor(self, t):
+        self.tensors.append(t)
+        return len(self.tensors) - 1
+
+    def conv(self, name, conv, bn, src, relu, dst=None, y_off=0, res=-1, f32=False):
+        if not isinstance(conv, nn.Conv2d) or (bn is not None and not isinstance(bn, nn.BatchNorm2d)):
+            raise NotImplementedError(f"freeze: {name}: {type(conv).__name__} / {type(bn).__name__} is not conv + BatchNorm2d")
+        k, s, p, d = conv.kernel_size, conv.stride, conv.padding, conv.dilation
+        if (k[0] != k[1] or k[0] not in (1, 3) or s[0] != s[1] or s[0] not in (1, 2) or p[0] != p[1] or d[0] != d[1]
+                or conv.groups != 1 or conv.padding_mode != "zeros" or isinstance(p, str)):
+            raise NotImplementedError(f"freeze: {name}: unsupported conv geometry {conv}")
+        cout, cin = conv.weight.shape[:2]
+        if cin != sum(c for _, c in self.segments[src]):
+            raise ValueError(f"freeze: {name} reads {cin} channels, its input holds {self.segments[src]}")
+        scale, shift = fold_bn(conv, bn)
+        sh = torch.zeros(_r8(cout), dtype=torch.float32)
+        sh[:cout] = shift.float()
+        if dst is None:
+            dst = -1 if f32 else self.buffer([(0, cout)])
+        rec = {"op": "conv", "name": name, "src": src, "dst": dst, "res": res, "cin": int(cin), "cout": int(cout),
+               "cin8": self.pitch[src], "k": k[0], "stride": s[0], "pad": p[0], "dil": d[0], "relu": bool(relu),
+               "y_off": int(y_off), "f32": bool(f32), "segments": [list(sg) for sg in self.segments[src]],
+               "w": self.tensor(pack_weight(conv.weight, scale, self.segments[src], self.pitch[src])),
+               "shift": self.tensor(sh)}
+        if res >= 0 and self.pitch[res] != self.pitch[dst]:
+            raise ValueError(f"freeze: {name}: residual of {self.pitch[res]} channels on {self.pitch[dst]}")
+        self.records.append(rec)
+        return dst
+
+    def node(self, op, name, src, dst, y_off=0):
+        self.records.append({"op": op, "name": name, "src": src, "dst": dst, "y_off": int(y_off)})
+        return dst
+
+
+def _plan_sequential(pl, prefix, mods, x, tail_bn=None):
+    """conv (-> BatchNorm2d) (-> ReLU) groups of an nn.Sequential's children; tail_bn: the BatchNorm (+ ReLU) that the
+    model applies to the last conv from outside the container (the deep stem's bn1 / relu1)."""
+    i = 0
+    while i < len(mods):
+        conv = mods[i]
+        name = f"{prefix}.{i}"
+        if not isinstance(conv, nn.Conv2d):
+            raise NotImplementedError(f"freeze: {name}: {type(conv).__name__} in a conv stack")
+        i += 1
+        bn, relu = None, False
+        if i < len(mods) and isinstance(mods[i], nn.BatchNorm2d):
+            bn = mods[i]; i += 1
+        if i < len(mods) and isinstance(mods[i], nn.ReLU):
+            relu = True; i += 1
+        last = i >= len(mods)
+        if last and tail_bn is not None:
+            bn, relu = tail_bn, True
+        x = pl.conv(name, conv, bn, x, relu, f32=(last and bn is None))
+    return x
+
+
+def _plan_backbone(pl, bb, x):
+    from .networks.backbone.resnet import Bottleneck, ResNet
+    if not isinstance(bb, ResNet):
+        raise NotImplementedError(f"freeze: backbone {type(bb).__module__}.{type(bb).__name__} is not the ResNet")
+    x = _plan_sequential(pl, "backbone.conv1", list(bb.conv1.children()), x, tail_bn=bb.bn1)
+    mp = bb.maxpool
+    if not isinstance(mp, nn.MaxPool2d) or (mp.kernel_size, mp.stride, mp.padding) != (3, 2, 1):
+        raise NotImplementedError(f"freeze: backbone.maxpool {mp}")
+    x = pl.node("maxpool", "backbone.maxpool", x, pl.buffer(pl.segments[x]))
+    for li in range(1, 5):
+        for bi, blk in enumerate(getattr(bb, f"layer{li}")):
+            p = f"backbone.layer{li}.{bi}"
+            if not isinstance(blk, Bottleneck):
+                raise NotImplementedError(f"freeze: {p}: {type(blk).__name__}")
+            out = pl.conv(p + ".conv1", blk.conv1, blk.bn1, x, True)
+            out = pl.conv(p + ".conv2", blk.conv2, blk.bn2, out, True)
+            res = x
+            if blk.downsample is not None:
+                ds = list(blk.downsample.children())
+                if len(ds) != 2:
+                    raise NotImplementedError(f"freeze: {p}.downsample {blk.downsample}")
+                res = pl.conv(p + ".downsample.0", ds[0], ds[1], x, False)
+            x = pl.conv(p + ".conv3", blk.conv3, blk.bn3, out, True, res=res)
+    return x
+
+
+def _plan_aspp(pl, aspp, x):
+    from .networks.tools.aspp import ASPP
+    if not isinstance(aspp, ASPP) or aspp.outplanes is None:
+        raise NotImplementedError(f"freeze: aspp {type(aspp).__name__} (outplanes {getattr(aspp, 'outplanes', None)})")
+    pool = list(aspp.global_avg_pool.children())
+    if len(pool) != 4 or not isinstance(pool[0], nn.AdaptiveAvgPool2d) or pool[0].output_size not in (1, (1, 1)):
+        raise NotImplementedError(f"freeze: aspp.global_avg_pool {aspp.global_avg_pool}")
+    branches = [aspp.aspp1, aspp.aspp2, aspp.aspp3, aspp.aspp4]
+    widths = [m.atrous_conv.weight.shape[0] for m in branches] + [pool[1].weight.shape[0]]
+    offs, o = [], 0
+    for c in widths:      # every slice starts at a multiple of 8; the gaps hold the branches' zero padding
+        offs.append(o); o += _r8(c)
+    cat = pl.buffer(list(zip(offs, widths)), pitch=o)
+    for i, m in enumerate(branches):
+        pl.conv(f"aspp.aspp{i + 1}.atrous_conv", m.atrous_conv, m.bn, x, True, dst=cat, y_off=offs[i])
+    g = pl.node("avgpool", "aspp.global_avg_pool.0", x, pl.buffer(pl.segments[x]))
+    g = pl.conv("aspp.global_avg_pool.1", pool[1], pool[2], g, isinstance(pool[3], nn.ReLU))
+    pl.node("broadcast", "aspp.global_avg_pool.up", g, cat, y_off=offs[4])
+    return pl.conv("aspp.conv1", aspp.conv1, aspp.bn1, cat, True)
+
+
+def freeze(model, dtype=torch.float16):
+    """Freeze an eval-mode networks.deeplabv3 / networks.simple Seg_Model into an Engine (on the CPU; .to(device) or
+    load_engine(state, device) puts it on the GPU).  conv_deepsup is dropped."""
+    from .networks import deeplabv3, simple
+    if dtype != torch.float16:
+        raise NotImplementedError(f"freeze: dtype {dtype}: the engine is fp16 only")
+    if type(model) not in (deeplabv3.Seg_Model, simple.Seg_Model):
+        raise NotImplementedError(f"freeze: {type(model).__module__}.{type(model).__name__} is not supported "
+                                  "(networks.deeplabv3 and networks.simple are)")
+    if model.training:
+        raise RuntimeError("freeze: the model is in training mode; call model.eval() first (BatchNorm is folded from "
+                           "its running statistics)")
+    pl = _Planner()
+    with torch.no_grad():
+        x = pl.buffer([(0, 3)])                     # buffer 0: the converted input image
+        x = _plan_backbone(pl, model.backbone, x)
+        for name, _ in model.named_children():
+            if name not in ("backbone", "aspp", "last_conv", "conv_deepsup", "criterion"):
+                raise NotImplementedError(f"freeze: module {name} of {type(model).__module__}")
+        if type(model) is deeplabv3.Seg_Model:
+            x = _plan_aspp(pl, model.aspp, x)
+        out = _plan_sequential(pl, "last_conv", list(model.last_conv.children()), x)
+    if out != -1:
+        raise NotImplementedError("freeze: last_conv does not end in a classifier conv with a bias")
+    meta = {"align_corner": bool(model.align_corner), "num_classes": int(pl.records[-1]["cout"]), "in_channels": 3,
+            "dtype": "float16", "model": type(model).__module__.rsplit(".", 1)[-1]}
+    return Engine({"format": FORMAT, "meta": meta, "plan": pl.records, "buffers": list(pl.pitch), "tensors": pl.tensors})
+
+
+def load_engine(path_or_dict, device=None):
+    """The engine saved by torch.save(engine.state_dict(), path) (or that dict itself), on `device`."""
+    state = path_or_dict
+    if not isinstance(state, dict):
+        state = torch.load(path_or_dict, map_location="cpu", weights_only=True)
+    eng = Engine(state)
+    return eng.to(device) if device is not None else eng
+
+
+class Engine:
+    """A frozen fp16 inference program.  Holds the plan, the packed tensors and, per device, a pool of activation
+    slots: buffers whose lifetimes do not overlap share a slot, a slot grows to the largest tenant seen, and the
+    per-input-shape launch list is built once and reused."""
+
+    def __init__(self, state):
+        if state.get("format") != FORMAT:
+            raise ValueError(f"engine format {state.get('format')}: this build reads format {FORMAT}")
+        self.meta = dict(state["meta"])
+        self.plan = [dict(r) for r in state["plan"]]
+        self.buffers = list(state["buffers"])
+        self.tensors = list(state["tensors"])
+        self.align_corner = self.meta["align_corner"]
+        self.num_classes = self.meta["num_classes"]
+        self.device = torch.device("cpu")
+        self.training = False
+        first, last = {0: -1}, {}
+        for i, r in enumerate(self.plan):
+            for b in (r["src"], r["dst"], r.get("res", -1)):
+                if b >= 0:
+                    first.setdefault(b, i)
+                    last[b] = i
+        self._slot_of, free, nslots = {}, [], 0     # liveness: buffer -> slot, the same for every input shape
+        for i in range(-1, len(self.plan)):
+            for b in sorted(k for k, v in first.items() if v == i):
+                if free:
+                    self._slot_of[b] = free.pop()
+                else:
+                    self._slot_of[b] = nslots; nslots += 1
+            free += [self._slot_of[b] for b in sorted(k for k, v in last.items() if v == i)]
+        self._slots = [None] * nslots
+        self._generation = 0
+        self._programs = {}
+        self._avg_ws = None
+
+    # ---- persistence / placement
+    def state_dict(self):
+        """Tensors and plain Python containers only: the plan plus the packed tensors (on the CPU)."""
+        return {"format": FORMAT, "meta": dict(self.meta), "plan": [dict(r) for r in self.plan],
+                "buffers": list(self.buffers), "tensors": [t.detach().cpu() for t in self.tensors]}
+
+    def to(self, device):
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        self.tensors = [t.to(device) for t in self.tensors]
+        self.device = device
+        self._slots = [None] * len(self._slots)
+        self._programs, self._avg_ws = {}, None
+        self._generation += 1
+        return self
+
+    def eval(self):
+        return self
+
+    # ---- running the plan
+    def buffer_shapes(self, H, W):
+        """{buffer id: (h, w)} of every activation buffer for an H x W input (-1: the fp32 low-resolution logits)."""
+        hw = {0: (H, W)}
+        for r in self.plan:
+            h, w = hw[r["src"]]
+            if r["op"] == "conv":
+                ext = r["dil"] * (r["k"] - 1) + 1
+                o = ((h + 2 * r["pad"] - ext) // r["stride"] + 1, (w + 2 * r["pad"] - ext) // r["stride"] + 1)
+            elif r["op"] == "maxpool":
+                o = ((h - 1) // 2 + 1, (w - 1) // 2 + 1)
+            elif r["op"] == "avgpool":
+                o = (1, 1)
+            else:                                    # broadcast: the destination's own size
+                o = hw[r["dst"]]
+            if min(o) < 1:
+                raise RuntimeError(f"deploy.Engine: a {H}x{W} input is too small for {r['name']}")
+            if hw.setdefault(r["dst"], o) != o:
+                raise RuntimeError(f"deploy.Engine: {r['name']} writes {o} into a {hw[r['dst']]} buffer")
+            r_res = r.get("res", -1)
+            if r_res >= 0 and hw[r_res] != o:
+                raise RuntimeError(f"deploy.Engine: {r['name']}: residual {hw[r_res]} on {o}")
+        return hw
+
+    def _program(self, N, H, W):
+        key = (N, H, W)
+        prog = self._programs.get(key)
+        if prog is not None and prog[0] == self._generation:
+            return prog
+        L = _lib.lib()
+        hw = self.buffer_shapes(H, W)
+        need = [0] * len(self._slots)
+        for b, (h, w) in hw.items():
+            if b >= 0:
+                s = self._slot_of[b]
+                need[s] = max(need[s], N * h * w * self.buffers[b] * 2)
+        grown = False
+        for s, n in enumerate(need):
+            if self._slots[s] is None or self._slots[s].numel() < n:
+                self._slots[s] = torch.empty(n, dtype=torch.uint8, device=self.device)
+                grown = True
+        # the average pool's partial sums: sized before any launch list is built and grown like a slot, so that no
+        # cached list keeps a pointer into a buffer that has been given back
+        ws_need = max([int(L.dcfp_avgpool_nhwc_f16_workspace_bytes(N, self.buffers[r["src"]],
+                                                                    hw[r["src"]][0] * hw[r["src"]][1]))
+                       for r in self.plan if r["op"] == "avgpool"] + [0])
+        if ws_need and (self._avg_ws is None or self._avg_ws.numel() < ws_need):
+            self._avg_ws = torch.empty(ws_need, dtype=torch.uint8, device=self.device)
+            grown = True
+        if grown:
+            self._generation += 1
+            self._programs = {}
+
+        def ptr(b):
+            return C.c_void_p(self._slots[self._slot_of[b]].data_ptr())
+        calls, descs, out_shape, out_call = [], [], None, None
+        for r in self.plan:
+            h, w = hw[r["src"]]
+            name = r["name"]
+            if r["op"] == "conv":
+                ho, wo = hw[r["dst"]]
+                f32 = r["f32"]
+                d = _lib.ConvF16Desc(N, h, w, r["cin8"], self.buffers[r["src"]], r["cout"] if f32 else _r8(r["cout"]),
+                                     r["k"], r["stride"], r["pad"], r["dil"], ho, wo,
+                                     0 if f32 else self.buffers[r["dst"]], r["y_off"],
+                                     self.buffers[r["res"]] if r["res"] >= 0 else 0, 0, int(r["relu"]))
+                descs.append(d)
+                wt, sh = C.c_void_p(self.tensors[r["w"]].data_ptr()), C.c_void_p(self.tensors[r["shift"]].data_ptr())
+                if f32:
+                    out_shape = (N, r["cout"], ho, wo)
+                    out_call = (name, L.dcfp_conv2d_fwd_f16_nhwc_to_f32_nchw, (C.byref(d), ptr(r["src"]), wt, sh))
+                else:
+                    calls.append((name, L.dcfp_conv2d_fwd_f16_nhwc,
+                                  (C.byref(d), ptr(r["src"]), wt, sh, ptr(r["res"]) if r["res"] >= 0 else None,
+                                   ptr(r["dst"]))))
+            elif r["op"] == "maxpool":
+                ho, wo = hw[r["dst"]]
+                calls.append((name, L.dcfp_maxpool3x3s2_nhwc_f16,
+                              (ptr(r["src"]), ptr(r["dst"]), N, h, w, self.buffers[r["src"]], self.buffers[r["src"]],
+                               ho, wo, self.buffers[r["dst"]])))
+            elif r["op"] == "avgpool":
+                c8 = self.buffers[r["src"]]
+                nbytes = int(L.dcfp_avgpool_nhwc_f16_workspace_bytes(N, c8, h * w))
+                calls.append((name, L.dcfp_avgpool_nhwc_f16,
+                              (ptr(r["src"]), ptr(r["dst"]), N, h * w, c8, c8, self.buffers[r["dst"]],
+                               C.c_void_p(self._avg_ws.data_ptr()), nbytes)))
+            elif r["op"] == "broadcast":
+                ho, wo = hw[r["dst"]]
+                c8 = self.buffers[r["src"]]
+                calls.append((name, L.dcfp_broadcast_nhwc_f16,
+                              (ptr(r["src"]), c8, ptr(r["dst"]), N, ho * wo, c8, self.buffers[r["dst"]], r["y_off"])))
+            else:
+                raise RuntimeError(f"deploy.Engine: unknown op {r['op']} ({name})")
+        if out_call is None:
+            raise RuntimeError("deploy.Engine: the plan has no classifier")
+        prog = (self._generation, calls, out_call, out_shape, descs, ptr(0))
+        self._programs[key] = prog
+        return prog
+
+    @torch.no_grad()
+    def lowres_logits(self, image, deepsup=False):
+        """[fp32 N x classes x h x w logits at 1/os resolution] (the deep-supervision head is not part of an engine)."""
+        if self.device.type != "cuda" or not isinstance(image, torch.Tensor) or not image.is_cuda:
+            raise RuntimeError("deploy.Engine runs on the MI355X HIP kernels only: engine.to('cuda') and a CUDA image "
+                               "(no CPU fallback exists)")
+        if image.device != self.device:
+            raise RuntimeError(f"deploy.Engine: the engine is on {self.device}, the image on {image.device}")
+        if image.dtype != torch.float32 or image.dim() != 4 or image.shape[1] != self.meta["in_channels"]:
+            raise RuntimeError(f"deploy.Engine: image must be float32 [N,{self.meta['in_channels']},H,W]")
+        image = image.contiguous()
+        N, Cc, H, W = image.shape
+        with torch.cuda.device(self.device):         # (the launches go to the engine's device and its current stream)
+            return self._run(image, N, Cc, H, W)
+
+    def _run(self, image, N, Cc, H, W):
+        _, calls, out_call, out_shape, _, in_ptr = self._program(N, H, W)
+        L, stream = _lib.lib(), ops._stream()
+        check(L.dcfp_nchw_f32_to_nhwc_f16(C.c_void_p(image.data_ptr()), in_ptr, N, Cc, H, W, self.buffers[0], stream),
+              "deploy: input conversion")
+        for name, fn, args in calls:
+            check(fn(*args, stream), "deploy: " + name)
+        out = torch.empty(out_shape, dtype=torch.float32, device=image.device)
+        name, fn, args = out_call
+        check(fn(*args, C.c_void_p(out.data_ptr()), stream), "deploy: " + name)
+        return [out]
+
+    @torch.no_grad()
+    def __call__(self, image, labels=None, deepsup=False):
+        """[fp32 N x classes x H x W logits]: the low-resolution logits through the bilinear upsample kernel."""
+        lowres = self.lowres_logits(image)
+        return [ops.upsample_bilinear(z, image.shape[2:], self.align_corner) for z in lowres]
+
+    def conv_records(self):
+        return [r for r in self.plan if r["op"] == "conv"]

@@ -522,6 +522,47 @@ typedef struct DcfpSgdEntry {
 int dcfp_sgd_momentum_f32(const DcfpSgdEntry* table, int n_tensors, int64_t total_chunks,
                           float lr, float momentum, int first_step, dcfp_stream_t stream);
 
+/* ------------------------------------------------- fp16 deployment engine
+ * The frozen half-precision inference path (dcfp_amd/deploy.py; the reference's totrt.py stage).  Activations are
+ * NHWC fp16 with a channel pitch that is a multiple of 8; weights are packed once as [Cout8][KH][KW][Cin8] fp16 with
+ * the eval-mode BatchNorm scale folded in (zero rows / columns in the padding); accumulation is fp32 on the fp16
+ * matrix cores (v_mfma_f32_32x32x16_f16), one rounding to fp16 in the epilogue.
+ *   y[n, oy, ox, y_off + co] = relu?(sum_k x * w + shift[co] (+ residual[n, oy, ox, res_off + co]))
+ * Cross-correlation, zero padding, square 1x1 or 3x3 filter, stride 1 or 2, any dilation.  Every pointer is 16-byte
+ * aligned; x must hold Cin8 valid channels per pixel (x_pitch >= Cin8 apart); N*H*W and N*Hout*Wout < 2^31. */
+typedef struct DcfpConvF16Desc {
+    int32_t N, H, W;            /* input  [N,H,W,x_pitch], channels 0 .. Cin8-1 read                    */
+    int32_t Cin8, x_pitch;      /* multiples of 8                                                      */
+    int32_t Cout;               /* output channels written: a multiple of 8 for the fp16 output (the
+                                   padded count), the true class count for the fp32 NCHW output; the
+                                   packed weight and shift always hold Cout rounded up to 8 rows       */
+    int32_t K, stride, pad, dil;/* K = 1 or 3; stride 1 or 2; same in h and w                           */
+    int32_t Hout, Wout;         /* (H + 2*pad - dil*(K-1) - 1)/stride + 1                               */
+    int32_t y_pitch, y_off;     /* fp16 output: channel pitch and first channel (multiples of 8)        */
+    int32_t res_pitch, res_off; /* residual (fp16 NHWC at the output's resolution), when given          */
+    int32_t relu;
+} DcfpConvF16Desc;
+int dcfp_conv2d_fwd_f16_nhwc(const DcfpConvF16Desc* d, const void* x, const void* w_packed, const float* shift,
+                             const void* residual /* nullable */, void* y, dcfp_stream_t stream);
+/* The classifier's epilogue: y fp32 NCHW dense [N, Cout, Hout, Wout] = acc + bias (no ReLU, no residual; y_*, res_*
+ * and relu of the descriptor are ignored), what dcfp_upsample_argmax_f32 / dcfp_upsample_bilinear_fwd_f32 read. */
+int dcfp_conv2d_fwd_f16_nhwc_to_f32_nchw(const DcfpConvF16Desc* d, const void* x, const void* w_packed,
+                                         const float* bias, float* y, dcfp_stream_t stream);
+/* nn.MaxPool2d(3, 2, 1) on NHWC fp16 (resnet.py:98): C8 channels of x [N,H,W,x_pitch] -> y [N,Ho,Wo,y_pitch]. */
+int dcfp_maxpool3x3s2_nhwc_f16(const void* x, void* y, int N, int H, int W, int C8, int x_pitch, int Ho, int Wo,
+                               int y_pitch, dcfp_stream_t stream);
+/* nn.AdaptiveAvgPool2d(1) on NHWC fp16 (aspp.py:60): y[n, c] = fp16(mean over the HW pixels of x[n, :, c]), summed
+ * in fp32 in a fixed order (deterministic).  workspace: dcfp_avgpool_nhwc_f16_workspace_bytes(N, C8, HW). */
+size_t dcfp_avgpool_nhwc_f16_workspace_bytes(int N, int C8, int64_t HW);
+int dcfp_avgpool_nhwc_f16(const void* x, void* y, int N, int64_t HW, int C8, int x_pitch, int y_pitch,
+                          void* workspace, size_t workspace_bytes, dcfp_stream_t stream);
+/* Bilinear resize from a 1x1 map = broadcast (aspp.py:76): y[n, p, y_off + c] = v[n, c] for the HW pixels p and
+ * c < C8; v rows v_pitch apart.  Channels of y outside the slice are not touched. */
+int dcfp_broadcast_nhwc_f16(const void* v, int v_pitch, void* y, int N, int64_t HW, int C8, int y_pitch, int y_off,
+                            dcfp_stream_t stream);
+/* The engine's input converter: x fp32 NCHW dense [N,C,H,W] -> y fp16 NHWC [N,H,W,C8], channels C .. C8-1 zero. */
+int dcfp_nchw_f32_to_nhwc_f16(const float* x, void* y, int N, int C, int H, int W, int C8, dcfp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,12 +18,21 @@ def main():
     ap.add_argument("--size", default="1024,2048")
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--fp16", action="store_true", help="time predict_labels through the frozen fp16 engine (dcfp_amd/deploy.py)")
+    ap.add_argument("--channel-cfg", default=None, help="slim the model with this channel_cfg.pth (pruners.init_pruned_model)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     h, w = [int(v) for v in a.size.split(",")]
     bb = {"os": 8, "mg_unit": [1, 2, 4], "inplanes": 128, "pretrained": False}
     m = networks.deeplabv3.Seg_Model(backbone=a.backbone, backbone_para=bb, num_classes=19, align_corner=True,
-                                     deepsup=False).to(dev).eval()
+                                     deepsup=False)
+    if a.channel_cfg:
+        from dcfp_amd.pruners import init_pruned_model
+        init_pruned_model(m, torch.load(a.channel_cfg, weights_only=False))
+    m = m.to(dev).eval()
+    if a.fp16:
+        from dcfp_amd import deploy
+        m = deploy.freeze(m.cpu()).to(dev)
     x = torch.randn(a.batch, 3, h, w, device=dev)
     for _ in range(5):
         ev.predict_labels(m, x)
@@ -34,7 +43,7 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     print(f"inference: {a.batch * a.iters / dt:.2f} images/s ({dt / a.iters * 1e3:.1f} ms per batch of {a.batch}) "
-          f"DeepLabv3-{a.backbone} {h}x{w} fp32" + (" (conv math: bf16x3 split)" if os.environ.get("DCFP_CONV_MATH") == "bf16x3" else ""))
+          f"DeepLabv3-{a.backbone}{' slim' if a.channel_cfg else ''} {h}x{w} " + ("fp16 engine" if a.fp16 else "fp32") + (" (conv math: bf16x3 split)" if os.environ.get("DCFP_CONV_MATH") == "bf16x3" else ""))
 
 
 if __name__ == "__main__":
