@@ -135,6 +135,9 @@ SIGNATURES = {
     "dcfp_upsample_wce_bwd_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "dcfp_upsample_argmax_f32": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "dcfp_confusion_matrix_i64": (_I, [_P, _P, _I, _L, _I, _P, _P]),
+    "dcfp_label_boundary_workspace_bytes": (_Z, [_I, _I, _I]),
+    "dcfp_label_boundary_i32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _Z, _P]),
+    "dcfp_label_boundary_i64": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _Z, _P]),
     "dcfp_eic_update_f32": (_I, [_P, _I, _F, _F, _P]),
     "dcfp_sgd_momentum_f32": (_I, [_P, _I, _L, _F, _F, _I, _P]),
     "dcfp_conv2d_fwd_f16_nhwc": (_I, [_H, _P, _P, _P, _P, _P, _P]),

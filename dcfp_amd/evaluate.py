@@ -9,6 +9,7 @@ import torch.nn.functional as F
 
 from . import ops
 from .networks import _exec
+from .utils.edge_utils import mask_to_boundary
 
 
 @torch.no_grad()
@@ -103,5 +104,35 @@ def mean_iou(confusion_matrix):
     """evaluate.py:374-380: IoU per class = tp / (pos + res - tp); mean over classes."""
     cm = confusion_matrix.double()
     pos, res, tp = cm.sum(1), cm.sum(0), cm.diag()
+    iou = tp / torch.clamp(pos + res - tp, min=1.0)
+    return iou.mean().item(), iou
+
+
+def boundary_confusion_matrix(gt_label, pred_label, class_num, dilation_ratio=0.02, ignore_index=255, out=None):
+    """evaluate.py:352-362 on the device -> int64 [C, C+1].  Both maps are reduced to their class boundaries
+    (utils.edge_utils.mask_to_boundary); what is left of the ground truth is counted, everything else of it is
+    ignore.  A counted pixel that the prediction does not mark as boundary is a miss of its ground-truth class and
+    lands in column C (the reference lets 255 alias into gt*C + pred there)."""
+    gt_b = mask_to_boundary(gt_label.to(torch.int64), class_num, dilation_ratio, ignore_index)
+    pred_b = mask_to_boundary(pred_label.to(torch.int32), class_num, dilation_ratio, class_num)
+    if out is not None and (out.dtype != torch.int64 or tuple(out.shape) != (class_num, class_num + 1)
+                            or not out.is_contiguous()):
+        raise RuntimeError("boundary_confusion_matrix: out must be a contiguous int64 [C, C+1] tensor")
+    # the [C, C+1] matrix is the first C rows of the (C+1)-class one: its last row (gt == C) stays empty because
+    # the ground truth holds classes below C or ignore only
+    full = torch.zeros((class_num + 1, class_num + 1), dtype=torch.int64, device=gt_b.device)
+    ops.confusion_matrix(pred_b, gt_b, class_num + 1, ignore_index, full)
+    if out is None:
+        return full[:class_num].clone()
+    out += full[:class_num]
+    return out
+
+
+def boundary_iou(confusion_matrix):
+    """IoU per class over boundary pixels from the [C, C+1] matrix: tp / max(1, pos + res - tp) with pos the row
+    sums (misses included) and res the column sums over the class columns."""
+    cm = confusion_matrix.double()
+    Cn = cm.shape[0]
+    pos, res, tp = cm.sum(1), cm[:, :Cn].sum(0), cm[:, :Cn].diag()
     iou = tp / torch.clamp(pos + res - tp, min=1.0)
     return iou.mean().item(), iou

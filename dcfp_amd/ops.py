@@ -1928,3 +1928,23 @@ def confusion_matrix(pred, gt, num_classes, ignore_index=255, out=None):
     check(_lib.lib().dcfp_confusion_matrix_i64(_p(pred), _p(gt), int(ignore_index), pred.numel(),
                                                int(num_classes), _p(out), _stream()), "confusion_matrix")
     return out
+
+
+def label_boundary(labels, num_classes, d, background=255):
+    """The label map with everything but the class boundaries set to `background`: a pixel with
+    0 <= label < num_classes keeps its label unless the whole (2d+1)x(2d+1) window centred on it lies inside the
+    image and carries that label.  int32 / int64 [H,W] or [N,H,W] -> a new tensor of the same shape and dtype."""
+    if not isinstance(labels, torch.Tensor) or not labels.is_cuda:
+        raise RuntimeError("dcfp_amd: labels must be a CUDA/HIP tensor (no CPU fallback exists)")
+    if labels.dtype not in (torch.int32, torch.int64) or labels.dim() not in (2, 3):
+        raise RuntimeError("label_boundary: int32 / int64 [H,W] or [N,H,W] labels expected")
+    src = labels.contiguous()
+    N = src.shape[0] if src.dim() == 3 else 1
+    H, W = src.shape[-2:]
+    out = torch.empty_like(src)
+    L = _lib.lib()
+    ws = _workspace("label_boundary", L.dcfp_label_boundary_workspace_bytes(N, H, W), src.device)
+    fn = L.dcfp_label_boundary_i32 if src.dtype == torch.int32 else L.dcfp_label_boundary_i64
+    check(fn(_p(src), _p(out), N, H, W, int(num_classes), int(d), int(background), _p(ws), ws.numel(), _stream()),
+          "label_boundary")
+    return out

@@ -490,6 +490,17 @@ int dcfp_confusion_matrix_i64(const int32_t* pred, const int64_t* gt, int ignore
                               int64_t n_pixels, int C, int64_t* conf /* [C*C], accumulated */,
                               dcfp_stream_t stream);
 
+/* Boundary IoU (evaluate.py:352-357, utils/edge_utils.py:98-127): the label map with everything but the class
+ * boundaries set to `background`.  A pixel is valid if 0 <= label < num_classes; a valid pixel is interior if
+ * the whole (2d+1)x(2d+1) window centred on it lies inside the image and carries its label;
+ * out = label where valid and not interior, else background.  [N,H,W] dense, images independent, out != labels.
+ * Work per pixel does not depend on d or num_classes (boundary.hip); num_classes <= 255 (one-byte keys). */
+size_t dcfp_label_boundary_workspace_bytes(int N, int H, int W);
+int dcfp_label_boundary_i32(const int32_t* labels, int32_t* out, int N, int H, int W, int num_classes, int d,
+                            int background, void* workspace, size_t workspace_bytes, dcfp_stream_t stream);
+int dcfp_label_boundary_i64(const int64_t* labels, int64_t* out, int N, int H, int W, int num_classes, int d,
+                            int background, void* workspace, size_t workspace_bytes, dcfp_stream_t stream);
+
 /* ------------------------------------------------------------- EIC score
  * dcfp_pruning.step (pruners/dcfp_pruner.py:15-20), all scored BN layers in one
  * launch.  table: device array of n_layers records; eic is updated in place:

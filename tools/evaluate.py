@@ -1,0 +1,166 @@
+#!/usr/bin/env python
+"""Evaluation driver — the command line and protocol of the reference's evaluate.py main() (evaluate.py:249-393) over
+SYNTHETIC data: build the (optionally slimmed, optionally frozen-to-fp16) model, predict batch by batch, accumulate the
+confusion matrix on the device, print {'meanIU', 'IU_array'} and append IoU / precision / recall / FPS to result.txt in
+the snapshot directory.  `--iou-type boundary` scores class boundaries only.  Datasets, PNG output,
+--longsize/--shortsize and multi-rank evaluation are not part of it."""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+
+from dcfp_amd import deploy, evaluate as ev, networks, ops  # noqa: E402
+from dcfp_amd.pruners import init_pruned_model  # noqa: E402
+from dcfp_amd.utils.pyt_utils import load_model  # noqa: E402
+
+FPS_WARMUP = 5        # evaluate.py:314
+
+
+def str2bool(v):
+    if v.lower() in ("yes", "true", "t", "y", "1"):
+        return True
+    if v.lower() in ("no", "false", "f", "n", "0"):
+        return False
+    raise argparse.ArgumentTypeError("Boolean value expected.")
+
+
+def get_parser():
+    p = argparse.ArgumentParser(description="DCFP")
+    p.add_argument("--ignore-label", type=int, default=255)
+    p.add_argument("--batch-size", type=int, default=4)
+    p.add_argument("--input-size", type=str, default="769,769")
+    p.add_argument("--whole", type=str2bool, default="False", help="whole-image instead of sliding-window prediction")
+    p.add_argument("--flip", type=str2bool, default="False")
+    p.add_argument("--ms", type=str, default="1", help="comma-separated scales")
+    p.add_argument("--iou-type", type=str, default="segm", choices=("segm", "boundary"))
+    p.add_argument("--dilation-ratio", type=float, default=0.02)
+    p.add_argument("--model", type=str, default="deeplabv3")
+    p.add_argument("--backbone", type=str, default="resnet50")
+    p.add_argument("--backbone-para", type=str, default='{"pretrained": false}')
+    p.add_argument("--model-para", type=str, default="{}")
+    p.add_argument("--align-corner", type=str2bool, default="True")
+    p.add_argument("--restore-from", type=str, default=None)
+    p.add_argument("--channel-cfg", type=str, default=None, help="path to channel_cfg.")
+    p.add_argument("--use-trt", type=str2bool, default="False", help="evaluate through the frozen fp16 engine")
+    p.add_argument("--num-classes", type=int, default=19)
+    p.add_argument("--num-images", type=int, default=40)
+    p.add_argument("--seed", type=int, default=12345)
+    p.add_argument("--snapshot-dir", type=str, default="ckpt")
+    return p
+
+
+class SyntheticSegDataset:
+    """Images N(0,1); ground truth piecewise constant, so that a boundary metric means something: one class per image
+    overlaid with seeded random rectangles of random classes, then ignore rectangles over about 5 % of the area."""
+
+    def __init__(self, num_classes, ignore_label, size, seed, rectangles=24, ignore_rectangles=5):
+        self.num_classes, self.ignore_label, self.size = num_classes, ignore_label, size
+        self.rectangles, self.ignore_rectangles = rectangles, ignore_rectangles
+        self.gen = torch.Generator().manual_seed(seed)
+
+    def _int(self, lo, hi):
+        return int(torch.randint(lo, max(lo + 1, hi), (1,), generator=self.gen))
+
+    def labels(self, n):
+        h, w = self.size
+        lab = torch.empty((n, h, w), dtype=torch.int64)
+        ih, iw = max(1, round(h * 0.1)), max(1, round(w * 0.1))     # 5 of 1 % each, overlaps aside
+        for i in range(n):
+            lab[i] = self._int(0, self.num_classes)
+            for _ in range(self.rectangles):
+                rh, rw = self._int(max(1, h // 16), max(2, h // 2)), self._int(max(1, w // 16), max(2, w // 2))
+                y, x = self._int(0, h - rh + 1), self._int(0, w - rw + 1)
+                lab[i, y:y + rh, x:x + rw] = self._int(0, self.num_classes)
+            for _ in range(self.ignore_rectangles):
+                y, x = self._int(0, h - ih + 1), self._int(0, w - iw + 1)
+                lab[i, y:y + ih, x:x + iw] = self.ignore_label
+        return lab
+
+    def batch(self, n, device):
+        h, w = self.size
+        images = torch.randn(n, 3, h, w, generator=self.gen)
+        return images.to(device), self.labels(n).to(device)
+
+
+def build_model(args):
+    model = getattr(networks, args.model).Seg_Model(
+        backbone=args.backbone, backbone_para=json.loads(args.backbone_para), model_para=json.loads(args.model_para),
+        num_classes=args.num_classes, align_corner=args.align_corner, criterion=None, deepsup=False)
+    if args.channel_cfg:
+        init_pruned_model(model, torch.load(args.channel_cfg, weights_only=False))
+    if args.restore_from:
+        load_model(model, args.restore_from)
+    return model.eval()
+
+
+def main(argv=None):
+    args = get_parser().parse_args(argv)
+    h, w = map(int, args.input_size.split(","))
+    scales = [float(s) for s in args.ms.split(",")]
+    C = args.num_classes
+    device = torch.device("cuda:0")
+    torch.manual_seed(args.seed)
+    model = build_model(args)
+    model = deploy.freeze(model).to(device) if args.use_trt else model.to(device)
+    dataset = SyntheticSegDataset(C, args.ignore_label, (h, w), args.seed)
+    boundary = args.iou_type == "boundary"
+    conf = torch.zeros((C, C + 1 if boundary else C), dtype=torch.int64, device=device)
+    nbatches = max(1, (args.num_images + args.batch_size - 1) // args.batch_size)
+    warmup = min(FPS_WARMUP, nbatches - 1)       # (the reference needs more than 5 batches; fewer are all timed but one)
+    pure_inf_time, metric_time, timed_images, fps = 0.0, 0.0, 0, 0.0
+    for idx in range(nbatches):
+        n = min(args.batch_size, args.num_images - idx * args.batch_size) if args.num_images > 0 else args.batch_size
+        image, label = dataset.batch(n, device)
+        with torch.no_grad():
+            torch.cuda.synchronize()
+            start_time = time.perf_counter()
+            if args.whole and scales == [1.0]:
+                pred = ev.predict_labels(model, image)
+            else:
+                output = ev.predict_multiscale(model, image, (h, w), scales, C, args.flip, args.align_corner, args.whole)
+                pred = ops.upsample_argmax(output, (h, w), True)      # same size, corners aligned: the plain argmax
+            torch.cuda.synchronize()
+            elapsed = time.perf_counter() - start_time
+            if boundary:
+                ev.boundary_confusion_matrix(label, pred, C, args.dilation_ratio, args.ignore_label, out=conf)
+            else:
+                ev.get_confusion_matrix(label, pred, C, args.ignore_label, out=conf)
+            torch.cuda.synchronize()
+            metric = time.perf_counter() - start_time - elapsed
+        print_str = " Iter%d/%d" % (idx + 1, nbatches)
+        if idx >= warmup:
+            pure_inf_time += elapsed
+            metric_time += metric
+            timed_images += n
+            fps = timed_images / pure_inf_time
+            print_str += f" FPS: {fps:.2f} img / s, metric {metric * 1e3:.3f} ms"
+        print(print_str, flush=True)
+
+    if boundary:
+        mean_IU, IU_array = ev.boundary_iou(conf)
+    else:
+        mean_IU, IU_array = ev.mean_iou(conf)
+    cm = conf.double().cpu()
+    pos, res, tp = cm.sum(1), cm[:, :C].sum(0), cm[:, :C].diag()
+    IU_array = IU_array.cpu().numpy()
+    p, r = tp / (res + 1e-5), tp / (pos + 1e-5)
+    print({"meanIU": mean_IU, "IU_array": IU_array})
+    os.makedirs(args.snapshot_dir, exist_ok=True)
+    with open(os.path.join(args.snapshot_dir, "result.txt"), "a") as f:
+        f.write("test with {}\n".format(args.restore_from))
+        f.write(json.dumps({"meanIU": mean_IU, "IU_array": IU_array.tolist()}) + "\n")
+        f.write(json.dumps({"meanP": p.mean().item(), "p": p.tolist()}) + "\n")
+        f.write(json.dumps({"meanR": r.mean().item(), "r": r.tolist()}) + "\n")
+        f.write(json.dumps({"FPS": fps, "iou_type": args.iou_type, "images": timed_images,
+                            "metric_ms_per_batch": metric_time * 1e3 / max(1, nbatches - warmup),
+                            "tp": tp.tolist(), "pos": pos.tolist(), "res": res.tolist()}) + "\n")
+        f.write("--------\n")
+    return mean_IU
+
+
+if __name__ == "__main__":
+    main()
