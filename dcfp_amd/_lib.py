@@ -147,6 +147,9 @@ SIGNATURES = {
     "dcfp_avgpool_nhwc_f16": (_I, [_P, _P, _I, _L, _I, _I, _I, _P, _Z, _P]),
     "dcfp_broadcast_nhwc_f16": (_I, [_P, _I, _P, _I, _L, _I, _I, _I, _P]),
     "dcfp_nchw_f32_to_nhwc_f16": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    "dcfp_resize_bilinear_nhwc_f16": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P]),
+    "dcfp_pyramid_pool_nhwc_f16_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _P]),
+    "dcfp_pyramid_pool_nhwc_f16": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
 }
 
 

@@ -1,16 +1,22 @@
 """Half-precision deployment engine — the fourth stage of the reference's pipeline (totrt.py / scripts/cs/trt.sh:
 freeze the fine-tuned, pruned network into an FP16 engine, save it, time it, evaluate through it).
 
-`freeze(model)` walks an eval-mode DeepLabv3 / `simple` Seg_Model (full width or slimmed by
-pruners.init_pruned_model) once and returns an `Engine`: a flat plan of layer records over numbered activation
-buffers plus the packed tensors.  Planning and packing are plain torch on the CPU; running the plan needs the device
-and goes through the kernels of csrc/conv_f16.hip only:
+`build_engine(model)` walks an eval-mode Seg_Model of any of the four heads - `simple`, `deeplabv3`, `deeplabv3p`, `psp`,
+full width or slimmed by pruners.init_pruned_model - once and returns an `Engine`: a flat plan of layer records over
+numbered activation buffers plus the packed tensors.  (`freeze(model)` is the older entry point for `deeplabv3` and
+`simple` and gives the same engine for them.)  Planning and packing are plain torch on the CPU; running the plan needs
+the device and goes through the kernels of csrc/conv_f16.hip and csrc/heads_f16.hip only:
 
   * activations NHWC fp16, channels padded to a multiple of 8 (the padding holds exact zeros);
   * weights [Cout8][kh][kw][Cin8] fp16 with the eval-mode BatchNorm scale folded in (in fp64, one rounding), the
     BatchNorm shift (and a conv bias) as an fp32 vector added in the conv's epilogue, with the residual add and ReLU;
   * the ASPP branches write their channel slice of the concat buffer (no cat), the image-pool branch is a global
-    average pool, a 1x1 conv on N pixels and a broadcast; the classifier writes fp32 NCHW logits.
+    average pool, a 1x1 conv on N pixels and a broadcast; the classifier writes fp32 NCHW logits;
+  * DeepLabv3+: the decoder concat [ASPP output resized, conv1(layer1)] is one buffer - a `resize` node and
+    decoder.conv1 write its two slices; the layer1 output stays alive until then;
+  * PSPNet: the concat [stage 0 .. 3, feats] is one buffer - the last bottleneck's conv3 writes the feats slice
+    directly, one `pyramid` node pools all levels from that slice in one sweep, a 1x1 conv per level runs on the s x s
+    map and a `resize` node writes each prior into its slice.
 
 An Engine offers what evaluate.predict_whole / predict_sliding / predict_multiscale / predict_labels ask of a net:
 engine(image) -> [logits], engine.lowres_logits(image) -> [lowres], engine.align_corner.
@@ -25,6 +31,7 @@ from ._lib import check
 
 FORMAT = 1
 _POOL_OPS = ("maxpool", "avgpool", "broadcast")
+PYRAMID_MAX_LEVELS, PYRAMID_MAX_SIZE = 4, 8         # what dcfp_pyramid_pool_nhwc_f16 takes
 
 
 def _r8(c):
@@ -95,13 +102,14 @@ class _Planner:
                "y_off": int(y_off), "f32": bool(f32), "segments": [list(sg) for sg in self.segments[src]],
                "w": self.tensor(pack_weight(conv.weight, scale, self.segments[src], self.pitch[src])),
                "shift": self.tensor(sh)}
-        if res >= 0 and self.pitch[res] != self.pitch[dst]:
-            raise ValueError(f"freeze: {name}: residual of {self.pitch[res]} channels on {self.pitch[dst]}")
+        if res >= 0 and [tuple(sg) for sg in self.segments[res]] != [(0, int(cout))]:
+            # (the residual keeps its own pitch - the kernel takes res_pitch - but holds the conv's channels from 0)
+            raise ValueError(f"freeze: {name}: residual holds {self.segments[res]}, the conv writes {cout} channels")
         self.records.append(rec)
         return dst
 
-    def node(self, op, name, src, dst, y_off=0):
-        self.records.append({"op": op, "name": name, "src": src, "dst": dst, "y_off": int(y_off)})
+    def node(self, op, name, src, dst, y_off=0, **extra):
+        self.records.append({"op": op, "name": name, "src": src, "dst": dst, "y_off": int(y_off), **extra})
         return dst
 
 
@@ -127,7 +135,9 @@ def _plan_sequential(pl, prefix, mods, x, tail_bn=None):
     return x
 
 
-def _plan_backbone(pl, bb, x):
+def _plan_backbone(pl, bb, x, tail=None):
+    """{1..4: the output buffer of layer1..4}.  tail = (buffer, offset): the last block's conv3 writes that channel
+    slice of a buffer the caller made (PSPNet's concat) instead of a buffer of its own."""
     from .networks.backbone.resnet import Bottleneck, ResNet
     if not isinstance(bb, ResNet):
         raise NotImplementedError(f"freeze: backbone {type(bb).__module__}.{type(bb).__name__} is not the ResNet")
@@ -136,8 +146,10 @@ def _plan_backbone(pl, bb, x):
     if not isinstance(mp, nn.MaxPool2d) or (mp.kernel_size, mp.stride, mp.padding) != (3, 2, 1):
         raise NotImplementedError(f"freeze: backbone.maxpool {mp}")
     x = pl.node("maxpool", "backbone.maxpool", x, pl.buffer(pl.segments[x]))
+    feats = {}
     for li in range(1, 5):
-        for bi, blk in enumerate(getattr(bb, f"layer{li}")):
+        layer = getattr(bb, f"layer{li}")
+        for bi, blk in enumerate(layer):
             p = f"backbone.layer{li}.{bi}"
             if not isinstance(blk, Bottleneck):
                 raise NotImplementedError(f"freeze: {p}: {type(blk).__name__}")
@@ -149,8 +161,12 @@ def _plan_backbone(pl, bb, x):
                 if len(ds) != 2:
                     raise NotImplementedError(f"freeze: {p}.downsample {blk.downsample}")
                 res = pl.conv(p + ".downsample.0", ds[0], ds[1], x, False)
-            x = pl.conv(p + ".conv3", blk.conv3, blk.bn3, out, True, res=res)
-    return x
+            if tail is not None and li == 4 and bi == len(layer) - 1:
+                x = pl.conv(p + ".conv3", blk.conv3, blk.bn3, out, True, res=res, dst=tail[0], y_off=tail[1])
+            else:
+                x = pl.conv(p + ".conv3", blk.conv3, blk.bn3, out, True, res=res)
+        feats[li] = x
+    return feats
 
 
 def _plan_aspp(pl, aspp, x):
@@ -174,33 +190,130 @@ def _plan_aspp(pl, aspp, x):
     return pl.conv("aspp.conv1", aspp.conv1, aspp.bn1, cat, True)
 
 
-def freeze(model, dtype=torch.float16):
-    """Freeze an eval-mode networks.deeplabv3 / networks.simple Seg_Model into an Engine (on the CPU; .to(device) or
-    load_engine(state, device) puts it on the GPU).  conv_deepsup is dropped."""
-    from .networks import deeplabv3, simple
+def _slices(widths):
+    """(offsets, pitch) of a concat buffer: every slice starts at a multiple of 8; the gaps hold the zero padding."""
+    offs, o = [], 0
+    for c in widths:
+        offs.append(o); o += _r8(c)
+    return offs, o
+
+
+def _is_plain_1x1(conv):
+    return (isinstance(conv, nn.Conv2d) and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.bias is None
+            and conv.padding == (0, 0) and conv.groups == 1)
+
+
+def _plan_psp(pl, model, x):
+    """Backbone -> pyramid, with no cat and no copy of the features (networks/tools/ppm.py)."""
+    from .networks.tools.ppm import PPMModule
+    ppm = model.ppm
+    if not isinstance(ppm, PPMModule):
+        raise NotImplementedError(f"freeze: ppm {type(ppm).__name__} is not the PPMModule")
+    if not 1 <= len(ppm.stages) <= PYRAMID_MAX_LEVELS:
+        raise NotImplementedError(f"freeze: ppm.stages has {len(ppm.stages)} stages (1 .. {PYRAMID_MAX_LEVELS} are supported)")
+    sizes = []
+    for k, st in enumerate(ppm.stages):
+        mods = list(st.children()) if isinstance(st, nn.Sequential) else []
+        if len(mods) != 4 or not isinstance(mods[0], nn.AdaptiveAvgPool2d) or not isinstance(mods[2], nn.BatchNorm2d) \
+                or not isinstance(mods[3], nn.ReLU):
+            raise NotImplementedError(f"freeze: ppm.stages.{k} {st} is not pool, conv, BatchNorm2d, ReLU")
+        size = mods[0].output_size
+        size = (size, size) if isinstance(size, int) else tuple(size)
+        if len(size) != 2 or size[0] != size[1] or not isinstance(size[0], int) or not 1 <= size[0] <= PYRAMID_MAX_SIZE:
+            raise NotImplementedError(f"freeze: ppm.stages.{k}.0 pools to {mods[0].output_size} "
+                                      f"(square sizes 1 .. {PYRAMID_MAX_SIZE} are supported)")
+        if not _is_plain_1x1(mods[1]):
+            raise NotImplementedError(f"freeze: ppm.stages.{k}.1 {mods[1]} is not a bias-free 1x1 conv")
+        sizes.append(int(size[0]))
+    c_feats = int(ppm.stages[0][1].weight.shape[1])
+    widths = [int(st[1].weight.shape[0]) for st in ppm.stages] + [c_feats]
+    offs, pitch = _slices(widths)
+    cat = pl.buffer(list(zip(offs, widths)), pitch=pitch)          # [stage 0 .. stage 3, feats] (ppm.py:37)
+    _plan_backbone(pl, model.backbone, x, tail=(cat, offs[-1]))
+    pooled = [pl.buffer([(0, c_feats)]) for _ in sizes]
+    pl.node("pyramid", "ppm.stages.pool", cat, pooled[0], dsts=pooled, x_off=offs[-1], c8=_r8(c_feats), sizes=sizes)
+    for k, st in enumerate(ppm.stages):
+        g = pl.conv(f"ppm.stages.{k}.1", st[1], st[2], pooled[k], True)
+        pl.node("resize", f"ppm.stages.{k}.up", g, cat, y_off=offs[k], align=bool(ppm.align_corners))
+    x = _plan_sequential(pl, "ppm.bottleneck", list(ppm.bottleneck.children()), cat)
+    if x == -1 or not isinstance(model.last_conv, nn.Conv2d) or model.last_conv.bias is None:
+        raise NotImplementedError(f"freeze: last_conv {model.last_conv} is not a classifier conv with a bias")
+    return pl.conv("last_conv", model.last_conv, None, x, False, f32=True)
+
+
+def _plan_deeplabv3p(pl, model, x):
+    """Backbone (layer1 tapped) -> ASPP -> decoder, the decoder concat written in slices (deeplabv3p.py:31-38)."""
+    from .networks.deeplabv3p import Decoder
+    dec = model.decoder
+    if not isinstance(dec, Decoder):
+        raise NotImplementedError(f"freeze: decoder {type(dec).__name__} is not the Decoder")
+    if not _is_plain_1x1(dec.conv1):
+        raise NotImplementedError(f"freeze: decoder.conv1 {dec.conv1} is not a bias-free 1x1 conv")
+    for name, _ in dec.named_children():
+        if name not in ("conv1", "bn1", "relu", "last_conv"):
+            raise NotImplementedError(f"freeze: module decoder.{name}")
+    feats = _plan_backbone(pl, model.backbone, x)
+    a = _plan_aspp(pl, model.aspp, feats[4])
+    widths = [sum(c for _, c in pl.segments[a]), int(dec.conv1.weight.shape[0])]
+    offs, pitch = _slices(widths)
+    cat = pl.buffer(list(zip(offs, widths)), pitch=pitch)          # [ASPP output resized, conv1(layer1)]
+    pl.conv("decoder.conv1", dec.conv1, dec.bn1, feats[1], True, dst=cat, y_off=offs[1])
+    pl.node("resize", "decoder.up", a, cat, y_off=offs[0], align=bool(dec.align_corner))
+    return _plan_sequential(pl, "decoder.last_conv", list(dec.last_conv.children()), cat)
+
+
+def _freeze(model, dtype, heads):
+    from . import networks
     if dtype != torch.float16:
         raise NotImplementedError(f"freeze: dtype {dtype}: the engine is fp16 only")
-    if type(model) not in (deeplabv3.Seg_Model, simple.Seg_Model):
+    kinds = {getattr(networks, h).Seg_Model: h for h in heads}
+    if type(model) not in kinds:
         raise NotImplementedError(f"freeze: {type(model).__module__}.{type(model).__name__} is not supported "
-                                  "(networks.deeplabv3 and networks.simple are)")
+                                  f"({' and '.join('networks.' + h for h in heads)} are" +
+                                  ("; deploy.build_engine freezes every head)" if len(heads) == 2 else ")"))
+    kind = kinds[type(model)]
     if model.training:
         raise RuntimeError("freeze: the model is in training mode; call model.eval() first (BatchNorm is folded from "
                            "its running statistics)")
+    own = {"simple": ("last_conv",), "deeplabv3": ("aspp", "last_conv"), "deeplabv3p": ("aspp", "decoder"),
+           "psp": ("ppm", "last_conv")}[kind]
     pl = _Planner()
     with torch.no_grad():
         x = pl.buffer([(0, 3)])                     # buffer 0: the converted input image
-        x = _plan_backbone(pl, model.backbone, x)
         for name, _ in model.named_children():
-            if name not in ("backbone", "aspp", "last_conv", "conv_deepsup", "criterion"):
+            if name not in ("backbone", "conv_deepsup", "criterion") + own:
                 raise NotImplementedError(f"freeze: module {name} of {type(model).__module__}")
-        if type(model) is deeplabv3.Seg_Model:
-            x = _plan_aspp(pl, model.aspp, x)
-        out = _plan_sequential(pl, "last_conv", list(model.last_conv.children()), x)
+        if kind == "psp":
+            out = _plan_psp(pl, model, x)
+        elif kind == "deeplabv3p":
+            out = _plan_deeplabv3p(pl, model, x)
+        else:
+            x = _plan_backbone(pl, model.backbone, x)[4]
+            if kind == "deeplabv3":
+                x = _plan_aspp(pl, model.aspp, x)
+            out = _plan_sequential(pl, "last_conv", list(model.last_conv.children()), x)
     if out != -1:
         raise NotImplementedError("freeze: last_conv does not end in a classifier conv with a bias")
     meta = {"align_corner": bool(model.align_corner), "num_classes": int(pl.records[-1]["cout"]), "in_channels": 3,
-            "dtype": "float16", "model": type(model).__module__.rsplit(".", 1)[-1]}
+            "dtype": "float16", "model": kind}
     return Engine({"format": FORMAT, "meta": meta, "plan": pl.records, "buffers": list(pl.pitch), "tensors": pl.tensors})
+
+
+def freeze(model, dtype=torch.float16):
+    """Freeze an eval-mode networks.deeplabv3 / networks.simple Seg_Model into an Engine (on the CPU; .to(device) or
+    load_engine(state, device) puts it on the GPU).  conv_deepsup is dropped.
+
+    This is the engine's first entry point and it keeps its contract, which includes refusing the other heads by name;
+    build_engine is the entry point for all four heads and returns exactly this engine for these two."""
+    return _freeze(model, dtype, ("deeplabv3", "simple"))
+
+
+def build_engine(model, dtype=torch.float16):
+    """Freeze an eval-mode Seg_Model of networks.simple / deeplabv3 / deeplabv3p / psp into an Engine (on the CPU;
+    .to(device) or load_engine(state, device) puts it on the GPU).  conv_deepsup is dropped.  What the planner does not
+    know - a pyramid size outside 1 .. 8, more than 4 stages, a stage conv that is not a bias-free 1x1 - raises
+    NotImplementedError naming the module."""
+    return _freeze(model, dtype, ("deeplabv3", "simple", "deeplabv3p", "psp"))
 
 
 def load_engine(path_or_dict, device=None):
@@ -230,7 +343,7 @@ class Engine:
         self.training = False
         first, last = {0: -1}, {}
         for i, r in enumerate(self.plan):
-            for b in (r["src"], r["dst"], r.get("res", -1)):
+            for b in [r["src"], r["dst"], r.get("res", -1)] + list(r.get("dsts", ())):
                 if b >= 0:
                     first.setdefault(b, i)
                     last[b] = i
@@ -280,8 +393,17 @@ class Engine:
                 o = ((h - 1) // 2 + 1, (w - 1) // 2 + 1)
             elif r["op"] == "avgpool":
                 o = (1, 1)
-            else:                                    # broadcast: the destination's own size
+            elif r["op"] == "pyramid":               # one s x s map per level; "dst" is the first of them
+                for b, s in zip(r["dsts"], r["sizes"]):
+                    if hw.setdefault(b, (s, s)) != (s, s):
+                        raise RuntimeError(f"deploy.Engine: {r['name']} writes {(s, s)} into a {hw[b]} buffer")
+                o = (r["sizes"][0],) * 2
+            elif r["op"] in ("broadcast", "resize"):   # the destination's own size
+                if r["dst"] not in hw:
+                    raise RuntimeError(f"deploy.Engine: {r['name']} writes a buffer of unknown size")
                 o = hw[r["dst"]]
+            else:
+                raise RuntimeError(f"deploy.Engine: unknown op {r['op']} ({r['name']})")
             if min(o) < 1:
                 raise RuntimeError(f"deploy.Engine: a {H}x{W} input is too small for {r['name']}")
             if hw.setdefault(r["dst"], o) != o:
@@ -308,11 +430,20 @@ class Engine:
             if self._slots[s] is None or self._slots[s].numel() < n:
                 self._slots[s] = torch.empty(n, dtype=torch.uint8, device=self.device)
                 grown = True
-        # the average pool's partial sums: sized before any launch list is built and grown like a slot, so that no
-        # cached list keeps a pointer into a buffer that has been given back
-        ws_need = max([int(L.dcfp_avgpool_nhwc_f16_workspace_bytes(N, self.buffers[r["src"]],
-                                                                    hw[r["src"]][0] * hw[r["src"]][1]))
-                       for r in self.plan if r["op"] == "avgpool"] + [0])
+        # the partial sums of the average pool and of the pyramid pool (one workspace: the launches of a call run in
+        # order on one stream): sized before any launch list is built and grown like a slot, so that no cached list
+        # keeps a pointer into a buffer that has been given back
+        ws_of = {}
+        for i, r in enumerate(self.plan):
+            h, w = hw[r["src"]]
+            if r["op"] == "avgpool":
+                ws_of[i] = int(L.dcfp_avgpool_nhwc_f16_workspace_bytes(N, self.buffers[r["src"]], h * w))
+            elif r["op"] == "pyramid":
+                sizes = (C.c_int * len(r["sizes"]))(*r["sizes"])
+                ws_of[i] = int(L.dcfp_pyramid_pool_nhwc_f16_workspace_bytes(N, h, w, r["c8"], len(sizes), sizes))
+                if ws_of[i] == 0:
+                    raise RuntimeError(f"deploy.Engine: {r['name']}: pyramid {r['sizes']} on a {h}x{w} map is not supported")
+        ws_need = max(list(ws_of.values()) + [0])
         if ws_need and (self._avg_ws is None or self._avg_ws.numel() < ws_need):
             self._avg_ws = torch.empty(ws_need, dtype=torch.uint8, device=self.device)
             grown = True
@@ -323,7 +454,7 @@ class Engine:
         def ptr(b):
             return C.c_void_p(self._slots[self._slot_of[b]].data_ptr())
         calls, descs, out_shape, out_call = [], [], None, None
-        for r in self.plan:
+        for i, r in enumerate(self.plan):
             h, w = hw[r["src"]]
             name = r["name"]
             if r["op"] == "conv":
@@ -349,15 +480,28 @@ class Engine:
                                ho, wo, self.buffers[r["dst"]])))
             elif r["op"] == "avgpool":
                 c8 = self.buffers[r["src"]]
-                nbytes = int(L.dcfp_avgpool_nhwc_f16_workspace_bytes(N, c8, h * w))
                 calls.append((name, L.dcfp_avgpool_nhwc_f16,
                               (ptr(r["src"]), ptr(r["dst"]), N, h * w, c8, c8, self.buffers[r["dst"]],
-                               C.c_void_p(self._avg_ws.data_ptr()), nbytes)))
+                               C.c_void_p(self._avg_ws.data_ptr()), ws_of[i])))
             elif r["op"] == "broadcast":
                 ho, wo = hw[r["dst"]]
                 c8 = self.buffers[r["src"]]
                 calls.append((name, L.dcfp_broadcast_nhwc_f16,
                               (ptr(r["src"]), c8, ptr(r["dst"]), N, ho * wo, c8, self.buffers[r["dst"]], r["y_off"])))
+            elif r["op"] == "resize":
+                ho, wo = hw[r["dst"]]
+                calls.append((name, L.dcfp_resize_bilinear_nhwc_f16,
+                              (ptr(r["src"]), N, h, w, self.buffers[r["src"]], self.buffers[r["src"]], ptr(r["dst"]),
+                               ho, wo, self.buffers[r["dst"]], r["y_off"], int(r["align"]))))
+            elif r["op"] == "pyramid":
+                n = len(r["sizes"])
+                sizes = (C.c_int * n)(*r["sizes"])
+                outs = (C.c_void_p * n)(*[ptr(b).value for b in r["dsts"]])
+                pitches = (C.c_int * n)(*[self.buffers[b] for b in r["dsts"]])
+                descs.append((sizes, outs, pitches))     # (kept alive with the launch list)
+                calls.append((name, L.dcfp_pyramid_pool_nhwc_f16,
+                              (ptr(r["src"]), N, h, w, r["c8"], self.buffers[r["src"]], r["x_off"], n, sizes, outs,
+                               pitches, C.c_void_p(self._avg_ws.data_ptr()), ws_of[i])))
             else:
                 raise RuntimeError(f"deploy.Engine: unknown op {r['op']} ({name})")
         if out_call is None:

@@ -573,6 +573,23 @@ int dcfp_broadcast_nhwc_f16(const void* v, int v_pitch, void* y, int N, int64_t 
                             dcfp_stream_t stream);
 /* The engine's input converter: x fp32 NCHW dense [N,C,H,W] -> y fp16 NHWC [N,H,W,C8], channels C .. C8-1 zero. */
 int dcfp_nchw_f32_to_nhwc_f16(const float* x, void* y, int N, int C, int H, int W, int C8, dcfp_stream_t stream);
+/* F.interpolate(mode='bilinear'), both align_corners modes, on NHWC fp16 (the DeepLabv3+ decoder's resize of the ASPP
+ * output, deeplabv3p.py:31, and the PSPNet priors, ppm.py:36): channels 0 .. C8-1 of x [N,h,w,x_pitch] ->
+ * y[n, Y, X, y_off + c] of y [N,H,W,y_pitch]; channels of y outside the slice are not touched.  Any h x w -> H x W.
+ * PyTorch's index math in fp32 (the weights of dcfp_upsample_bilinear_fwd_f32), fp32 interpolation, one rounding.
+ * A 1x1 source gives the bits of dcfp_broadcast_nhwc_f16. */
+int dcfp_resize_bilinear_nhwc_f16(const void* x, int N, int h, int w, int C8, int x_pitch, void* y, int H, int W,
+                                  int y_pitch, int y_off, int align_corners, dcfp_stream_t stream);
+/* nn.AdaptiveAvgPool2d(sizes[k]) for nlev <= 4 levels (sizes 1 .. 8) in one sweep (ppm.py:29): channels
+ * x_off .. x_off+C8-1 of x [N,H,W,x_pitch] -> y[k] dense [N, sizes[k], sizes[k], y_pitch[k]], channels 0 .. C8-1.
+ * PyTorch's windows (rows floor(i*H/s) .. ceil((i+1)*H/s)-1).  x is read once: pass 1 sums the cells between all the
+ * levels' window boundaries in fp32 into the workspace, pass 2 adds a window's cells (rows, then columns, ascending),
+ * divides by the area and rounds once.  Fixed order, no atomics.  workspace (16-byte aligned):
+ * dcfp_pyramid_pool_nhwc_f16_workspace_bytes(N, H, W, C8, nlev, sizes), 0 for arguments the kernel refuses. */
+size_t dcfp_pyramid_pool_nhwc_f16_workspace_bytes(int N, int H, int W, int C8, int nlev, const int* sizes);
+int dcfp_pyramid_pool_nhwc_f16(const void* x, int N, int H, int W, int C8, int x_pitch, int x_off, int nlev,
+                               const int* sizes, void* const* y, const int* y_pitch, void* workspace,
+                               size_t workspace_bytes, dcfp_stream_t stream);
 
 #ifdef __cplusplus
 }

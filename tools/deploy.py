@@ -72,7 +72,7 @@ def main(argv=None):
         init_pruned_model(model, torch.load(args.channel_cfg, weights_only=False))
     if args.restore_from:
         load_model(model, args.restore_from)
-    engine = deploy.freeze(model.eval())
+    engine = deploy.build_engine(model.eval())
     os.makedirs(args.save_dir, exist_ok=True)
     path = os.path.join(args.save_dir, "engine_fp16.pth")
     torch.save(engine.state_dict(), path)

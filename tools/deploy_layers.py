@@ -4,7 +4,7 @@
   rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python tools/deploy_layers.py --plan OUT/plan.json
   python tools/deploy_layers.py --report OUT --plan OUT/plan.json
 
-The first runs the frozen DeepLabv3 a few times under the profiler and writes the launch list of one call (one entry
+The first runs the frozen model (--model, default deeplabv3) a few times under the profiler and writes the launch list of one call (one entry
 per kernel launch, in order, with the FLOPs and the least bytes the layer needs, computed from its shapes).  The second
 matches the trace's engine kernels to that list by launch order (the last --iters calls; median per launch) and prints,
 per family: kernel time, achieved TF/s, the time at the fp16 matrix peak (2.5 PF dense) and at the measured HBM copy
@@ -22,7 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 PEAK_F16, HBM = 2.5e15, 6.29e12
 ENGINE_KERNELS = re.compile(r"conv_f16_kernel|maxpool_nhwc_f16|avgpool_partial|avgpool_final|broadcast_nhwc_f16|"
-                            r"nchw_f32_to_nhwc_f16")
+                            r"nchw_f32_to_nhwc_f16|resize_bilinear_kernel|pyramid_partial|pyramid_final")
 
 
 def family(name):
@@ -36,6 +36,22 @@ def family(name):
     if name in ("last_conv.0", "last_conv.3"):
         return "head 3x3"
     if name == "last_conv.6":
+        return "classifier (fp32 NCHW)"
+    if name == "ppm.stages.pool":
+        return "pyramid pool (4 levels, one sweep)"
+    if re.match(r"ppm\.stages\.\d\.up", name):
+        return "pyramid prior resizes"
+    if re.match(r"ppm\.stages\.\d\.1", name):
+        return "pyramid stage 1x1 (s x s maps)"
+    if name == "ppm.bottleneck.0":
+        return "pyramid bottleneck 3x3"
+    if name == "decoder.up":
+        return "decoder resize"
+    if name == "decoder.conv1":
+        return "decoder 1x1 (layer1 tap)"
+    if name in ("decoder.last_conv.0", "decoder.last_conv.3"):
+        return "decoder 3x3"
+    if name in ("decoder.last_conv.6", "last_conv"):
         return "classifier (fp32 NCHW)"
     if name.startswith("aspp.global_avg_pool") or name == "backbone.maxpool" or name == "input":
         return "pools / convert / broadcast"
@@ -59,6 +75,11 @@ def launches(engine, N, H, W):
         elif r["op"] == "avgpool":
             out.append((r["name"], 0, 2 * N * h * w * engine.buffers[r["src"]]))
             out.append((r["name"], 0, 0))
+        elif r["op"] == "pyramid":                      # two launches: the sweep over the features, then the bins
+            out.append((r["name"], 0, 2 * N * h * w * r["c8"]))
+            out.append((r["name"], 0, 0))
+        elif r["op"] == "resize":                       # store-bound: the bytes written
+            out.append((r["name"], 0, 2 * engine.buffers[r["src"]] * N * ho * wo))
         else:
             c8 = engine.buffers[r["src"]]
             out.append((r["name"], 0, 2 * c8 * N * (h * w + ho * wo) if r["op"] == "maxpool" else 2 * c8 * N * ho * wo))
@@ -70,16 +91,16 @@ def run(a):
     from dcfp_amd import deploy, networks
     h, w = [int(v) for v in a.size.split(",")]
     bb = {"os": 8, "mg_unit": [1, 2, 4], "inplanes": 128, "pretrained": False}
-    m = networks.deeplabv3.Seg_Model(backbone=a.backbone, backbone_para=bb, num_classes=19, align_corner=True,
-                                     deepsup=False).eval()
-    eng = deploy.freeze(m).to("cuda:0")
+    m = getattr(networks, a.model).Seg_Model(backbone=a.backbone, backbone_para=bb, num_classes=19, align_corner=True,
+                                             deepsup=False).eval()
+    eng = deploy.build_engine(m).to("cuda:0")
     x = torch.randn(a.batch, 3, h, w, device="cuda:0")
     for _ in range(3 + a.iters):
         eng.lowres_logits(x)
     torch.cuda.synchronize()
     with open(a.plan, "w") as f:
         json.dump({"iters": a.iters, "launches": launches(eng, a.batch, h, w),
-                   "what": f"DeepLabv3-{a.backbone} {a.batch}x3x{h}x{w}"}, f)
+                   "what": f"{a.model}-{a.backbone} {a.batch}x3x{h}x{w}"}, f)
 
 
 def report(a):
@@ -110,6 +131,7 @@ def report(a):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="deeplabv3", choices=("simple", "deeplabv3", "deeplabv3p", "psp"))
     ap.add_argument("--backbone", default="resnet101")
     ap.add_argument("--size", default="1024,2048")
     ap.add_argument("--batch", type=int, default=1)

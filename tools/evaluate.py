@@ -105,7 +105,7 @@ def main(argv=None):
     device = torch.device("cuda:0")
     torch.manual_seed(args.seed)
     model = build_model(args)
-    model = deploy.freeze(model).to(device) if args.use_trt else model.to(device)
+    model = deploy.build_engine(model).to(device) if args.use_trt else model.to(device)
     dataset = SyntheticSegDataset(C, args.ignore_label, (h, w), args.seed)
     boundary = args.iou_type == "boundary"
     conf = torch.zeros((C, C + 1 if boundary else C), dtype=torch.int64, device=device)
