@@ -53,6 +53,20 @@ class WpEntry(C.Structure):
                [(n, C.c_int32) for n in ("T", "Ck", "CkP", "M", "Mpad", "sAm", "sAc", "perm8")]
 
 
+class AugTap(C.Structure):
+    """DcfpAugTap: one column or row of the augmentation's geometry tables."""
+    _fields_ = [(n, C.c_int32) for n in ("src", "c0", "c1", "lsrc")]
+
+
+class AugSample(C.Structure):
+    """DcfpAugSample: one sample of an augmentation launch (host record, device pointers)."""
+    _fields_ = [("image", C.c_void_p), ("label", C.c_void_p)] + \
+               [(n, C.c_int32) for n in ("src_h", "src_w", "col_off", "row_off", "lut_a_off", "lut_b_off",
+                                         "hsv_flags", "hue_delta")] + \
+               [("sat_alpha", C.c_float), ("pad_", C.c_int32)]
+
+
+AUG_SATURATION, AUG_HUE = 1, 2
 SGD_CHUNK = 16384
 CONV_FWD, CONV_DGRAD, CONV_WGRAD = 0, 1, 2
 E_BADDESC, E_UNSUPPORTED, E_WORKSPACE = -1, -2, -3   # DCFP_E_* of include/dcfp_hip.h
@@ -138,6 +152,8 @@ SIGNATURES = {
     "dcfp_label_boundary_workspace_bytes": (_Z, [_I, _I, _I]),
     "dcfp_label_boundary_i32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _Z, _P]),
     "dcfp_label_boundary_i64": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _Z, _P]),
+    "dcfp_augment_u8_to_f32_nchw": (_I, [C.POINTER(AugSample), _I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _I, _P, _P, _P, _P]),
+    "dcfp_balance_weight_f32": (_I, [_P, _P, _P, _I, _L, _I, _I, _I, C.c_double, _P, _P]),
     "dcfp_eic_update_f32": (_I, [_P, _I, _F, _F, _P]),
     "dcfp_sgd_momentum_f32": (_I, [_P, _I, _L, _F, _F, _I, _P]),
     "dcfp_conv2d_fwd_f16_nhwc": (_I, [_H, _P, _P, _P, _P, _P, _P]),

@@ -1,0 +1,24 @@
+"""dcfp_amd.datasets: the data layer of the reference (`datasets/`) with the augmentation chain on the device.
+
+`build_dataset` has the reference's signature; the dataset root and list file come from `data_para` (keys `root`,
+`list_path`) instead of the reference's machine-specific `mypath.Path`.  Cityscapes (`CS`) is built; the reference's
+CTX, ADE and COCO classes are out of scope (the base class is general: num_classes, id table, class_weights)."""
+from . import cs as CSdatasets
+from .base import AugConfig, AugParams, BaseDataSet, draw_params  # noqa: F401
+from .loader import TrainLoader  # noqa: F401
+
+_DATASETS = {"CS": CSdatasets}
+
+
+def build_dataset(dataset, split="val", data_dir="val", crop_size=(512, 512), scale=False, mirror=False,
+                  brightness=False, ignore_label=255, balance=0, longsize=-1, shortsize=-1, data_para={}):
+    if dataset not in _DATASETS:
+        raise NotImplementedError("dataset %r: only %s are built (DESIGN §13)" % (dataset, sorted(_DATASETS)))
+    para = dict(data_para)
+    try:
+        root, list_path = para.pop("root"), para.pop("list_path")
+    except KeyError:
+        raise ValueError("data_para must name the dataset's `root` and `list_path` (split %r of %r)" % (data_dir, dataset))
+    return _DATASETS[dataset].DataSet(root, list_path, split=split, crop_size=crop_size, scale=scale, mirror=mirror,
+                                      brightness=brightness, ignore_label=ignore_label, balance=balance,
+                                      longsize=longsize, shortsize=shortsize, **para)

@@ -1948,3 +1948,66 @@ def label_boundary(labels, num_classes, d, background=255):
     check(fn(_p(src), _p(out), N, H, W, int(num_classes), int(d), int(background), _p(ws), ws.numel(), _stream()),
           "label_boundary")
     return out
+
+
+def augment_batch(images, labels, records, taps, lut_a, lut_b, id_table, crop_size, ignore_label=255):
+    """The device half of the training augmentation (datasets.base builds its arguments).
+    images: N uint8 [H,W,3] BGR tensors, labels: N uint8 [H,W] raw-id tensors or None, all on one device and dense;
+    records: N tuples (col_off, row_off, lut_a_off, lut_b_off, hsv_flags, hue_delta, sat_alpha); taps int32 [T,4],
+    lut_a uint8 [A] or None, lut_b float32 [B], id_table uint8 [256] or None: device tensors.
+    -> (fp32 [N,3,ch,cw], int64 [N,ch,cw], int32 [N,256] histogram); the last two are None without labels."""
+    N = len(images)
+    ch, cw = int(crop_size[0]), int(crop_size[1])
+    if N == 0 or len(records) != N or (labels is not None and len(labels) != N):
+        raise RuntimeError("augment_batch: one record (and one label map) per image expected")
+    dev = taps.device
+    for t, dt in ((taps, torch.int32), (lut_b, torch.float32), (lut_a, torch.uint8), (id_table, torch.uint8)):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
+            raise RuntimeError("dcfp_amd: the augmentation tables must be dense CUDA/HIP tensors (no CPU fallback exists)")
+    if taps.dim() != 2 or taps.shape[1] != 4 or (id_table is not None and id_table.numel() != 256):
+        raise RuntimeError("augment_batch: taps [T,4] and a 256-entry id table expected")
+    recs = (_lib.AugSample * N)()
+    for i, (img, r) in enumerate(zip(images, records)):
+        lab = None if labels is None else labels[i]
+        if not (img.is_cuda and img.device == dev and img.dtype == torch.uint8 and img.dim() == 3 and
+                img.shape[2] == 3 and img.is_contiguous()):
+            raise RuntimeError("augment_batch: dense uint8 [H,W,3] device images expected")
+        if lab is not None and not (lab.device == dev and lab.dtype == torch.uint8 and lab.is_contiguous() and
+                                    tuple(lab.shape) == tuple(img.shape[:2])):
+            raise RuntimeError("augment_batch: dense uint8 [H,W] device label maps of the images' sizes expected")
+        recs[i] = _lib.AugSample(img.data_ptr(), None if lab is None else lab.data_ptr(), img.shape[0], img.shape[1],
+                                 int(r[0]), int(r[1]), int(r[2]), int(r[3]), int(r[4]), int(r[5]), float(r[6]), 0)
+    out = torch.empty((N, 3, ch, cw), dtype=torch.float32, device=dev)
+    lab_out = hist = None
+    if labels is not None:
+        lab_out = torch.empty((N, ch, cw), dtype=torch.int64, device=dev)
+        hist = torch.empty((N, 256), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.lib().dcfp_augment_u8_to_f32_nchw(
+            recs, N, ch, cw, _p(taps), taps.shape[0], _p(lut_a), 0 if lut_a is None else lut_a.numel(), _p(lut_b),
+            lut_b.numel(), _p(id_table), int(ignore_label), _p(out), _p(lab_out), _p(hist), _stream()), "augment_batch")
+    return out, lab_out, hist
+
+
+def balance_weight(labels, hist, num_classes, balance, ignore_label=255, target_class=None, beta=0.9999):
+    """get_label (Base.py:73-89) on the device: int64 [N,H,W] trainId labels + the int32 [N,256] histogram of
+    augment_batch -> fp32 [N,H,W] class-balance weights (0 at ignore_label).  balance 1: 1/(n_c+1); balance 2:
+    (1+1e-8-beta^n_t)/(1+1e-8-beta^n_c) with the per-sample int32 [N] target_class; both clipped to [0,1], in fp64."""
+    if not isinstance(labels, torch.Tensor) or not labels.is_cuda:
+        raise RuntimeError("dcfp_amd: labels must be a CUDA/HIP tensor (no CPU fallback exists)")
+    if balance not in (1, 2) or labels.dtype != torch.int64 or labels.dim() != 3 or not labels.is_contiguous() or \
+            hist.dtype != torch.int32 or tuple(hist.shape) != (labels.shape[0], 256) or not hist.is_contiguous():
+        raise RuntimeError("balance_weight: balance 1 or 2, dense int64 [N,H,W] labels and an int32 [N,256] histogram expected")
+    if balance == 2:
+        if target_class is None:
+            raise RuntimeError("balance_weight: balance 2 needs the per-sample target class")
+        target_class = torch.as_tensor(target_class, dtype=torch.int32).to(labels.device).contiguous()
+        if target_class.numel() != labels.shape[0]:
+            raise RuntimeError("balance_weight: one target class per sample expected")
+    N = labels.shape[0]
+    weight = torch.empty(labels.shape, dtype=torch.float32, device=labels.device)
+    with torch.cuda.device(labels.device):
+        check(_lib.lib().dcfp_balance_weight_f32(_p(labels), _p(hist), _p(target_class) if balance == 2 else None, N,
+                                                 labels.shape[1] * labels.shape[2], int(num_classes), int(ignore_label),
+                                                 int(balance), float(beta), _p(weight), _stream()), "balance_weight")
+    return weight

@@ -501,6 +501,57 @@ int dcfp_label_boundary_i32(const int32_t* labels, int32_t* out, int N, int H, i
 int dcfp_label_boundary_i64(const int64_t* labels, int64_t* out, int N, int H, int W, int num_classes, int d,
                             int background, void* workspace, size_t workspace_bytes, dcfp_stream_t stream);
 
+/* ------------------------------------------------- training augmentation
+ * The train-split chain of datasets/Base.py:224-261 (id -> trainId, random scale, photometric jitter,
+ * input_transform, pad + random crop, mirror, get_label) on the device; DESIGN §13 states the arithmetic.  The host
+ * draws the random parameters and folds the geometry into tables; the device gathers.
+ *   taps   : device array of records, 16-byte aligned.  A sample's column table is taps[col_off .. col_off+crop_w),
+ *            its row table taps[row_off .. row_off+crop_h).  src = source column / row of the left / upper tap, or -1
+ *            where the output pixel is padding; c0 + c1 = 2048 weigh src and src + 1 (clamped to the last one);
+ *            lsrc = nearest-neighbour source column / row of the label.
+ *   lut_a  : device bytes; 256 per sample at lut_a_off (u8 -> u8 before the HSV block), lut_a_off = -1: identity.
+ *   lut_b  : device floats; 3 x 256 per sample at lut_b_off: output plane c (R, G, B) of a pixel is
+ *            lut_b[lut_b_off + 256*c + u8 of source channel 2 - c].
+ *   HSV    : hsv_flags != 0 runs the BGR -> HSV -> BGR round trip between the two tables: saturation S =
+ *            clip(rint(S * sat_alpha)) and / or hue H = (H + hue_delta) mod 180.
+ *   output : images fp32 [N,3,crop_h,crop_w] (0.0 in the padding); labels int64 [N,crop_h,crop_w] =
+ *            id_table[raw id] (id_table: 256 device bytes, NULL = identity; ignore_label, 0 .. 255, in the padding);
+ *            hist int32 [N,256] = per-sample count of every label value of the crop, padding included (zeroed here).
+ *            labels and hist may be NULL together (test split); hist alone may be NULL.
+ * `samples` is a HOST array of N records (their pointers are device pointers): it is validated here, before any
+ * launch, and travels by value in the kernel argument, 16 records per launch.  16-byte stores are used when crop_w is
+ * a multiple of 4 and images / labels are 16-byte aligned; any source address and size works. */
+#define DCFP_AUG_SATURATION 1
+#define DCFP_AUG_HUE 2
+typedef struct DcfpAugTap {
+    int32_t src, c0, c1, lsrc;
+} DcfpAugTap;
+typedef struct DcfpAugSample {
+    const uint8_t* image;       /* BGR uint8 [src_h, src_w, 3], dense                          */
+    const uint8_t* label;       /* raw ids uint8 [src_h, src_w], dense; NULL without labels     */
+    int32_t src_h, src_w;
+    int32_t col_off, row_off;   /* first record of the column / row table in taps              */
+    int32_t lut_a_off;          /* bytes into lut_a, or -1                                     */
+    int32_t lut_b_off;          /* floats into lut_b                                           */
+    int32_t hsv_flags;          /* DCFP_AUG_SATURATION | DCFP_AUG_HUE                          */
+    int32_t hue_delta;
+    float sat_alpha;
+    int32_t pad_;
+} DcfpAugSample;
+int dcfp_augment_u8_to_f32_nchw(const DcfpAugSample* samples, int N, int crop_h, int crop_w, const DcfpAugTap* taps,
+                                int64_t n_taps, const uint8_t* lut_a, int64_t lut_a_bytes, const float* lut_b,
+                                int64_t lut_b_floats, const uint8_t* id_table, int ignore_label, float* images,
+                                int64_t* labels, int32_t* hist, dcfp_stream_t stream);
+/* get_label (Base.py:73-89) from the histogram above: per sample, with n_c = hist[n][c] for c < num_classes,
+ *   balance 1: w_c = clip(1 / (n_c + 1), 0, 1)
+ *   balance 2: w_c = clip((1 + 1e-8 - beta^n_t) / (1 + 1e-8 - beta^n_c), 0, 1), t = target_class[n] (device int32 [N];
+ *              a target outside 0 .. num_classes-1 gives the sample weight 0)
+ * in fp64, rounded once; weight fp32 [N, pixels] = w[label], 0 where the label is ignore_label or no class.
+ * balance 0 computes nothing (the reference returns the plain label); balance outside 0 .. 2 is DCFP_E_BADDESC. */
+int dcfp_balance_weight_f32(const int64_t* labels, const int32_t* hist, const int32_t* target_class, int N,
+                            int64_t pixels, int num_classes, int ignore_label, int balance, double beta, float* weight,
+                            dcfp_stream_t stream);
+
 /* ------------------------------------------------------------- EIC score
  * dcfp_pruning.step (pruners/dcfp_pruner.py:15-20), all scored BN layers in one
  * launch.  table: device array of n_layers records; eic is updated in place:

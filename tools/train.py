@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Training + scoring driver — the loop of the reference's train.py:140-293 (same flags for
-the model / optimiser / loss / pruning options) over SYNTHETIC Cityscapes-shaped batches (the
-dataset loaders of the reference are outside the hot path: SURVEY.md §2 row 19).
+the model / optimiser / loss / pruning options).  Without --dataset it runs over SYNTHETIC Cityscapes-shaped
+batches; with --dataset (and the reference's data flags) it reads a list file through dcfp_amd.datasets, whose
+augmentation chain runs on the device.
 One process per GPU: `python -m torch.distributed.run --nproc-per-node N tools/train.py ...`."""
 import argparse
 import json
@@ -60,6 +61,18 @@ def get_parser():
     p.add_argument("--loss-para", type=str, default="{}")
     p.add_argument("--prune-type", type=str, default=None)
     p.add_argument("--channel-cfg", type=str, default=None)
+    p.add_argument("--dataset", type=str, default=None,
+                   help="CS: read real data through dcfp_amd.datasets (default: synthetic batches)")
+    p.add_argument("--data-dir", type=str, default="train", help="name of the data split (kept for the reference's scripts)")
+    p.add_argument("--random-mirror", action="store_true")
+    p.add_argument("--random-brightness", action="store_true")
+    p.add_argument("--random-scale", action="store_true")
+    p.add_argument("--balance", type=int, default=0, help="1 / 2: per-crop class-balance weights for the GSRL loss")
+    p.add_argument("--longsize", type=int, default=-1)
+    p.add_argument("--shortsize", type=int, default=-1)
+    p.add_argument("--data-para", type=str, default="{}",
+                   help='JSON: "root" and "list_path" of the dataset, further DataSet keywords '
+                        '("target_class" for --balance 2)')
     p.add_argument("--log-time", type=str2bool, default="False",
                    help="synchronise after every iteration and print its device time (batch synthesis excluded)")
     return p
@@ -93,7 +106,17 @@ def main(argv=None):
         seed = args.random_seed + (engine.local_rank if engine.distributed else 0)
         torch.manual_seed(seed)
         h, w = map(int, args.input_size.split(","))
-        dataset = SyntheticDataset(args.num_classes, args.ignore_label, (h, w), seed)
+        if args.dataset is None:
+            dataset = SyntheticDataset(args.num_classes, args.ignore_label, (h, w), seed)
+        else:
+            from dcfp_amd.datasets import build_dataset
+            data_para = json.loads(args.data_para)
+            target_class = data_para.pop("target_class", None)
+            dataset = build_dataset(args.dataset, split="train", data_dir=args.data_dir, crop_size=(h, w),
+                                    scale=args.random_scale, mirror=args.random_mirror,
+                                    brightness=args.random_brightness, ignore_label=args.ignore_label,
+                                    balance=args.balance, longsize=args.longsize, shortsize=args.shortsize,
+                                    data_para=data_para)
         criterion = build_criterions(args.loss_type, dataset, json.loads(args.loss_para))
         seg_model = getattr(networks, args.model).Seg_Model(
             backbone=args.backbone, backbone_para=json.loads(args.backbone_para),
@@ -114,12 +137,31 @@ def main(argv=None):
         model = engine.data_parallel(seg_model)
         model.train()
         per_rank = max(1, args.batch_size // engine.world_size)
+        batches = None
+        if args.dataset is not None:
+            from dcfp_amd.datasets import TrainLoader
+            with torch.cuda.device(device):
+                loader = TrainLoader(dataset, per_rank, device, seed=args.random_seed, target_class=target_class)
+            if len(loader) == 0:
+                raise ValueError("the list file holds fewer samples than one batch per rank")
+
+            def epochs():
+                while True:
+                    yield from loader
+            batches = epochs()
         for it in range(args.start_iters, args.num_steps):
-            images, labels = dataset.batch(per_rank, device)
+            if batches is None:
+                images, labels = dataset.batch(per_rank, device)
+            else:
+                with torch.cuda.device(device):
+                    images, labels = next(batches)
             if args.log_time:
                 torch.cuda.synchronize()
                 t_it = time.perf_counter()
-            if "gsrl" in args.loss_type:   # fine-tune stage: {'ori', 'weight'} labels (datasets/Base.py:73-89)
+            if "gsrl" in args.loss_type and not isinstance(labels, dict):
+                if batches is not None:
+                    raise ValueError("--loss-type gsrl on --dataset needs --balance 1 or 2 (the per-crop weights)")
+                # fine-tune stage: {'ori', 'weight'} labels (datasets/Base.py:73-89); --dataset with --balance brings real ones
                 labels = {"ori": labels, "weight": 1.0 + (labels % 3 == 0).float()}
             optimizer.zero_grad()
             lr = adjust_learning_rate(optimizer, args.learning_rate, it, args.num_steps, args.power, args.warmup)
