@@ -66,6 +66,14 @@ class AugSample(C.Structure):
                [("sat_alpha", C.c_float), ("pad_", C.c_int32)]
 
 
+class CcSample(C.Structure):
+    """DcfpCcSample: one sample of a connected-components launch (host record, device pointer)."""
+    _fields_ = [("label", C.c_void_p)] + \
+               [(n, C.c_int32) for n in ("src_h", "src_w", "dst_h", "dst_w", "Hp", "Wp", "row_off", "col_off", "cls",
+                                         "pad_")] + \
+               [("work_off", C.c_int64)]
+
+
 AUG_SATURATION, AUG_HUE = 1, 2
 SGD_CHUNK = 16384
 CONV_FWD, CONV_DGRAD, CONV_WGRAD = 0, 1, 2
@@ -154,6 +162,9 @@ SIGNATURES = {
     "dcfp_label_boundary_i64": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _Z, _P]),
     "dcfp_augment_u8_to_f32_nchw": (_I, [C.POINTER(AugSample), _I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _I, _P, _P, _P, _P]),
     "dcfp_balance_weight_f32": (_I, [_P, _P, _P, _I, _L, _I, _I, _I, C.c_double, _P, _P]),
+    "dcfp_components_workspace_bytes": (_Z, [_I, _I]),
+    "dcfp_label_components_u8": (_I, [C.POINTER(CcSample), _I, _P, _L, _P, _P, _Z, _P, _P]),
+    "dcfp_component_pixel_i32": (_I, [C.POINTER(CcSample), _I, _P, _Z, _P, _P, _P, _P, _P]),
     "dcfp_eic_update_f32": (_I, [_P, _I, _F, _F, _P]),
     "dcfp_sgd_momentum_f32": (_I, [_P, _I, _L, _F, _F, _I, _P]),
     "dcfp_conv2d_fwd_f16_nhwc": (_I, [_H, _P, _P, _P, _P, _P, _P]),

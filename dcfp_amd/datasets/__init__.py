@@ -2,9 +2,11 @@
 
 `build_dataset` has the reference's signature; the dataset root and list file come from `data_para` (keys `root`,
 `list_path`) instead of the reference's machine-specific `mypath.Path`.  Cityscapes (`CS`) is built; the reference's
-CTX, ADE and COCO classes are out of scope (the base class is general: num_classes, id table, class_weights)."""
+CTX, ADE and COCO classes are out of scope (the base class is general: num_classes, id table, class_weights).
+`data_para={"resample": true}` selects the reference's class-balanced `resample` sampler; it needs the class index
+that `tools/label_index.py` writes next to the list file."""
 from . import cs as CSdatasets
-from .base import AugConfig, AugParams, BaseDataSet, draw_params  # noqa: F401
+from .base import AugConfig, AugParams, BaseDataSet, draw_crop, draw_params, draw_pre  # noqa: F401
 from .loader import TrainLoader  # noqa: F401
 
 _DATASETS = {"CS": CSdatasets}

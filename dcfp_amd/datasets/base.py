@@ -19,9 +19,15 @@ lookup-table arithmetic, so the device result is defined bit for bit:
            statements on arange(256).
   tables   crop offset, mirror and padding folded into one column and one row table per sample.
 
-Out of scope: the `resample` sampler (gen_index, label_index_*.pkl, the connected-components crop location) -
-`balance=2` takes its per-sample target class from the caller until that exists - and any claim of bit parity with cv2.
+The `resample` sampler (`resample=True`, the reference's fine-tune recipes): `tools/label_index.py` writes
+label_index_<DATASET>.pkl (per class, the files that hold it); `gen_index` builds the epoch index from it (every class
+as often as the most frequent one, `locate(index) -> (file, class)`); the crop is placed on a random pixel of a random
+8-connected component of that class on the scaled, padded label (`draw_pre` / `draw_crop`; the labelling and the pixel
+selection are ops.label_components / ops.component_pixel, csrc/components.hip) and `balance=2` takes the class as its
+target.  Out of scope: any claim of bit parity with cv2, its component numbering included.
 """
+import os
+import pickle
 import random
 from dataclasses import dataclass
 from typing import Optional
@@ -61,6 +67,16 @@ class AugConfig:
 def draw_params(rng, src_hw, cfg):
     """The reference's draws in the reference's order (Base.py:98-110, 112-182, 203-222, 240-258) from a
     random.Random; a step that returns early draws nothing more."""
+    p = draw_pre(rng, src_hw, cfg)
+    p.h_off = rng.randint(0, max(p.dst_h, cfg.crop_h) - cfg.crop_h)
+    p.w_off = rng.randint(0, max(p.dst_w, cfg.crop_w) - cfg.crop_w)
+    if cfg.mirror:
+        p.flip = rng.randint(0, 1) * 2 - 1 < 0          # image[:, :, ::flip]
+    return p
+
+
+def draw_pre(rng, src_hw, cfg):
+    """The draws before the crop: scale and photometric jitter."""
     H, W = int(src_hw[0]), int(src_hw[1])
     p = AugParams(dst_h=H, dst_w=W)
     if cfg.scale:
@@ -86,11 +102,53 @@ def draw_params(rng, src_hw, cfg):
             p.hue = rng.randint(-18, 18)
         if p.mode == 0:
             contrast()
-    p.h_off = rng.randint(0, max(p.dst_h, cfg.crop_h) - cfg.crop_h)
-    p.w_off = rng.randint(0, max(p.dst_w, cfg.crop_w) - cfg.crop_w)
-    if cfg.mirror:
-        p.flip = rng.randint(0, 1) * 2 - 1 < 0          # image[:, :, ::flip]
     return p
+
+
+def crop_steps(rng, p, cfg):
+    """The `resample` crop and mirror draws of one sample, in the reference's order (Base.py:203-222, 253-256), as a
+    generator of the questions only the device can answer: it yields ("count",) and is sent the number C of
+    components of the sample's class (the reference's nums - 1); with C >= 1 it draws n in 1..C, yields ("size", n)
+    and is sent that component's pixel count, draws k, yields ("pixel", n, k) and is sent (y, x), then makes the two
+    jitter draws; with C == 0 it makes the two plain draws.  Clipping and the mirror draw follow.  Fills p.h_off,
+    p.w_off, p.flip and returns the chosen pixel or None.  A batch advances its samples' generators in step, so that
+    each question costs one device call for all of them (loader.TrainLoader)."""
+    Hp, Wp = max(p.dst_h, cfg.crop_h), max(p.dst_w, cfg.crop_w)
+    pixel = None
+    count = yield ("count",)
+    if count >= 1:
+        n = rng.randint(1, count)
+        size = yield ("size", n)
+        k = rng.randint(0, size - 1)
+        pixel = yield ("pixel", n, k)
+        pixel = (int(pixel[0]), int(pixel[1]))
+        h_off = pixel[0] - cfg.crop_h // 2 - rng.randint(-(cfg.crop_h // 4), cfg.crop_h // 4)
+        w_off = pixel[1] - cfg.crop_w // 2 - rng.randint(-(cfg.crop_w // 4), cfg.crop_w // 4)
+    else:
+        h_off = rng.randint(0, Hp - cfg.crop_h)
+        w_off = rng.randint(0, Wp - cfg.crop_w)
+    p.h_off = min(max(h_off, 0), Hp - cfg.crop_h)
+    p.w_off = min(max(w_off, 0), Wp - cfg.crop_w)
+    if cfg.mirror:
+        p.flip = rng.randint(0, 1) * 2 - 1 < 0
+    return pixel
+
+
+def draw_crop(rng, p, cfg, counts_cb):
+    """crop_steps for one sample on its own: `counts_cb(question)` answers ("count",), ("size", n) and
+    ("pixel", n, k) as each draw needs it.  -> the chosen pixel or None."""
+    steps = crop_steps(rng, p, cfg)
+    try:
+        q = next(steps)
+        while True:
+            q = steps.send(counts_cb(q))
+    except StopIteration as done:
+        return done.value
+
+
+def index_seed(seed, epoch):
+    """The seed of one epoch's index: plain integer arithmetic, the same in every process (hash() is salted)."""
+    return int(seed) * 1000003 + int(epoch)
 
 
 def resize_taps(src_n, dst_n, f):
@@ -198,10 +256,12 @@ class BaseDataSet:
     def __init__(self, split="train", crop_size=(321, 321), mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225),
                  scale=True, mirror=True, brightness=True, ignore_label=255, balance=0, longsize=-1, shortsize=-1,
                  **kwargs):
-        if kwargs.get("resample", False):
-            raise NotImplementedError("the `resample` sampler of the reference is out of scope (DESIGN §13)")
         if balance not in (0, 1, 2):
             raise ValueError("balance must be 0, 1 or 2")
+        self.resample = bool(kwargs.get("resample", False))
+        self.seed = int(kwargs.get("seed", 0))         # of the epoch index; TrainLoader sets its own
+        self.class_files = None
+        self.file_index, self.class_index = [], []
         self.split = split
         self.crop_h, self.crop_w = crop_size
         self.mean, self.std = list(mean), list(std)
@@ -214,7 +274,45 @@ class BaseDataSet:
         self.id_to_trainid = {}
 
     def __len__(self):
+        if self.resample:
+            return int(self.class_files["label_f"].max() * self.num_classes)
         return len(self.files)
+
+    def load_index(self, path):
+        """label_index_<DATASET>.pkl of tools/label_index.py (or of the reference's label_index.py): {str(class):
+        [{'idx': file index, 'name': ...}], 'label_f': float64 [num_classes] list lengths}."""
+        if not os.path.isfile(path):
+            raise NotImplementedError("resample=True needs the class index %s, which does not exist: write it with "
+                                      "tools/label_index.py" % path)
+        with open(path, "rb") as f:
+            self.class_files = pickle.load(f)
+        for c in range(self.num_classes):
+            if len(self.class_files.get(str(c), ())) == 0:
+                raise ValueError("%s: class %d is in no file of the list, the resample index cannot balance it"
+                                 % (path, c))
+        self.gen_index(0)
+
+    def gen_index(self, epoch=0):
+        """Base.py:43-58: every class `length` times, its files in turn and a random sample for the remainder.  The
+        draws come from a generator seeded by (seed, epoch): every rank builds the same index without a broadcast."""
+        rng = random.Random(index_seed(self.seed, epoch))
+        length = int(self.class_files["label_f"].max())
+        self.file_index, self.class_index = [], []
+        for c in range(self.num_classes):
+            len_c = len(self.class_files[str(c)])
+            self.file_index += list(range(len_c)) * (length // len_c) + rng.sample(list(range(len_c)), length % len_c)
+            self.class_index += [c] * length
+
+    def pre_processing(self, epoch, max_epoch=None):
+        if self.resample:
+            self.gen_index(epoch)
+
+    def locate(self, index):
+        """-> (index into `files`, class the sample was drawn for or None)."""
+        if not self.resample:
+            return index, None
+        c = self.class_index[index]
+        return int(self.class_files[str(c)][self.file_index[index]]["idx"]), c
 
     @property
     def aug_config(self):

@@ -41,6 +41,9 @@ class DataSet(BaseDataSet):
             for image_path, label_path in self.img_ids:
                 self.files.append({"img": osp.join(root, image_path), "label": osp.join(root, label_path),
                                    "name": osp.splitext(osp.basename(label_path))[0]})
+        if self.resample:
+            self.load_index(osp.join(osp.dirname(list_path),
+                                     "label_index_CStest.pkl" if split == "test" else "label_index_CS.pkl"))
 
     @property
     def class_weights(self):

@@ -3,7 +3,17 @@
 A batch costs the host the file decoding, the random draws and a few KiB of tables (base.pack_batch); sources, label
 maps and tables travel in one pinned uint8 buffer and ops.augment_batch / ops.balance_weight produce the tensors the
 model takes.  Indices are sharded by rank the way torch's DistributedSampler does (seeded permutation per epoch, padded
-to a multiple of the world size, rank-strided)."""
+to a multiple of the world size, rank-strided).
+
+With a `resample` dataset the indices run over the dataset's epoch index (`pre_processing` at the start of every epoch,
+`locate(i)` -> file and class), the class is the `balance=2` target, and a batch is built in stages, because the crop
+offset depends on the device's answer: pre-crop draws; one staged copy of sources, label maps and nearest
+maps; ops.label_components; counts, then sizes, to the host; the n and k draws; ops.component_pixel; jitter and mirror
+draws; tables, ops.augment_batch and ops.balance_weight as before.  That is three small blocking copies per batch
+(counts; the sizes gathered right after; the pixels) in two round-trip stages - the accepted cost of placing the crop on
+the device's labelling.  Each sample of such a batch draws from its own child generator,
+random.Random(self.rng.getrandbits(64)), created in sample order, so that no sample's draws wait for another's answer;
+the order within a sample is the reference's."""
 import random
 from concurrent.futures import ThreadPoolExecutor
 
@@ -18,22 +28,26 @@ def _align16(n):
 class TrainLoader:
     def __init__(self, dataset, batch_size, device, seed=0, num_workers=4, rank=None, world_size=None, shuffle=True,
                  target_class=None):
-        """target_class: for balance == 2, an int or a callable (dataset index) -> class; the reference takes it from
-        its `resample` sampler, which is out of scope."""
+        """target_class: for balance == 2 on a dataset without `resample`, an int or a callable (dataset index) ->
+        class; a `resample` dataset brings the class of every sample itself (dataset.locate)."""
         import torch.distributed as dist
         if rank is None or world_size is None:
             on = dist.is_available() and dist.is_initialized()
             rank, world_size = (dist.get_rank(), dist.get_world_size()) if on else (0, 1)
-        if dataset.balance == 2 and target_class is None:
-            raise ValueError("balance=2 needs target_class (the `resample` sampler is out of scope)")
+        self.resample = bool(getattr(dataset, "resample", False))
+        if dataset.balance == 2 and target_class is None and not self.resample:
+            raise ValueError("balance=2 needs a `resample` dataset or target_class")
         self.dataset, self.batch_size, self.device = dataset, int(batch_size), torch.device(device)
         self.seed, self.rank, self.world_size, self.shuffle = int(seed), int(rank), int(world_size), shuffle
         self.target_class = target_class
         self.epoch = 0
         self.rng = random.Random(self.seed + self.rank)          # the augmentation draws, in sample order
         self.pool = ThreadPoolExecutor(max_workers=max(1, int(num_workers)))
+        if self.resample:
+            dataset.seed = self.seed                                 # every rank builds the same epoch index
         self.num_samples = -(-len(dataset) // self.world_size)
         self._id_table = None
+        self.last_pixels = None          # resample: the pixel every sample's crop was placed on (None: plain draws)
 
     def __len__(self):
         return self.num_samples // self.batch_size
@@ -56,9 +70,10 @@ class TrainLoader:
         return order[self.rank:total:self.world_size]
 
     def _submit(self, idx):
-        return [self.pool.submit(self.dataset.decode, i) for i in idx]
+        return [self.pool.submit(self.dataset.decode, self.dataset.locate(i)[0]) for i in idx]
 
     def __iter__(self):
+        self.dataset.pre_processing(self.epoch, None)
         idx = self.indices(self.epoch)
         self.epoch += 1
         batches = [idx[i:i + self.batch_size] for i in range(0, len(self) * self.batch_size, self.batch_size)]
@@ -72,10 +87,73 @@ class TrainLoader:
         """decoded: [(uint8 [H,W,3] BGR, uint8 [H,W] or None)] -> (images, labels) on the device."""
         ds = self.dataset
         hws = [im.shape[:2] for im, _ in decoded]
+        if self.resample and ds.split == "train":
+            return self.collate_resample(decoded, idx)
         params = [ds.draw_params(self.rng, hw) for hw in hws]
         return self.apply(decoded, params, idx)
 
-    def apply(self, decoded, params, idx=None):
+    def collate_resample(self, decoded, idx):
+        """The staged batch of a `resample` dataset (module docstring); idx: the batch's indices into the epoch index."""
+        from .. import ops
+        from . import base
+        ds, cfg = self.dataset, self.dataset.aug_config
+        hws = [im.shape[:2] for im, _ in decoded]
+        n = len(decoded)
+        classes = [ds.locate(i)[1] for i in idx]
+        rngs = [random.Random(self.rng.getrandbits(64)) for _ in range(n)]
+        params = [base.draw_pre(r, hw, cfg) for r, hw in zip(rngs, hws)]
+        maps, recs, off = [], [], 0
+        for p, (H, W), c in zip(params, hws, classes):
+            maps += [base.resize_taps(H, p.dst_h, p.f_scale)[:, 3], base.resize_taps(W, p.dst_w, p.f_scale)[:, 3]]
+            recs.append((p.dst_h, p.dst_w, max(p.dst_h, cfg.crop_h), max(p.dst_w, cfg.crop_w), off, off + p.dst_h, c))
+            off += p.dst_h + p.dst_w
+        views = self._stage([np.ascontiguousarray(np.concatenate(maps)).view(np.uint8)] +
+                            [im.reshape(-1) for im, _ in decoded] + [lab.reshape(-1) for _, lab in decoded])
+        d_maps = views[0].view(torch.int32)
+        d_images = [views[1 + i].view(hws[i][0], hws[i][1], 3) for i in range(n)]
+        d_labels = [views[1 + n + i].view(hws[i][0], hws[i][1]) for i in range(n)]
+        comp = ops.label_components(d_labels, recs, d_maps, self._device_id_table(), ds.ignore_label)
+
+        steps = [base.crop_steps(r, p, cfg) for r, p in zip(rngs, params)]
+        asked, pixels = [next(g) for g in steps], [None] * n
+
+        def answer(values):
+            for i, g in enumerate(steps):
+                if asked[i] is None:
+                    continue
+                try:
+                    asked[i] = g.send(values[i])
+                except StopIteration as done:
+                    asked[i], pixels[i] = None, done.value
+        answer(comp.counts())
+        if any(q is not None for q in asked):
+            answer(comp.sizes([q[1] if q else 0 for q in asked]))
+            yx = ops.component_pixel(comp, [q[1] if q else 0 for q in asked], [q[2] if q else 0 for q in asked])
+            answer(yx.tolist())
+        self.last_pixels = pixels
+        return self.apply(decoded, params, idx, sources=(d_images, d_labels), target=classes)
+
+    def _device_id_table(self):
+        if self._id_table is None:
+            self._id_table = torch.from_numpy(self.dataset.id_table()).to(self.device)
+        return self._id_table
+
+    def _stage(self, parts):
+        """uint8 arrays -> their device views: one pinned buffer, one copy."""
+        offs, total = [], 0
+        for p in parts:
+            offs.append(total)
+            total += _align16(p.size)
+        stage = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+        host = stage.numpy()
+        for p, o in zip(parts, offs):
+            host[o:o + p.size] = p
+        dev = stage.to(self.device, non_blocking=True)
+        return [dev[o:o + p.size] for p, o in zip(parts, offs)]
+
+    def apply(self, decoded, params, idx=None, sources=None, target=None):
+        """sources: (images, label maps) already on the device (the resample path staged them before the crop draws);
+        target: the balance=2 classes of the samples, else they come from `target_class`."""
         ds = self.dataset
         from .. import ops
         hws = [im.shape[:2] for im, _ in decoded]
@@ -89,36 +167,32 @@ class TrainLoader:
         parts = [taps.view(np.uint8).reshape(-1), lut_b.view(np.uint8).reshape(-1)]
         if lut_a is not None:
             parts.append(lut_a)
-        parts += [im.reshape(-1) for im, _ in decoded]
-        if with_labels:
-            parts += [lab.reshape(-1) for _, lab in decoded]
-        offs, total = [], 0
-        for p in parts:
-            offs.append(total)
-            total += _align16(p.size)
-        stage = torch.empty(total, dtype=torch.uint8, pin_memory=True)
-        host = stage.numpy()
-        for p, o in zip(parts, offs):
-            host[o:o + p.size] = p
-        dev = stage.to(self.device, non_blocking=True)
-        views = [dev[o:o + p.size] for p, o in zip(parts, offs)]
+        if sources is None:
+            parts += [im.reshape(-1) for im, _ in decoded]
+            if with_labels:
+                parts += [lab.reshape(-1) for _, lab in decoded]
+        views = self._stage(parts)
         d_taps = views.pop(0).view(torch.int32).view(-1, 4)
         d_lut_b = views.pop(0).view(torch.float32)
         d_lut_a = views.pop(0) if lut_a is not None else None
         n = len(decoded)
-        d_images = [views[i].view(hws[i][0], hws[i][1], 3) for i in range(n)]
-        d_labels = [views[n + i].view(hws[i][0], hws[i][1]) for i in range(n)] if with_labels else None
-        if self._id_table is None:
-            self._id_table = torch.from_numpy(ds.id_table()).to(self.device)
-        images, labels, hist = ops.augment_batch(d_images, d_labels, recs, d_taps, d_lut_a, d_lut_b, self._id_table,
-                                                 crop, ds.ignore_label)
+        if sources is None:
+            d_images = [views[i].view(hws[i][0], hws[i][1], 3) for i in range(n)]
+            d_labels = [views[n + i].view(hws[i][0], hws[i][1]) for i in range(n)] if with_labels else None
+        else:
+            d_images, d_labels = sources
+        images, labels, hist = ops.augment_batch(d_images, d_labels, recs, d_taps, d_lut_a, d_lut_b,
+                                                 self._device_id_table(), crop, ds.ignore_label)
         if not with_labels:
             return images, None
         if ds.balance > 0 and ds.split == "train":
-            target = None
-            if ds.balance == 2:
+            if ds.balance == 2 and target is None:
                 t = self.target_class
-                target = [t(i) if callable(t) else int(t) for i in (idx if idx is not None else range(n))]
-            weight = ops.balance_weight(labels, hist, ds.num_classes, ds.balance, ds.ignore_label, target, ds.beta)
+                if t is None:
+                    target = [ds.locate(i)[1] for i in idx]
+                else:
+                    target = [t(i) if callable(t) else int(t) for i in (idx if idx is not None else range(n))]
+            weight = ops.balance_weight(labels, hist, ds.num_classes, ds.balance, ds.ignore_label,
+                                        target if ds.balance == 2 else None, ds.beta)
             return images, {"ori": labels, "weight": weight}
         return images, labels

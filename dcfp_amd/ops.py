@@ -2011,3 +2011,102 @@ def balance_weight(labels, hist, num_classes, balance, ignore_label=255, target_
                                                  labels.shape[1] * labels.shape[2], int(num_classes), int(ignore_label),
                                                  int(balance), float(beta), _p(weight), _stream()), "balance_weight")
     return weight
+
+
+class Components:
+    """A labelled batch of `label_components`, left on the device.  Per sample s: `label_map(s)` int32
+    [Hp,Wp] (the smallest linear index of the pixel's component, -1 background), `labels(s)` the ascending list of
+    component labels and `component_sizes(s)` their pixel counts (both need `counts()`)."""
+
+    def __init__(self, records, layout, work, counts):
+        self.records, self.layout, self.work, self._counts_dev = records, layout, work, counts
+        self.N = len(layout)
+        self._i32 = work.view(torch.int32)
+        self._counts = None
+
+    def counts(self):
+        """The N component counts on the host: the one synchronisation of a labelled batch."""
+        if self._counts is None:
+            self._counts = self._counts_dev.tolist()
+        return self._counts
+
+    def sizes(self, n):
+        """Pixel count of component n[s] (1-based) of every sample, 0 where n[s] == 0: one gather, one copy."""
+        n = [int(v) for v in n]
+        if len(n) != self.N:
+            raise RuntimeError("Components.sizes: one component number per sample expected")
+        for v, c in zip(n, self.counts()):
+            if not 0 <= v <= c:
+                raise RuntimeError("Components.sizes: component %d of %d" % (v, c))
+        at = torch.tensor([lay["sizes"] + max(v, 1) - 1 for v, lay in zip(n, self.layout)], dtype=torch.int64)
+        got = self._i32[at.to(self.work.device)].tolist()
+        return [g if v > 0 else 0 for g, v in zip(got, n)]
+
+    def label_map(self, s):
+        lay = self.layout[s]
+        return self._i32[lay["base"]:lay["base"] + lay["Hp"] * lay["Wp"]].view(lay["Hp"], lay["Wp"])
+
+    def labels(self, s):
+        lay = self.layout[s]
+        return self._i32[lay["roots"]:lay["roots"] + self.counts()[s]]
+
+    def component_sizes(self, s):
+        lay = self.layout[s]
+        return self._i32[lay["sizes"]:lay["sizes"] + self.counts()[s]]
+
+
+def label_components(labels, records, maps, id_table, ignore_label=255):
+    """8-connected components of one class per sample on the scaled, padded label grid.
+    labels: N dense uint8 [H,W] raw-id device tensors; records: N tuples (dst_h, dst_w, Hp, Wp, row_off, col_off, cls);
+    maps: device int32 table holding every sample's nearest-neighbour row map [dst_h] at row_off and column map [dst_w]
+    at col_off; id_table: uint8 [256] or None.  Pixel (y, x) of the Hp x Wp grid is foreground iff y < dst_h, x < dst_w
+    and id_table[raw[row_map[y], col_map[x]]] == cls: the padding is background whatever `ignore_label` is (it is
+    taken for the call shape of the reference's padding and only range-checked).  -> Components; nothing is
+    synchronised here."""
+    N = len(labels)
+    if N == 0 or len(records) != N or not 0 <= int(ignore_label) <= 255:
+        raise RuntimeError("label_components: one record per label map and an ignore label in 0..255 expected")
+    if not (isinstance(maps, torch.Tensor) and maps.is_cuda and maps.dtype == torch.int32 and maps.is_contiguous()) or \
+            (id_table is not None and not (id_table.is_cuda and id_table.dtype == torch.uint8 and
+                                           id_table.numel() == 256 and id_table.is_contiguous())):
+        raise RuntimeError("dcfp_amd: the component maps and id table must be dense CUDA/HIP tensors "
+                           "(no CPU fallback exists)")
+    dev = maps.device
+    L = _lib.lib()
+    recs = (_lib.CcSample * N)()
+    layout, total = [], 0
+    for i, (lab, r) in enumerate(zip(labels, records)):
+        if not (isinstance(lab, torch.Tensor) and lab.is_cuda and lab.device == dev and lab.dtype == torch.uint8 and
+                lab.dim() == 2 and lab.is_contiguous()):
+            raise RuntimeError("label_components: dense uint8 [H,W] device label maps expected")
+        dst_h, dst_w, Hp, Wp, row_off, col_off, cls = (int(v) for v in r)
+        nbytes = L.dcfp_components_workspace_bytes(Hp, Wp)
+        if nbytes == 0:
+            raise RuntimeError("label_components: grid %dx%d is not supported" % (Hp, Wp))
+        recs[i] = _lib.CcSample(lab.data_ptr(), lab.shape[0], lab.shape[1], dst_h, dst_w, Hp, Wp, row_off, col_off,
+                                cls, 0, total)
+        base, p8, cap4 = total // 4, (Hp * Wp + 7) & ~7, (((Hp + 1) // 2) * ((Wp + 1) // 2) + 3) & ~3
+        layout.append({"Hp": Hp, "Wp": Wp, "base": base, "roots": base + 2 * p8, "sizes": base + 2 * p8 + cap4})
+        total += (nbytes + 15) & ~15
+    work = torch.empty(total, dtype=torch.uint8, device=dev)
+    counts = torch.empty(N, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(L.dcfp_label_components_u8(recs, N, _p(maps), maps.numel(), _p(id_table), _p(work), work.numel(),
+                                         _p(counts), _stream()), "label_components")
+    return Components(recs, layout, work, counts)
+
+
+def component_pixel(components, n, k):
+    """(y, x) of the k[s]-th pixel (0-based, linear-index order) of component n[s] (1-based) of every sample of a
+    labelled batch -> device int32 [N,2]; (-1, -1) where n[s] == 0.  A rank-select: the label map is read once."""
+    c = components
+    dev = c.work.device
+    nk = torch.tensor([[int(v) for v in n], [int(v) for v in k]], dtype=torch.int32)
+    if tuple(nk.shape) != (2, c.N):
+        raise RuntimeError("component_pixel: one (n, k) per sample expected")
+    nk = nk.to(dev)
+    yx = torch.empty((c.N, 2), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.lib().dcfp_component_pixel_i32(c.records, c.N, _p(c.work), c.work.numel(), _p(c._counts_dev),
+                                                  _p(nk[0]), _p(nk[1]), _p(yx), _stream()), "component_pixel")
+    return yx

@@ -552,6 +552,47 @@ int dcfp_balance_weight_f32(const int64_t* labels, const int32_t* hist, const in
                             int64_t pixels, int num_classes, int ignore_label, int balance, double beta, float* weight,
                             dcfp_stream_t stream);
 
+/* ------------------------------------------ connected components (resample sampler)
+ * The crop location of the `resample` sampler (Base.py:203-222): the 8-connected components of one class
+ * on the scaled, padded label grid, and the k-th pixel of a chosen component.  For a sample the grid is Hp x Wp
+ * (Hp >= dst_h, Wp >= dst_w); pixel (y, x) is foreground iff y < dst_h, x < dst_w and
+ *   id_table[label[maps[row_off + y] * src_w + maps[col_off + x]]] == cls
+ * (maps: device int32, the nearest-neighbour source row / column of every destination row / column, clamped to the
+ * source; id_table: 256 device bytes, NULL = identity).  Everything outside dst_h x dst_w is background.
+ * The label of a component is the smallest linear index y*Wp + x among its pixels; components are numbered 1 .. C in
+ * ascending order of that label; the pixels of a component are ordered by linear index.  Integer arithmetic only: the
+ * result is defined bit for bit and does not depend on the order in which blocks run.
+ * A sample owns the slice [work_off, work_off + dcfp_components_workspace_bytes(Hp, Wp)) of the work buffer (work_off a
+ * multiple of 16); as int32 it holds, each region starting on a multiple of 4 entries, with P = Hp*Wp, P8 = P rounded up
+ * to 8, cap = ceil(Hp/2)*ceil(Wp/2) (the most components 8-connectivity allows), nblk = ceil(P/2048):
+ *   [0, P)                    the label map (-1 background)
+ *   [P8, P8 + P)              scratch; at a component's label, its pixel count
+ *   [2*P8, +cap)              the labels of components 1 .. C, ascending
+ *   [2*P8 + up4(cap), +cap)   their pixel counts
+ *   then 2 * up4(nblk)        scan scratch
+ * `samples` is a HOST array of N records (label: device pointer), validated here before any launch
+ * (DCFP_E_BADDESC) and passed by value, 16 records per launch; samples may differ in every field.  counts: device
+ * int32 [N], the component count of every sample.  No host synchronisation inside either entry point. */
+typedef struct DcfpCcSample {
+    const uint8_t* label;       /* raw ids uint8 [src_h, src_w], dense                          */
+    int32_t src_h, src_w;
+    int32_t dst_h, dst_w;       /* the scaled size                                             */
+    int32_t Hp, Wp;             /* max(dst, crop): the padded grid                             */
+    int32_t row_off, col_off;   /* first entry of the row / column map in maps                 */
+    int32_t cls;                /* 0 .. 255                                                    */
+    int32_t pad_;
+    int64_t work_off;           /* bytes into the work buffer                                  */
+} DcfpCcSample;
+size_t dcfp_components_workspace_bytes(int Hp, int Wp);
+int dcfp_label_components_u8(const DcfpCcSample* samples, int N, const int32_t* maps, int64_t n_maps,
+                             const uint8_t* id_table, void* work, size_t work_bytes, int32_t* counts,
+                             dcfp_stream_t stream);
+/* yx int32 [N,2] = (y, x) of the k[s]-th pixel (0-based, linear-index order) of component n[s] (1-based) of a labelled
+ * batch; (-1, -1) where n[s] == 0 (skipped), n[s] > counts[s] or k[s] is not below the component's size.  n, k, counts:
+ * device int32 [N].  Reads the label map once plus one 2048-pixel segment per sample. */
+int dcfp_component_pixel_i32(const DcfpCcSample* samples, int N, void* work, size_t work_bytes, const int32_t* counts,
+                             const int32_t* n, const int32_t* k, int32_t* yx, dcfp_stream_t stream);
+
 /* ------------------------------------------------------------- EIC score
  * dcfp_pruning.step (pruners/dcfp_pruner.py:15-20), all scored BN layers in one
  * launch.  table: device array of n_layers records; eic is updated in place:

@@ -72,7 +72,8 @@ def get_parser():
     p.add_argument("--shortsize", type=int, default=-1)
     p.add_argument("--data-para", type=str, default="{}",
                    help='JSON: "root" and "list_path" of the dataset, further DataSet keywords '
-                        '("target_class" for --balance 2)')
+                        '("resample": true for the class-balanced sampler of the fine-tune recipes; "target_class" for '
+                        '--balance 2 without it)')
     p.add_argument("--log-time", type=str2bool, default="False",
                    help="synchronise after every iteration and print its device time (batch synthesis excluded)")
     return p
