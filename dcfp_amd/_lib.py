@@ -74,6 +74,12 @@ class CcSample(C.Structure):
                [("work_off", C.c_int64)]
 
 
+class VoteMap(C.Structure):
+    """DcfpVoteMap: the low-resolution logits of one (scale, flip) pass of a vote launch (host record, device pointer)."""
+    _fields_ = [("logits", C.c_void_p)] + [(n, C.c_int32) for n in ("h", "w", "hs", "ws", "flip")] + \
+               [("weight", C.c_float)]
+
+
 AUG_SATURATION, AUG_HUE = 1, 2
 SGD_CHUNK = 16384
 CONV_FWD, CONV_DGRAD, CONV_WGRAD = 0, 1, 2
@@ -157,6 +163,7 @@ SIGNATURES = {
     "dcfp_upsample_wce_bwd_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "dcfp_upsample_argmax_f32": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "dcfp_confusion_matrix_i64": (_I, [_P, _P, _I, _L, _I, _P, _P]),
+    "dcfp_vote_multiscale_f32": (_I, [C.POINTER(VoteMap), _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P]),
     "dcfp_label_boundary_workspace_bytes": (_Z, [_I, _I, _I]),
     "dcfp_label_boundary_i32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _Z, _P]),
     "dcfp_label_boundary_i64": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _Z, _P]),

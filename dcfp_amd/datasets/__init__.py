@@ -7,7 +7,7 @@ CTX, ADE and COCO classes are out of scope (the base class is general: num_class
 that `tools/label_index.py` writes next to the list file."""
 from . import cs as CSdatasets
 from .base import AugConfig, AugParams, BaseDataSet, draw_crop, draw_params, draw_pre  # noqa: F401
-from .loader import TrainLoader  # noqa: F401
+from .loader import EvalLoader, TrainLoader  # noqa: F401
 
 _DATASETS = {"CS": CSdatasets}
 

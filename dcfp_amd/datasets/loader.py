@@ -1,4 +1,4 @@
-"""TrainLoader: host threads decode, one pinned staging buffer and one copy per batch, the device does the rest.
+"""TrainLoader / EvalLoader: host threads decode, one pinned staging buffer and one copy per batch, the device does the rest.
 
 A batch costs the host the file decoding, the random draws and a few KiB of tables (base.pack_batch); sources, label
 maps and tables travel in one pinned uint8 buffer and ops.augment_batch / ops.balance_weight produce the tensors the
@@ -13,8 +13,13 @@ draws; tables, ops.augment_batch and ops.balance_weight as before.  That is thre
 (counts; the sizes gathered right after; the pixels) in two round-trip stages - the accepted cost of placing the crop on
 the device's labelling.  Each sample of such a batch draws from its own child generator,
 random.Random(self.rng.getrandbits(64)), created in sample order, so that no sample's draws wait for another's answer;
-the order within a sample is the reference's."""
+the order within a sample is the reference's.
+
+EvalLoader serves the `val` and `test` splits through the same staging and the same kernel (identity tables, id ->
+trainId, normalisation through LUT B): in file order, every file exactly once across the ranks (rank r takes r,
+r + world, ...; no wrap-around padding, the last batch may be short), a batch cut where the source size changes."""
 import random
+from collections import deque
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -196,3 +201,61 @@ class TrainLoader:
                                         target if ds.balance == 2 else None, ds.beta)
             return images, {"ori": labels, "weight": weight}
         return images, labels
+
+
+def cut_batches(stream, batch_size, key):
+    """Consecutive items of `stream` in lists of at most batch_size that agree in key(item)."""
+    batch = []
+    for item in stream:
+        if batch and (len(batch) == batch_size or key(item) != key(batch[0])):
+            yield batch
+            batch = []
+        batch.append(item)
+    if batch:
+        yield batch
+
+
+class EvalLoader(TrainLoader):
+    """Batches of a `val` / `test` dataset: (images fp32 [n,3,H,W], labels int64 [n,H,W] or None, metas) with
+    metas[i] = {'name', 'size': (H, W)}.  Every file is served exactly once across the ranks - unlike the reference's
+    DistributedSampler, which repeats files to even the shards and so counts them twice in the confusion matrix
+    (DESIGN §12)."""
+
+    def __init__(self, dataset, batch_size, device, num_workers=4, rank=None, world_size=None):
+        if dataset.split not in ("val", "test"):
+            raise ValueError("EvalLoader serves the val and test splits, not %r" % (dataset.split,))
+        if int(batch_size) < 1:
+            raise ValueError("EvalLoader: batch_size must be at least 1")
+        super().__init__(dataset, batch_size, device, seed=0, num_workers=num_workers, rank=rank, world_size=world_size,
+                         shuffle=False, target_class=0)      # (balance weights are a train-split matter: no target)
+        self.ahead = 2 * self.batch_size
+
+    def indices(self, epoch=0):
+        """This rank's files, in file order: r, r + world, ..."""
+        return list(range(self.rank, len(self.dataset.files), self.world_size))
+
+    def batches(self, sizes):
+        """The batches (lists of file indices) this rank serves when file i has size sizes[i]."""
+        return list(cut_batches(self.indices(), self.batch_size, lambda i: tuple(sizes[i])))
+
+    def __len__(self):
+        """Batches of this rank if all files have one size (a size change adds one)."""
+        return -(-len(self.indices()) // self.batch_size)
+
+    def _decoded(self):
+        """(file index, decoded) in order, `ahead` files decoding on the pool beyond the one handed out."""
+        idx, pending, nxt = self.indices(), deque(), 0
+        while pending or nxt < len(idx):
+            while nxt < len(idx) and len(pending) <= self.ahead:
+                pending.append((idx[nxt], self.pool.submit(self.dataset.decode, idx[nxt])))
+                nxt += 1
+            i, f = pending.popleft()
+            yield i, f.result()
+
+    def __iter__(self):
+        for batch in cut_batches(self._decoded(), self.batch_size, lambda it: it[1][0].shape[:2]):
+            decoded = [d for _, d in batch]
+            images, labels = self.collate(decoded, [i for i, _ in batch])
+            metas = [{"name": self.dataset.files[i]["name"], "size": tuple(int(v) for v in d[0].shape[:2])}
+                     for i, d in batch]
+            yield images, labels, metas

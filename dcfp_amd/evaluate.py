@@ -1,7 +1,7 @@
-"""Evaluation helpers — the device-side half of evaluate.py:113-117,145-247,340-380: whole-image, sliding-window and
+"""Evaluation helpers — the device-side half of evaluate.py:113-143,145-247,340-380: whole-image, sliding-window and
 multi-scale(+flip) prediction, on-device argmax and confusion matrix, mIoU.  Inference runs the
 conv kernels with the eval-mode BatchNorm folded into their epilogues (one kernel per
-conv+BN+ReLU); `predict_labels` never materialises the full-resolution logits."""
+conv+BN+ReLU); `predict_labels` and `predict_vote` never materialise the full-resolution logits."""
 from math import ceil
 
 import torch
@@ -82,6 +82,65 @@ def predict_multiscale(net, image, tile_size, scales, classes, flip_evaluation, 
         full += ops.upsample_bilinear(probs, (H_, W_), align_corner)
     full /= len(scales)
     return full
+
+
+@torch.no_grad()
+def predict_vote(net, image, scales, flip, align_corner, out_hw=None, labels=None, conf=None, want_scores=False,
+                 ignore_index=255):
+    """predict_multiscale(whole=True) + argmax (+ confusion matrix) without any N x C x hs x ws tensor: per scale the
+    network's low-resolution logits of the resized image (and of its mirror image with `flip`), then ONE
+    ops.multiscale_vote launch over all of them.  out_hw: the top-left crop of the image that is
+    predicted (the unpadded size after pad_inf), default the whole image; labels int64 [N,out_h,out_w] with conf
+    int64 [C,C]: counted into conf in the same launch.  -> (pred int32 [N,out_h,out_w], scores fp32
+    [N,C,out_h,out_w] or None).  net: a Seg_Model or a deploy.Engine."""
+    _exec.require_device(image)
+    H_, W_ = image.shape[2:]
+    maps = []
+    for scale in scales:
+        scale = float(scale)
+        hs, ws = int(H_ * scale), int(W_ * scale)
+        img = ops.upsample_bilinear(image, (hs, ws), align_corner)
+        weight = (0.5 if flip else 1.0) / len(scales)
+        maps.append((net.lowres_logits(img)[0], (hs, ws), False, weight))
+        if flip:
+            maps.append((net.lowres_logits(torch.flip(img, [3]))[0], (hs, ws), True, weight))
+    return ops.multiscale_vote(maps, (H_, W_), (H_, W_) if out_hw is None else out_hw, align_corner, labels=labels,
+                               conf=conf, want_scores=want_scores, ignore_index=ignore_index)
+
+
+def pad_inf_size(h, w, stride=8):
+    """evaluate.py:119-123: the next size of the form stride*k + 1 on both axes."""
+    return h + (stride + 1 - h % stride) % stride, w + (stride + 1 - w % stride) % stride
+
+
+def pad_inf(image):
+    """evaluate.py:119-130: zero padding at the bottom / right up to 8k+1 on both axes."""
+    return pad(image, pad_inf_size(image.shape[2], image.shape[3]))
+
+
+def generate_size(h, w, size, mode):
+    """evaluate.py:132-141: the size an image is resized to so that its long / short side becomes `size`."""
+    if mode == "long":
+        f_scale = size * 1.0 / max(h, w)
+    elif mode == "short":
+        f_scale = size * 1.0 / min(h, w)
+    else:
+        raise NotImplementedError(mode)
+    return int(h * f_scale + 0.5), int(w * f_scale + 0.5)
+
+
+def generate_size_image(image, size, mode):
+    """evaluate.py:132-143 on the device."""
+    return ops.upsample_bilinear(image, generate_size(image.shape[2], image.shape[3], size, mode), False)
+
+
+def save_palette_png(pred, palette, path):
+    """evaluate.py:346-350: a [H,W] class map as an 8-bit palette PNG (palette: flat list of R, G, B)."""
+    from PIL import Image
+    import numpy as np
+    im = Image.fromarray(np.ascontiguousarray(np.asarray(pred, dtype=np.uint8)))
+    im.putpalette([int(v) for v in palette])
+    im.save(path)
 
 
 @torch.no_grad()

@@ -1930,6 +1930,59 @@ def confusion_matrix(pred, gt, num_classes, ignore_index=255, out=None):
     return out
 
 
+VOTE_MAX_MAPS = 16
+
+
+def multiscale_vote(maps, grid_hw, out_hw, align_corners, labels=None, conf=None, want_scores=False, want_pred=True,
+                    ignore_index=255):
+    """The multi-scale + flip vote of evaluate.py:198-227 (whole=True) in one launch (csrc/vote.hip).
+    maps: up to 16 tuples (logits fp32 [N,C,h,w], (hs, ws), flip, weight) - the low-resolution logits of the network
+    on the image resized to hs x ws (mirrored along x when flip); grid_hw: the size (H, W) the reference resizes every
+    pass back to; out_hw: the top-left crop of that grid that is produced.  labels int64 [N,out_h,out_w] and conf int64
+    [C,C] (accumulated, given together) count the confusion matrix in the same launch.  -> (pred int32 [N,out_h,out_w] or None, scores
+    fp32 [N,C,out_h,out_w] or None).  The N x C x hs x ws logits are never formed."""
+    maps = list(maps)
+    if not 1 <= len(maps) <= VOTE_MAX_MAPS:
+        raise RuntimeError("multiscale_vote: 1 .. %d maps expected, got %d" % (VOTE_MAX_MAPS, len(maps)))
+    H, W = int(grid_hw[0]), int(grid_hw[1])
+    oh, ow = int(out_hw[0]), int(out_hw[1])
+    first = maps[0][0]
+    _require(first, "logits")
+    if first.dim() != 4:
+        raise RuntimeError("multiscale_vote: logits [N,C,h,w] expected")
+    dev, (N, Cc) = first.device, first.shape[:2]
+    if not (0 < oh <= H and 0 < ow <= W):
+        raise RuntimeError("multiscale_vote: the output %dx%d must be a crop of the grid %dx%d" % (oh, ow, H, W))
+    recs, keep = (_lib.VoteMap * len(maps))(), []
+    for i, (logits, (hs, ws), flip, weight) in enumerate(maps):
+        _require(logits, "logits")
+        if logits.dim() != 4 or tuple(logits.shape[:2]) != (N, Cc) or logits.device != dev:
+            raise RuntimeError("multiscale_vote: every map holds [N,C,h,w] logits of one batch on one device")
+        logits = logits.contiguous()
+        keep.append(logits)
+        recs[i] = _lib.VoteMap(logits.data_ptr(), logits.shape[2], logits.shape[3], int(hs), int(ws), int(bool(flip)),
+                               float(weight))
+    if (conf is None) != (labels is None):
+        raise RuntimeError("multiscale_vote: labels and the confusion matrix come together")
+    if labels is not None:
+        if not (isinstance(labels, torch.Tensor) and labels.is_cuda and labels.device == dev and
+                labels.dtype == torch.int64 and tuple(labels.shape) == (N, oh, ow) and labels.is_contiguous()):
+            raise RuntimeError("multiscale_vote: dense int64 [N,out_h,out_w] device labels expected")
+        if not (isinstance(conf, torch.Tensor) and conf.is_cuda and conf.device == dev and conf.dtype == torch.int64 and
+                tuple(conf.shape) == (Cc, Cc) and conf.is_contiguous()):
+            raise RuntimeError("multiscale_vote: conf must be a contiguous int64 [C,C] device tensor")
+    if not (want_scores or want_pred or labels is not None):
+        raise RuntimeError("multiscale_vote: nothing asked for")
+    scores = torch.empty((N, Cc, oh, ow), dtype=torch.float32, device=dev) if want_scores else None
+    pred = torch.empty((N, oh, ow), dtype=torch.int32, device=dev) if want_pred else None
+    with torch.cuda.device(dev):
+        check(_lib.lib().dcfp_vote_multiscale_f32(recs, len(maps), N, Cc, H, W, oh, ow, int(bool(align_corners)),
+                                                  _p(scores), _p(pred), _p(labels), int(ignore_index), _p(conf),
+                                                  _stream()),
+              "multiscale_vote")
+    return pred, scores
+
+
 def label_boundary(labels, num_classes, d, background=255):
     """The label map with everything but the class boundaries set to `background`: a pixel with
     0 <= label < num_classes keeps its label unless the whole (2d+1)x(2d+1) window centred on it lies inside the

@@ -490,6 +490,35 @@ int dcfp_confusion_matrix_i64(const int32_t* pred, const int64_t* gt, int ignore
                               int64_t n_pixels, int C, int64_t* conf /* [C*C], accumulated */,
                               dcfp_stream_t stream);
 
+/* The multi-scale + flip vote of evaluate.py:198-227 with whole=True, fused with the argmax and the confusion matrix
+ * above into one launch (vote.hip).  Every map is the network's low-resolution logits of one (scale, flip)
+ * pass.  For y < out_h, x < out_w:
+ *   score[n,c,y,x] = sum_k weight_k * sum_{(Y,wY) in lerp(y: hs_k -> H)} sum_{(X,wX) in lerp(x: ws_k -> W)}
+ *                    wY * wX * U_k(c, Y, flip_k ? ws_k-1-X : X)
+ * where U_k(c, Y, X') is the bilinear value of logits_k[n,c] resized from (h_k, w_k) to (hs_k, ws_k) at (Y, X'); all
+ * four index computations follow the coordinate rule of the upsample kernels.  pred = the first maximum of score over
+ * c; conf[gt*C + pred] += 1 where gt != ignore_index and 0 <= gt < C (C <= 1024 with conf).  scores
+ * [N,C,out_h,out_w], pred [N,out_h,out_w] and conf [C*C] (accumulated; needs gt [N,out_h,out_w]) are optional, at
+ * least one of them is asked for.  The N x C x hs x ws logits never exist.  No float atomics, a fixed summation
+ * order: two calls give the same bits.  `maps` is a HOST array of n_maps <= 16 records (logits: device pointer),
+ * validated here before the launch (DCFP_E_BADDESC) and passed by value. */
+typedef struct DcfpVoteMap {
+    const float* logits;   /* [N, C, h, w] dense fp32: net.lowres_logits of the resized (and maybe mirrored) image */
+    int h, w;              /* its size */
+    int hs, ws;            /* size of the image the network saw = size its logits are upsampled to */
+    int flip;              /* 1: the network saw the image mirrored along x */
+    float weight;          /* 1/len(scales), or 0.5/len(scales) for each map of a flip pair */
+} DcfpVoteMap;
+int dcfp_vote_multiscale_f32(const DcfpVoteMap* maps, int n_maps, int N, int C,
+                             int H, int W,          /* the grid the reference votes on (image size after pad_inf) */
+                             int out_h, int out_w,  /* top-left crop that is produced, <= H, W */
+                             int align_corners,
+                             float* scores,         /* optional [N, C, out_h, out_w] */
+                             int32_t* pred,         /* optional [N, out_h, out_w] */
+                             const int64_t* gt, int ignore_index,   /* optional [N, out_h, out_w] */
+                             int64_t* conf,         /* optional [C*C], accumulated; needs gt */
+                             dcfp_stream_t stream);
+
 /* Boundary IoU (evaluate.py:352-357, utils/edge_utils.py:98-127): the label map with everything but the class
  * boundaries set to `background`.  A pixel is valid if 0 <= label < num_classes; a valid pixel is interior if
  * the whole (2d+1)x(2d+1) window centred on it lies inside the image and carries its label;

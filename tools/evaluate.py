@@ -1,9 +1,16 @@
 #!/usr/bin/env python
-"""Evaluation driver — the command line and protocol of the reference's evaluate.py main() (evaluate.py:249-393) over
-SYNTHETIC data: build the (optionally slimmed, optionally frozen-to-fp16) model, predict batch by batch, accumulate the
-confusion matrix on the device, print {'meanIU', 'IU_array'} and append IoU / precision / recall / FPS to result.txt in
-the snapshot directory.  `--iou-type boundary` scores class boundaries only.  Datasets, PNG output,
---longsize/--shortsize and multi-rank evaluation are not part of it."""
+"""Evaluation driver — the command line and protocol of the reference's evaluate.py main() (evaluate.py:249-393): build
+the (optionally slimmed, optionally frozen-to-fp16) model, predict batch by batch, accumulate the confusion matrix on
+the device, print {'meanIU', 'IU_array'} and append IoU / precision / recall / FPS to result.txt in the snapshot
+directory.  `--iou-type boundary` scores class boundaries only.
+
+Without `--dataset` the data are SYNTHETIC (seeded rectangles).  With `--dataset CS --data-para '{"root": ...,
+"list_path": ...}'` the validation list is read through datasets.EvalLoader: --longsize / --shortsize, the 8k+1 padding
+of `--whole True --align-corner True`, palette PNGs with `--save-predict True`, and one process per GPU under
+torchrun (`--ddp`, every file counted exactly once, the matrix summed over the ranks).  `--whole True` with more than
+one scale or with --flip then runs evaluate.predict_vote: prediction, argmax and confusion matrix are one launch after
+the network (`--fused-vote False`: the N x C x H x W path, for A/B).  The test-split submission of evaluate_test.py
+and the CTX / ADE / COCO datasets are not part of it."""
 import argparse
 import json
 import os
@@ -50,6 +57,18 @@ def get_parser():
     p.add_argument("--num-images", type=int, default=40)
     p.add_argument("--seed", type=int, default=12345)
     p.add_argument("--snapshot-dir", type=str, default="ckpt")
+    p.add_argument("--dataset", type=str, default=None, help="choose dataset (default: synthetic data)")
+    p.add_argument("--data-dir", type=str, default="val", help="choose data type.")
+    p.add_argument("--data-para", type=str, default="{}", help='JSON: {"root": ..., "list_path": ...}')
+    p.add_argument("--num-workers", type=int, default=8)
+    p.add_argument("--longsize", type=int, default=-1)
+    p.add_argument("--shortsize", type=int, default=-1)
+    p.add_argument("--save-predict", type=str2bool, default="False", help="save predict images")
+    p.add_argument("--ddp", type=str2bool, default="True")
+    p.add_argument("--dist-backend", type=str, default=None, help="default: the engine's choice (nccl on a GPU)")
+    p.add_argument("--fused-vote", type=str2bool, default=None,
+                   help="multi-scale / flip whole-image prediction through evaluate.predict_vote "
+                        "(default: True with --dataset, False without)")
     return p
 
 
@@ -98,7 +117,10 @@ def build_model(args):
 
 
 def main(argv=None):
-    args = get_parser().parse_args(argv)
+    parser = get_parser()
+    if parser.parse_known_args(argv)[0].dataset is not None:
+        return main_dataset(parser, argv)
+    args = parser.parse_args(argv)
     h, w = map(int, args.input_size.split(","))
     scales = [float(s) for s in args.ms.split(",")]
     C = args.num_classes
@@ -120,6 +142,8 @@ def main(argv=None):
             start_time = time.perf_counter()
             if args.whole and scales == [1.0]:
                 pred = ev.predict_labels(model, image)
+            elif args.whole and args.fused_vote:
+                pred, _ = ev.predict_vote(model, image, scales, args.flip, args.align_corner)
             else:
                 output = ev.predict_multiscale(model, image, (h, w), scales, C, args.flip, args.align_corner, args.whole)
                 pred = ops.upsample_argmax(output, (h, w), True)      # same size, corners aligned: the plain argmax
@@ -140,6 +164,12 @@ def main(argv=None):
             print_str += f" FPS: {fps:.2f} img / s, metric {metric * 1e3:.3f} ms"
         print(print_str, flush=True)
 
+    return report(args, conf, C, fps, timed_images, metric_time * 1e3 / max(1, nbatches - warmup))
+
+
+def report(args, conf, C, fps, timed_images, metric_ms_per_batch):
+    """Metrics of the accumulated matrix: printed, and appended to result.txt in the snapshot directory."""
+    boundary = args.iou_type == "boundary"
     if boundary:
         mean_IU, IU_array = ev.boundary_iou(conf)
     else:
@@ -156,11 +186,108 @@ def main(argv=None):
         f.write(json.dumps({"meanP": p.mean().item(), "p": p.tolist()}) + "\n")
         f.write(json.dumps({"meanR": r.mean().item(), "r": r.tolist()}) + "\n")
         f.write(json.dumps({"FPS": fps, "iou_type": args.iou_type, "images": timed_images,
-                            "metric_ms_per_batch": metric_time * 1e3 / max(1, nbatches - warmup),
+                            "metric_ms_per_batch": metric_ms_per_batch,
                             "tp": tp.tolist(), "pos": pos.tolist(), "res": res.tolist()}) + "\n")
         f.write("--------\n")
     return mean_IU
 
+
+def main_dataset(parser, argv=None):
+    """The reference's protocol on a dataset's validation list (module docstring)."""
+    import torch.distributed as dist
+    from dcfp_amd.datasets import EvalLoader, build_dataset
+    from dcfp_amd.engine import Engine
+    if argv is not None:
+        sys.argv = [sys.argv[0]] + list(argv)            # the engine reads --ddp / --local_rank from the command line
+    backend = parser.parse_known_args(argv)[0].dist_backend
+    with Engine(custom_parser=parser, backend=backend) as engine:
+        args = parser.parse_args(argv)
+        h, w = map(int, args.input_size.split(","))
+        scales = [float(s) for s in args.ms.split(",")]
+        fused = True if args.fused_vote is None else args.fused_vote
+        rank, world = (dist.get_rank(), engine.world_size) if engine.distributed else (0, 1)
+        device = torch.device("cuda", engine.local_rank if engine.distributed else 0)
+        torch.cuda.set_device(device)
+        torch.manual_seed(args.seed)
+        dataset = build_dataset(args.dataset, split="val", data_dir=args.data_dir, ignore_label=args.ignore_label,
+                                data_para=json.loads(args.data_para))
+        C = args.num_classes = dataset.num_classes
+        loader = EvalLoader(dataset, max(1, args.batch_size // world), device, num_workers=args.num_workers,
+                            rank=rank, world_size=world)
+        model = build_model(args)
+        model = deploy.build_engine(model).to(device) if args.use_trt else model.to(device)
+        palette = [int(v) for v in dataset.cmap_labels.reshape(-1)]
+        save_path = os.path.join(args.snapshot_dir, "outputs")
+        if args.save_predict:
+            os.makedirs(save_path, exist_ok=True)
+        boundary = args.iou_type == "boundary"
+        resized = args.longsize > 0 or args.shortsize > 0
+        conf = torch.zeros((C, C + 1 if boundary else C), dtype=torch.int64, device=device)
+        nbatches = len(loader)
+        warmup = min(FPS_WARMUP, nbatches - 1)
+        pure_inf_time, metric_time, timed_images, timed_batches, fps = 0.0, 0.0, 0, 0, 0.0
+        for idx, (image, label, metas) in enumerate(loader):
+            size = metas[0]["size"]
+            with torch.no_grad():
+                if args.longsize > 0:
+                    image = ev.generate_size_image(image, args.longsize, "long")
+                elif args.shortsize > 0:
+                    image = ev.generate_size_image(image, args.shortsize, "short")
+                size_scale = tuple(image.shape[2:])
+                if args.whole and args.align_corner:
+                    image = ev.pad_inf(image)
+                torch.cuda.synchronize()
+                start_time = time.perf_counter()
+                counted = False
+                if args.whole and scales == [1.0] and not args.flip and not resized:
+                    pred = ev.predict_labels(model, image)[:, :size_scale[0], :size_scale[1]].contiguous()
+                elif args.whole and fused:
+                    counted = not resized and not boundary        # prediction, argmax and confusion: one launch
+                    pred, scores = ev.predict_vote(model, image, scales, args.flip, args.align_corner, out_hw=size_scale,
+                                                   labels=label if counted else None, conf=conf if counted else None,
+                                                   want_scores=resized, ignore_index=args.ignore_label)
+                    if resized:
+                        pred = ops.upsample_argmax(scores, size, False)
+                else:
+                    output = ev.predict_multiscale(model, image, (h, w), scales, C, args.flip, args.align_corner,
+                                                   args.whole)
+                    output = output[:, :, :size_scale[0], :size_scale[1]].contiguous()
+                    pred = ops.upsample_argmax(output, size, not resized)   # same size, corners aligned: the plain argmax
+                torch.cuda.synchronize()
+                elapsed = time.perf_counter() - start_time
+                if boundary:
+                    ev.boundary_confusion_matrix(label, pred, C, args.dilation_ratio, args.ignore_label, out=conf)
+                elif not counted:
+                    ev.get_confusion_matrix(label, pred, C, args.ignore_label, out=conf)
+                torch.cuda.synchronize()
+                metric = time.perf_counter() - start_time - elapsed
+            if args.save_predict:
+                for i, meta in enumerate(metas):
+                    ev.save_palette_png(pred[i].cpu().numpy(), palette, os.path.join(save_path, meta["name"] + ".png"))
+            print_str = " Iter%d/%d" % (idx + 1, nbatches)
+            if idx >= warmup:
+                pure_inf_time += elapsed
+                metric_time += metric
+                timed_images += image.shape[0]
+                timed_batches += 1
+                fps = timed_images / pure_inf_time
+                print_str += f" FPS: {fps:.2f} img / s, metric {metric * 1e3:.3f} ms"
+            if rank == 0:
+                print(print_str, flush=True)
+        if engine.distributed:
+            if dist.get_backend() == "gloo":                      # gloo reduces on the host
+                total = conf.cpu()
+                dist.all_reduce(total)
+                conf = total.to(device)
+            else:
+                dist.all_reduce(conf)
+            torch.cuda.synchronize()
+            dist.destroy_process_group()
+        if rank != 0:
+            return None
+        cm = conf[:, :C]
+        print(json.dumps({"tp": int(cm.diag().sum()), "pos": int(conf.sum()), "res": int(cm.sum())}))
+        return report(args, conf, C, fps, timed_images, metric_time * 1e3 / max(1, timed_batches))
 
 if __name__ == "__main__":
     main()
