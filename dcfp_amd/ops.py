@@ -951,6 +951,10 @@ def bn_backward_impl(dy, x, y, gamma, beta, state, relu, training, eps, want_res
     otherwise the mask is re-derived from x inside the kernels (pass y=None).  between: optional callable
     run after the reduction (and the start of the SyncBN exchange) and before dx - independent work
     that hides the exchange."""
+    if relu and len(state) > 4 and state[4] is not None and not dy.is_contiguous():
+        # the kernels that take the ReLU mask as bits want dy dense over the batch too (DCFP_E_UNSUPPORTED otherwise): a
+        # gradient that arrives as a channel-slice view - the backward of a cat or a narrow behind the block - is copied once
+        dy = dy.contiguous()
     if BN_BWD_FUSED and training and pre is None and state[3] is None and not isinstance(state[2], torch.Tensor):
         # no exchange between the two stages: one launch, dy and x read once
         frelu, fy, gp, tg, kg, bp, tb, kb = _bn_bwd_preface(relu, y, state, gamma, beta, gparam, bparam)
