@@ -60,10 +60,14 @@ class FusedSGD(torch.optim.Optimizer):
         if self._arena is None or not self._arena.covers(params):
             self._arena = ParamArena.of(params)
             self._tables = {}
+            reused = self._arena.flat_mom is not None       # an arena found again (load_state_dict) holds old momentum
             for i, p in enumerate(self._arena.params):      # momentum restored before the arena existed
                 old = self.state[p].get("momentum_buffer") if p in self.state else None
                 view = self._arena.momentum_view(i)
-                if old is not None and old.data_ptr() != view.data_ptr():
+                if old is None:
+                    if reused:       # no loaded state for this parameter: it starts from zero, as torch.optim.SGD's would
+                        view.zero_()
+                elif old.data_ptr() != view.data_ptr():
                     view.copy_(old)
                 self.state[p]["momentum_buffer"] = view
         return self._arena
