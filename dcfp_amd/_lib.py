@@ -41,6 +41,12 @@ class SgdEntry(C.Structure):
                 ("weight_decay", C.c_float), ("pad_", C.c_int32)]
 
 
+class AdamEntry(C.Structure):
+    """DcfpAdamEntry: one tensor of a multi-tensor AdamW launch."""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("n", C.c_int64), ("first_chunk", C.c_int64)]
+
+
 class BnRunning(C.Structure):
     """DcfpBnRunning: nn.BatchNorm2d's training-mode bookkeeping folded into the statistics kernels."""
     _fields_ = [("running_mean", C.c_void_p), ("running_var", C.c_void_p), ("num_batches_tracked", C.c_void_p),
@@ -174,6 +180,7 @@ SIGNATURES = {
     "dcfp_component_pixel_i32": (_I, [C.POINTER(CcSample), _I, _P, _Z, _P, _P, _P, _P, _P]),
     "dcfp_eic_update_f32": (_I, [_P, _I, _F, _F, _P]),
     "dcfp_sgd_momentum_f32": (_I, [_P, _I, _L, _F, _F, _I, _P]),
+    "dcfp_adamw_f32": (_I, [_P, _I, _L, _F, _F, _F, _F, _F, _F, _F, _P]),
     "dcfp_conv2d_fwd_f16_nhwc": (_I, [_H, _P, _P, _P, _P, _P, _P]),
     "dcfp_conv2d_fwd_f16_nhwc_to_f32_nchw": (_I, [_H, _P, _P, _P, _P, _P]),
     "dcfp_maxpool3x3s2_nhwc_f16": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),

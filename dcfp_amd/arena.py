@@ -6,10 +6,11 @@ scored BN's `weight.grad` (pruners/dcfp_pruner.py:15-20) and DDP's bucketed grad
 (engine.py:65-68).  The reference leaves all of that to ~470 separately allocated tensors.
 
 Here every parameter of a model is a VIEW into one flat fp32 buffer, every gradient a view into a
-second one and every momentum buffer a view into a third (65 M floats = 260 MB each for
-DeepLabv3-R101, 256-byte aligned slots).  Consequences:
+second one and every optimizer-state tensor (SGD's momentum buffer; AdamW's exp_avg and exp_avg_sq) a
+view into a named state buffer of its own (65 M floats = 260 MB each for DeepLabv3-R101, 256-byte
+aligned slots).  Consequences:
 
-  * addresses never change, so the pointer tables of the multi-tensor HIP kernels (SGD, EIC) are
+  * addresses never change, so the pointer tables of the multi-tensor HIP kernels (SGD, AdamW, EIC) are
     built ONCE instead of every step (`zero_grad(set_to_none=True)` used to hand out new gradient
     tensors each iteration);
   * the backward kernels (wgrad split-K reduce, BN dgamma/dbeta finalize, bias gradient) write their
@@ -59,7 +60,7 @@ class ParamArena:
         self.total = off
         self.flat_param = torch.zeros(off, dtype=torch.float32, device=dev)
         self.flat_grad = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.flat_mom = None
+        self.state_buffers = {}          # name -> flat optimizer-state buffer ("momentum": flat_mom)
         self.grad_views = []
         with torch.no_grad():
             for i, (p, o) in enumerate(zip(params, self.offsets)):
@@ -115,14 +116,31 @@ class ParamArena:
         p = self.params[index]
         return p.data_ptr() == self.flat_param.data_ptr() + 4 * self.offsets[index]
 
+    # ------------------------------------------------------------------ optimizer state
+    def has_state(self, name):
+        return name in self.state_buffers
+
+    def state_buffer(self, name):
+        """The flat optimizer-state buffer `name` (momentum, exp_avg, exp_avg_sq ...): created zeroed on first use,
+        same slot offsets as the parameters."""
+        buf = self.state_buffers.get(name)
+        if buf is None:
+            buf = self.state_buffers[name] = torch.zeros_like(self.flat_param)
+        return buf
+
+    def state_view(self, name, index):
+        o, p = self.offsets[index], self.params[index]
+        return self.state_buffer(name)[o:o + p.numel()].view(p.shape)
+
+    @property
+    def flat_mom(self):
+        return self.state_buffers.get("momentum")
+
     def momentum(self):
-        if self.flat_mom is None:
-            self.flat_mom = torch.zeros_like(self.flat_param)
-        return self.flat_mom
+        return self.state_buffer("momentum")
 
     def momentum_view(self, index):
-        o, p = self.offsets[index], self.params[index]
-        return self.momentum()[o:o + p.numel()].view(p.shape)
+        return self.state_view("momentum", index)
 
     # ------------------------------------------------------------------ gradients
     def zero_grad(self, set_to_none=True):

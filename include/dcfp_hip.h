@@ -654,6 +654,29 @@ typedef struct DcfpSgdEntry {
 int dcfp_sgd_momentum_f32(const DcfpSgdEntry* table, int n_tensors, int64_t total_chunks,
                           float lr, float momentum, int first_step, dcfp_stream_t stream);
 
+/* ------------------------------------------------------------------ AdamW
+ * torch.optim.AdamW step (decoupled weight decay, no amsgrad, no maximize) over a list of tensors that share one
+ * step count, in the order of torch's single-tensor implementation:
+ *   p *= 1 - lr*wd ; m = lerp(m, g, 1-beta1) ; v = beta2*v + (1-beta2)*g*g ;
+ *   denom = sqrt(v)/bias_correction2_sqrt + eps ; p -= (lr/bias_correction1) * m/denom
+ * One launch over the device table, one block per DCFP_SGD_CHUNK elements of one tensor.  1 - lr*wd, lr/bc1,
+ * 1 - beta1 and 1 - beta2 are formed in double here and rounded once; every scalar is passed by value, so a
+ * learning rate or weight decay that changes every step needs no new table.  Entries whose four pointers are all
+ * 16-byte aligned take 16-byte loads and stores, the others (and the last n % 4 elements) a scalar path with the
+ * same bits per element.  grad is only read; nothing is written past n.  DCFP_E_BADDESC: negative counts,
+ * total_chunks > 2^31-1, null table; n_tensors == 0 or total_chunks == 0: DCFP_OK, no launch. */
+typedef struct DcfpAdamEntry {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    int64_t n;
+    int64_t first_chunk; /* prefix sum of ceil(n / DCFP_SGD_CHUNK) over earlier entries */
+} DcfpAdamEntry;
+int dcfp_adamw_f32(const DcfpAdamEntry* table, int n_tensors, int64_t total_chunks,
+                   float lr, float beta1, float beta2, float eps, float weight_decay,
+                   float bias_correction1, float bias_correction2_sqrt, dcfp_stream_t stream);
+
 /* ------------------------------------------------- fp16 deployment engine
  * The frozen half-precision inference path (dcfp_amd/deploy.py; the reference's totrt.py stage).  Activations are
  * NHWC fp16 with a channel pitch that is a multiple of 8; weights are packed once as [Cout8][KH][KW][Cin8] fp16 with
