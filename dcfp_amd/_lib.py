@@ -159,6 +159,8 @@ SIGNATURES = {
     "dcfp_upsample_ce_fwd_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P,
                                       _Z, _P]),
     "dcfp_upsample_ce_bwd_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "dcfp_upsample_ce_bwd_plan": (_I, [_I, _I, _I, _I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                       C.POINTER(C.c_int)]),
     "dcfp_ohem_zoom_gt_prob_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "dcfp_ohem_threshold_f32": (_I, [_P, _P, _L, _I, _F, _L, _P, _P]),
     "dcfp_ohem_keep_mask_u8": (_I, [_P, _P, _L, _P, _P]),

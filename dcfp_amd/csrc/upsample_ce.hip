@@ -402,6 +402,164 @@ upsample_ce_bwd_cells_kernel(const float* __restrict__ logits, const long long* 
     }
 }
 
+// The cell kernel for any class count (Pascal-Context 59, ADE 150, COCO-Stuff 171): once the per-pixel LSE is
+// known the softmax factorises over classes, so a workgroup runs the cell kernel's arithmetic on a class WINDOW
+// [c0, c0 + CT) of the C-class tensor, c0 = chunk * CT.  The class-independent work of a destination pixel (stencils,
+// label, LSE, weight) is repeated ceil(C / CT) times instead of C times, and each class of a pixel is evaluated once
+// instead of four times.  One launch covers every chunk; the chunk index varies fastest, so the blocks that read the
+// same tile's labels, LSE and weights are neighbours in dispatch order.  The tail chunk holds nc = C - c0 < CT real
+// classes: a phantom class is never loaded, never evaluated (no expf term exists for it) and never stored.  Full
+// chunks run the body without any of those guards (TAIL = false); the branch between the two is block-uniform.
+// Summation order per output: the 19-class kernel's (even rows + odd rows per cell, then the <= 4 (cell, corner)
+// terms in a fixed order) - no atomics, run-to-run bit-identical, and a chunk's result does not depend on any other
+// chunk's logits.  The 19-class instantiation above is left as it is: its code object is the training path's.
+//
+// Budget at CT = 20: 8 x 20 corner / accumulator registers per lane (the 19-class kernel: 8 x 19, 219 VGPRs of the
+// 256 that two workgroups of four waves per CU leave each lane), LDS 128 x 4 x 21 x 4 B = 43 KB per workgroup.
+#ifndef DCFP_CE_CHUNK
+#define DCFP_CE_CHUNK 20          // the chunk width; the candidates' times are in DESIGN §13a
+#endif
+constexpr int kCeChunk = DCFP_CE_CHUNK;
+constexpr int kCeChunkMinC = 2;   // the smallest class count timed; faster than the per-output kernels from there on
+                                  // (DESIGN §13a).  C == 1 (gradient identically zero) stays where it was
+
+template <bool ALIGN, int CT, bool TAIL>
+__device__ __forceinline__ void ce_bwd_cells_chunk_body(
+    float (*corner)[4][CT + 1], const float* __restrict__ base /* logits of (n, c0) */,
+    const long long* __restrict__ lab, const uint8_t* __restrict__ kp, const float* __restrict__ wp,
+    const float* __restrict__ ls, int ignore_index, int c0, int nc, int h, int w, int H, int W, float sh, float sw,
+    float gs, float* __restrict__ out /* dlogits of (n, c0) */, int I0, int J0) {
+    const int tid = threadIdx.x;
+    const long long plane = (long long)h * w;
+    const int cell = tid >> 1, part = tid & 1;
+    if (cell < kCellCount) {
+        const int ci = I0 - 1 + cell / (kCellTW + 1), cj = J0 - 1 + cell % (kCellTW + 1);
+        float a00[CT], a01[CT], a10[CT], a11[CT];
+#pragma unroll
+        for (int c = 0; c < CT; ++c) a00[c] = a01[c] = a10[c] = a11[c] = 0.f;
+        if (ci >= 0 && ci < h && cj >= 0 && cj < w) {
+            const int i1 = ci + (ci < h - 1 ? 1 : 0), j1 = cj + (cj < w - 1 ? 1 : 0);
+            float p00[CT], p01[CT], p10[CT], p11[CT];
+#pragma unroll
+            for (int c = 0; c < CT; ++c) {
+                p00[c] = p01[c] = p10[c] = p11[c] = 0.f;
+                if (TAIL && c >= nc) continue;
+                const float* p = base + c * plane;
+                p00[c] = p[ci * w + cj]; p01[c] = p[ci * w + j1];
+                p10[c] = p[i1 * w + cj]; p11[c] = p[i1 * w + j1];
+            }
+            int ylo, yhi, xlo, xhi;
+            dst_range<ALIGN>(ci, sh, H, ylo, yhi);
+            dst_range<ALIGN>(cj, sw, W, xlo, xhi);
+            for (int Y = ylo + part; Y <= yhi; Y += 2) {
+                const Lerp Lh = lerp_of<ALIGN>(Y, sh, h);
+                if (Lh.i0 != ci) continue;
+                for (int X = xlo; X <= xhi; ++X) {
+                    const Lerp Lw = lerp_of<ALIGN>(X, sw, w);
+                    if (Lw.i0 != cj) continue;
+                    const long long q = (long long)Y * W + X;
+                    const long long label = lab[q];
+                    if (label == ignore_index || (kp && !kp[q])) continue;
+                    float pw = 1.f;
+                    if (wp) {
+                        pw = wp[q];
+                        if (pw == 0.f) continue;
+                    }
+                    const float lq = ls[q];
+                    const long long lrel = label - c0;      // the label's position in this window, if it is in it
+                    const float w00 = Lh.l0 * Lw.l0 * pw, w01 = Lh.l0 * Lw.l1 * pw;
+                    const float w10 = Lh.l1 * Lw.l0 * pw, w11 = Lh.l1 * Lw.l1 * pw;
+#pragma unroll
+                    for (int c = 0; c < CT; ++c) {
+                        if (TAIL && c >= nc) continue;
+                        const float z = Lh.l0 * (Lw.l0 * p00[c] + Lw.l1 * p01[c]) +
+                                        Lh.l1 * (Lw.l0 * p10[c] + Lw.l1 * p11[c]);
+                        const float g = expf(z - lq) - (lrel == c ? 1.f : 0.f);
+                        a00[c] += w00 * g; a01[c] += w01 * g;
+                        a10[c] += w10 * g; a11[c] += w11 * g;
+                    }
+                }
+            }
+        }
+        // the two lanes of a cell: even rows + odd rows, always in that order
+#pragma unroll
+        for (int c = 0; c < CT; ++c) {
+            a00[c] += __shfl_xor(a00[c], 1, 64); a01[c] += __shfl_xor(a01[c], 1, 64);
+            a10[c] += __shfl_xor(a10[c], 1, 64); a11[c] += __shfl_xor(a11[c], 1, 64);
+        }
+        if (part == 0) {
+#pragma unroll
+            for (int c = 0; c < CT; ++c) {
+                corner[cell][0][c] = a00[c]; corner[cell][1][c] = a01[c];
+                corner[cell][2][c] = a10[c]; corner[cell][3][c] = a11[c];
+            }
+        }
+    }
+    __syncthreads();
+    // gather, as in the 19-class kernel, over the nc real classes of the window
+    for (int o = tid; o < kCellTH * kCellTW * nc; o += kCellThreads) {
+        const int c = o / (kCellTH * kCellTW);
+        const int r = o - c * (kCellTH * kCellTW);
+        const int li = r / kCellTW, lj = r - li * kCellTW;
+        const int i = I0 + li, j = J0 + lj;
+        if (i >= h || j >= w) continue;
+        float acc = 0.f;
+#pragma unroll
+        for (int di = 0; di < 2; ++di) {
+            const int ci = i - 1 + di;
+            if (ci < 0) continue;
+#pragma unroll
+            for (int a = 0; a < 2; ++a) {
+                if (ci + ((a && ci < h - 1) ? 1 : 0) != i) continue;
+#pragma unroll
+                for (int dj = 0; dj < 2; ++dj) {
+                    const int cj = j - 1 + dj;
+                    if (cj < 0) continue;
+#pragma unroll
+                    for (int bb = 0; bb < 2; ++bb) {
+                        if (cj + ((bb && cj < w - 1) ? 1 : 0) != j) continue;
+                        acc += corner[(li + di) * (kCellTW + 1) + (lj + dj)][a * 2 + bb][c];
+                    }
+                }
+            }
+        }
+        out[c * plane + (long long)i * w + j] = acc * gs;
+    }
+}
+
+template <bool ALIGN, int CT>
+__global__ void __launch_bounds__(kCellThreads, 2)
+upsample_ce_bwd_cells_chunk_kernel(const float* __restrict__ logits, const long long* __restrict__ labels,
+                                   const uint8_t* __restrict__ keep, int ignore_index, int N, int C, int h, int w,
+                                   int H, int W, float sh, float sw, const float* __restrict__ lse,
+                                   const float* __restrict__ grad_scale, float* __restrict__ dlogits,
+                                   const float* __restrict__ pix_weight, int scale_per_image, int tiles_w,
+                                   int tiles_h, int chunks) {
+    __shared__ float corner[kCellCount][4][CT + 1];
+    int b = blockIdx.x;
+    const int chunk = b % chunks;
+    b /= chunks;
+    const int tw = b % tiles_w;
+    b /= tiles_w;
+    const int th = b % tiles_h;
+    const int n = b / tiles_h;
+    const int c0 = chunk * CT;
+    const int nc = C - c0 < CT ? C - c0 : CT;
+    const long long plane = (long long)h * w;
+    const long long img = (long long)n * H * W;
+    const float* base = logits + ((long long)n * C + c0) * plane;     // batch stride C * plane, not CT * plane
+    float* out = dlogits + ((long long)n * C + c0) * plane;
+    const uint8_t* kp = keep ? keep + img : nullptr;
+    const float* wp = pix_weight ? pix_weight + img : nullptr;
+    const float gs = grad_scale[scale_per_image ? n : 0];
+    if (nc == CT)
+        ce_bwd_cells_chunk_body<ALIGN, CT, false>(corner, base, labels + img, kp, wp, lse + img, ignore_index, c0, nc,
+                                                  h, w, H, W, sh, sw, gs, out, th * kCellTH, tw * kCellTW);
+    else
+        ce_bwd_cells_chunk_body<ALIGN, CT, true>(corner, base, labels + img, kp, wp, lse + img, ignore_index, c0, nc,
+                                                 h, w, H, W, sh, sw, gs, out, th * kCellTH, tw * kCellTW);
+}
+
 // OHEM threshold search input (loss/ohem.py:20-33): the reference zooms the full-resolution
 // softmax to 1/factor with scipy.ndimage.zoom(order=1) and the labels with order=0, then
 // gathers the zoomed probability of the zoomed label.  Per zoomed position that is a bilinear
@@ -765,6 +923,45 @@ static void launch_ce_bwd_19(const float* logits, const long long* lab, const ui
                        keep, ignore_index, N, h, w, H, W, sh, sw, lse, gscale, dlogits, pix_weight, per_image);
 }
 
+// Which backward kernel a shape gets: the one decision both launchers and dcfp_upsample_ce_bwd_plan make.
+enum { kCePlanCells19 = 0, kCePlanCellsChunked = 1, kCePlanPerOutput = 2 };
+struct CeBwdPlan { int variant, chunk_width, chunks; };
+
+static CeBwdPlan ce_bwd_plan(int N, int C, int h, int w) {
+    static const bool cells = [] { const char* e = getenv("DCFP_CE_BWD_CELLS"); return !e || atoi(e) != 0; }();
+    const long long tiles = (long long)N * ((h + kCellTH - 1) / kCellTH) * ((w + kCellTW - 1) / kCellTW);
+    if (C == 19)   // launch_ce_bwd_19 (the 32-bit block count holds whenever the entry points' own check does)
+        return cells ? CeBwdPlan{kCePlanCells19, 19, 1} : CeBwdPlan{kCePlanPerOutput, 0, 0};
+    const int chunks = (C + kCeChunk - 1) / kCeChunk;
+    if (cells && C >= kCeChunkMinC && tiles * chunks <= 0x7fffffffLL)
+        return CeBwdPlan{kCePlanCellsChunked, kCeChunk, chunks};
+    return CeBwdPlan{kCePlanPerOutput, 0, 0};
+}
+
+template <bool ALIGN>
+static void launch_ce_bwd_chunked(const CeBwdPlan& plan, const float* logits, const long long* lab,
+                                  const uint8_t* keep, int ignore_index, int N, int C, int h, int w, int H, int W,
+                                  float sh, float sw, const float* lse, const float* gscale, float* dlogits,
+                                  const float* pix_weight, int per_image, hipStream_t st) {
+    const int tiles_w = (w + kCellTW - 1) / kCellTW, tiles_h = (h + kCellTH - 1) / kCellTH;
+    hipLaunchKernelGGL((upsample_ce_bwd_cells_chunk_kernel<ALIGN, kCeChunk>),
+                       dim3((unsigned)((long long)N * tiles_h * tiles_w * plan.chunks)), dim3(kCellThreads), 0, st,
+                       logits, lab, keep, ignore_index, N, C, h, w, H, W, sh, sw, lse, gscale, dlogits, pix_weight,
+                       per_image, tiles_w, tiles_h, plan.chunks);
+}
+
+extern "C" int dcfp_upsample_ce_bwd_plan(int N, int C, int h, int w, int H, int W, int* variant, int* chunk_width,
+                                         int* chunks) {
+    if (!variant || !chunk_width || !chunks || N <= 0 || C <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0)
+        return DCFP_E_BADDESC;
+    if (((long long)N * C * h * w + kThreads - 1) / kThreads > 0x7fffffffLL) return DCFP_E_UNSUPPORTED;
+    const CeBwdPlan plan = ce_bwd_plan(N, C, h, w);
+    *variant = plan.variant;
+    *chunk_width = plan.chunk_width;
+    *chunks = plan.chunks;
+    return DCFP_OK;
+}
+
 extern "C" int dcfp_upsample_ce_bwd_f32(const float* logits, const int64_t* labels,
                                         const uint8_t* pixel_keep, int ignore_index, int N, int C,
                                         int h, int w, int H, int W, int align_corners,
@@ -786,6 +983,16 @@ extern "C" int dcfp_upsample_ce_bwd_f32(const float* logits, const int64_t* labe
         else
             launch_ce_bwd_19<false>(logits, lab, pixel_keep, ignore_index, N, h, w, H, W, sh, sw, lse, grad_scale,
                                     dlogits, nullptr, 0, dcfp_s(stream));
+        DCFP_RETURN_LAUNCH();
+    }
+    const CeBwdPlan plan = ce_bwd_plan(N, C, h, w);
+    if (plan.variant == kCePlanCellsChunked) {   // every other class count: the cell kernel per class chunk
+        if (align_corners)
+            launch_ce_bwd_chunked<true>(plan, logits, lab, pixel_keep, ignore_index, N, C, h, w, H, W, sh, sw, lse,
+                                        grad_scale, dlogits, nullptr, 0, dcfp_s(stream));
+        else
+            launch_ce_bwd_chunked<false>(plan, logits, lab, pixel_keep, ignore_index, N, C, h, w, H, W, sh, sw, lse,
+                                         grad_scale, dlogits, nullptr, 0, dcfp_s(stream));
         DCFP_RETURN_LAUNCH();
     }
     if (align_corners)
@@ -894,6 +1101,16 @@ extern "C" int dcfp_upsample_wce_bwd_f32(const float* logits, const int64_t* lab
         else
             launch_ce_bwd_19<false>(logits, lab, nullptr, ignore_index, N, h, w, H, W, sh, sw, lse,
                                     grad_scale_per_image, dlogits, pix_weight, 1, dcfp_s(stream));
+        DCFP_RETURN_LAUNCH();
+    }
+    const CeBwdPlan plan = ce_bwd_plan(N, C, h, w);
+    if (plan.variant == kCePlanCellsChunked) {
+        if (align_corners)
+            launch_ce_bwd_chunked<true>(plan, logits, lab, nullptr, ignore_index, N, C, h, w, H, W, sh, sw, lse,
+                                        grad_scale_per_image, dlogits, pix_weight, 1, dcfp_s(stream));
+        else
+            launch_ce_bwd_chunked<false>(plan, logits, lab, nullptr, ignore_index, N, C, h, w, H, W, sh, sw, lse,
+                                         grad_scale_per_image, dlogits, pix_weight, 1, dcfp_s(stream));
         DCFP_RETURN_LAUNCH();
     }
     if (align_corners)

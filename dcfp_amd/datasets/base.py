@@ -249,9 +249,24 @@ def pack_batch(params, src_hws, cfg, mean, std):
             np.concatenate(lbs).astype(np.float32), recs)
 
 
+def bitrev_palette(n, first=1):
+    """uint8 [n, 3] RGB: the bit-reversal colour map of PASCAL VOC tooling, entries first .. first + n - 1.  Bit k of
+    the entry's index (k = 0, 1, 2 in turn, three bits per round) goes to the highest free bit of R, G, B: distinct
+    indices below 256 give distinct colours, and only index 0 is black."""
+    out = np.zeros((n, 3), dtype=np.uint8)
+    for row in range(n):
+        v, bit = row + first, 7
+        while v and bit >= 0:
+            for ch in range(3):
+                out[row, ch] |= ((v >> ch) & 1) << bit
+            v >>= 3
+            bit -= 1
+    return out
+
+
 class BaseDataSet:
     """Configuration and host-side table building of one dataset; subclasses provide `files`, `num_classes`,
-    `class_weights`, `id_to_trainid` and `decode(index)`."""
+    `class_weights` and `id_to_trainid`."""
 
     def __init__(self, split="train", crop_size=(321, 321), mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225),
                  scale=True, mirror=True, brightness=True, ignore_label=255, balance=0, longsize=-1, shortsize=-1,
@@ -343,8 +358,58 @@ class BaseDataSet:
             label_copy[label == k] = np.array(v).astype(label_copy.dtype)
         return label_copy
 
+    def decode(self, index):
+        """-> (uint8 [H,W,3] BGR, uint8 [H,W] raw ids or None): cv2.imread(IMREAD_COLOR / IMREAD_GRAYSCALE) through PIL
+        (PNG is lossless; a JPEG goes through PIL's decoder, and no pixel parity with cv2's is claimed)."""
+        from PIL import Image
+        item = self.files[index]
+        with Image.open(item["img"]) as im:
+            image = np.ascontiguousarray(np.asarray(im.convert("RGB"), dtype=np.uint8)[:, :, ::-1])
+        label = None
+        if "label" in item:
+            with Image.open(item["label"]) as im:
+                label = np.ascontiguousarray(np.asarray(im.convert("L"), dtype=np.uint8))
+            if label.shape != image.shape[:2]:
+                raise ValueError("%s: label size %s differs from image size %s" % (item["name"], label.shape, image.shape[:2]))
+        return image, label
+
     def pack_batch(self, params, src_hws, crop_size=None):
         cfg = self.aug_config
         if crop_size is not None:
             cfg.crop_h, cfg.crop_w = crop_size
         return pack_batch(params, src_hws, cfg, self.mean, self.std)
+
+
+class NameListDataSet(BaseDataSet):
+    """A dataset whose list file holds one sample name per line (Pascal-Context, COCO-Stuff): images at
+    root/images/<name>.jpg, labels at root/<LABEL_DIR>/<name><LABEL_SUFFIX>, raw label 0 unlabelled and raw k the class
+    k - 1.  Subclasses set KEY (of label_index_<KEY>.pkl), NUM_CLASSES, LABEL_DIR and LABEL_SUFFIX."""
+    KEY = NUM_CLASSES = LABEL_DIR = LABEL_SUFFIX = None
+    class_weights = None
+
+    def __init__(self, root, list_path, max_iters=None, split="train", crop_size=(321, 321),
+                 mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), scale=True, mirror=True, brightness=True,
+                 ignore_label=255, balance=0, longsize=-1, shortsize=-1, **kwargs):
+        if split not in ("train", "val"):
+            raise NotImplementedError("%s: split %r is not built (train and val are)" % (self.KEY, split))
+        if ignore_label != 255:
+            # the reference shifts the uint8 map by one (0 - 1 wraps to 255): the table below is that only at 255
+            raise ValueError("%s: ignore_label must be 255, the value raw label 0 maps to (got %r)"
+                             % (self.KEY, ignore_label))
+        super().__init__(split=split, crop_size=crop_size, mean=mean, std=std, scale=scale, mirror=mirror,
+                         brightness=brightness, ignore_label=ignore_label, balance=balance, longsize=longsize,
+                         shortsize=shortsize, **kwargs)
+        self.num_classes = self.NUM_CLASSES
+        self.root, self.list_path = root, list_path
+        self.id_to_trainid = {0: ignore_label}
+        self.id_to_trainid.update({k: k - 1 for k in range(1, 256)})
+        self.cmap_labels = bitrev_palette(self.num_classes, first=1)
+        with open(list_path) as f:
+            self.img_ids = [line.strip() for line in f if line.strip()]
+        if max_iters is not None:
+            self.img_ids = self.img_ids * int(np.ceil(float(max_iters) / len(self.img_ids)))
+        self.files = [{"img": os.path.join(root, "images", name + ".jpg"),
+                       "label": os.path.join(root, self.LABEL_DIR, name + self.LABEL_SUFFIX), "name": name}
+                      for name in self.img_ids]
+        if self.resample:
+            self.load_index(os.path.join(os.path.dirname(list_path), "label_index_%s.pkl" % self.KEY))

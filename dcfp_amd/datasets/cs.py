@@ -54,17 +54,3 @@ class DataSet(BaseDataSet):
             self._class_weights = torch.tensor(CLASS_WEIGHTS, dtype=torch.float32,
                                                device="cuda" if torch.cuda.is_available() else "cpu")
         return self._class_weights
-
-    def decode(self, index):
-        """-> (uint8 [H,W,3] BGR, uint8 [H,W] raw ids or None): cv2.imread(IMREAD_COLOR / IMREAD_GRAYSCALE) through PIL."""
-        from PIL import Image
-        item = self.files[index]
-        with Image.open(item["img"]) as im:
-            image = np.ascontiguousarray(np.asarray(im.convert("RGB"), dtype=np.uint8)[:, :, ::-1])
-        label = None
-        if "label" in item:
-            with Image.open(item["label"]) as im:
-                label = np.ascontiguousarray(np.asarray(im.convert("L"), dtype=np.uint8))
-            if label.shape != image.shape[:2]:
-                raise ValueError("%s: label size %s differs from image size %s" % (item["name"], label.shape, image.shape[:2]))
-        return image, label

@@ -1826,6 +1826,18 @@ def upsample_cross_entropy(logits, labels, size, align_corners, ignore_index=255
                               ignore_index, pixel_keep)
 
 
+CE_BACKWARD_VARIANTS = ("cells19", "cells_chunked", "per_output")
+
+
+def ce_backward_plan(N, C_, h, w, H, W):
+    """-> (variant, chunk_width, chunks): the kernel the fused upsample + CE backward (plain and weighted) launches at
+    this shape; variant is one of CE_BACKWARD_VARIANTS (dcfp_upsample_ce_bwd_plan)."""
+    v, ct, n = C.c_int(-1), C.c_int(0), C.c_int(0)
+    check(_lib.lib().dcfp_upsample_ce_bwd_plan(int(N), int(C_), int(h), int(w), int(H), int(W), C.byref(v),
+                                               C.byref(ct), C.byref(n)), "upsample_ce_bwd_plan")
+    return CE_BACKWARD_VARIANTS[v.value], ct.value, n.value
+
+
 # ------------------------------------------------------------------ GSRL pieces
 def upsample_margin(logits, size, align_corners):
     """p1 - p2 of softmax(F.interpolate(logits, size)) per pixel, [N,H,W]."""

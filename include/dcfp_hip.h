@@ -23,7 +23,8 @@
  *     weight-gradient kernel where the cost model prefers it, default / 2 wherever it applies and beats the direct
  *     kernel), DCFP_WINO_WGRAD_RATE (TF the cost model prices that kernel at), DCFP_CONV_STEM (0: the Cin = 3 stem conv
  *     through the general kernels), DCFP_IGEMM_NT (1 / 2: nt / sc1 output stores of the 1x1 kernel, A/B), DCFP_WF_SCALAR_EPI, DCFP_CONV_GEMV (0: 1x1 convs on a 1 x 1 map through the general kernels),
- *     DCFP_CE_BWD_CELLS (0: the per-output fused upsample + CE backward instead of the cell-organised one) -
+ *     DCFP_CE_BWD_CELLS (0: the per-output fused upsample + CE backward instead of the cell-organised one, at every
+ *     class count) -
  *     kernel / algorithm selection A/B knobs, results are identical up to the documented
  *     fp32 tolerances; changing them after the first call has no effect.  (A thread_local 16-entry cache
  *     of dispatch decisions for dilated convs is the only other state.)
@@ -434,6 +435,13 @@ int dcfp_upsample_ce_bwd_f32(const float* logits, const int64_t* labels,
                              int N, int C, int h, int w, int H, int W, int align_corners,
                              const float* lse, const float* grad_scale /* device scalar */,
                              float* dlogits, dcfp_stream_t stream);
+/* Which kernel dcfp_upsample_ce_bwd_f32 and dcfp_upsample_wce_bwd_f32 launch at this shape (both make this decision):
+ *   variant 0 "cells19"        C == 19: the cell-organised kernel with all 19 classes in registers; 19, 1
+ *           1 "cells_chunked"  the same kernel per class window of chunk_width classes, chunks = ceil(C / chunk_width)
+ *                              windows in one launch
+ *           2 "per_output"     one thread per dlogits element (DCFP_CE_BWD_CELLS=0, C == 1, or a block count
+ *                              beyond 32 bits); chunk_width = chunks = 0. */
+int dcfp_upsample_ce_bwd_plan(int N, int C, int h, int w, int H, int W, int* variant, int* chunk_width, int* chunks);
 
 /* OHEM threshold input (loss/ohem.py:20-33): per position of the 1/factor-zoomed grid
  * (H8 x W8 = round(H/factor) x round(W/factor), scipy.ndimage.zoom coordinates) the nearest

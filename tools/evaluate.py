@@ -4,13 +4,13 @@ the (optionally slimmed, optionally frozen-to-fp16) model, predict batch by batc
 the device, print {'meanIU', 'IU_array'} and append IoU / precision / recall / FPS to result.txt in the snapshot
 directory.  `--iou-type boundary` scores class boundaries only.
 
-Without `--dataset` the data are SYNTHETIC (seeded rectangles).  With `--dataset CS --data-para '{"root": ...,
+Without `--dataset` the data are SYNTHETIC (seeded rectangles).  With `--dataset CS|CTX|COCO --data-para '{"root": ...,
 "list_path": ...}'` the validation list is read through datasets.EvalLoader: --longsize / --shortsize, the 8k+1 padding
 of `--whole True --align-corner True`, palette PNGs with `--save-predict True`, and one process per GPU under
 torchrun (`--ddp`, every file counted exactly once, the matrix summed over the ranks).  `--whole True` with more than
 one scale or with --flip then runs evaluate.predict_vote: prediction, argmax and confusion matrix are one launch after
 the network (`--fused-vote False`: the N x C x H x W path, for A/B).  The test-split submission of evaluate_test.py
-and the CTX / ADE / COCO datasets are not part of it."""
+and the ADE dataset are not part of it."""
 import argparse
 import json
 import os

@@ -6,7 +6,7 @@ class it holds.  The pickle is a plain dict {str(class): [{'idx': file index, 'n
 float64 [num_classes] list lengths}, the format of the reference's label_index.py: a file written by either side loads
 in the other.  The dataset looks for it in the directory of its list file.
 
-    python tools/label_index.py --dataset CS --data-para '{"root": ..., "list_path": ".../train.lst"}' --save-dir ...
+    python tools/label_index.py --dataset CS|CTX|COCO --data-para '{"root": ..., "list_path": ".../train.lst"}' --save-dir ...
 
 Host numpy: this runs once per dataset."""
 import argparse

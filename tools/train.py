@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """Training + scoring driver — the loop of the reference's train.py:140-293 (same flags for
 the model / optimiser / loss / pruning options).  Without --dataset it runs over SYNTHETIC Cityscapes-shaped
-batches; with --dataset (and the reference's data flags) it reads a list file through dcfp_amd.datasets, whose
-augmentation chain runs on the device.
+batches; with --dataset CS|CTX|COCO (and the reference's data flags) it reads a list file through dcfp_amd.datasets,
+whose augmentation chain runs on the device (ADE is not built).
 One process per GPU: `python -m torch.distributed.run --nproc-per-node N tools/train.py ...`."""
 import argparse
 import json
@@ -62,7 +62,7 @@ def get_parser():
     p.add_argument("--prune-type", type=str, default=None)
     p.add_argument("--channel-cfg", type=str, default=None)
     p.add_argument("--dataset", type=str, default=None,
-                   help="CS: read real data through dcfp_amd.datasets (default: synthetic batches)")
+                   help="CS, CTX or COCO: read real data through dcfp_amd.datasets (default: synthetic batches)")
     p.add_argument("--data-dir", type=str, default="train", help="name of the data split (kept for the reference's scripts)")
     p.add_argument("--random-mirror", action="store_true")
     p.add_argument("--random-brightness", action="store_true")
