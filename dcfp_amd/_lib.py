@@ -175,6 +175,9 @@ SIGNATURES = {
     "dcfp_label_boundary_workspace_bytes": (_Z, [_I, _I, _I]),
     "dcfp_label_boundary_i32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _Z, _P]),
     "dcfp_label_boundary_i64": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _Z, _P]),
+    "dcfp_png_deflate_bound": (_Z, [_I, _I]),
+    "dcfp_png_deflate_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "dcfp_png_deflate_labels_i32": (_I, [_P, _I, _I, _I, _P, _I, _P, _Z, _P, _P, _P, _Z, _P]),
     "dcfp_augment_u8_to_f32_nchw": (_I, [C.POINTER(AugSample), _I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _I, _P, _P, _P, _P]),
     "dcfp_balance_weight_f32": (_I, [_P, _P, _P, _I, _L, _I, _I, _I, C.c_double, _P, _P]),
     "dcfp_components_workspace_bytes": (_Z, [_I, _I]),

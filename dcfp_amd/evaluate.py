@@ -2,8 +2,12 @@
 multi-scale(+flip) prediction, on-device argmax and confusion matrix, mIoU.  Inference runs the
 conv kernels with the eval-mode BatchNorm folded into their epilogues (one kernel per
 conv+BN+ReLU); `predict_labels` and `predict_vote` never materialise the full-resolution logits."""
+import struct
+import zlib
+from concurrent.futures import ThreadPoolExecutor
 from math import ceil
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -141,6 +145,111 @@ def save_palette_png(pred, palette, path):
     im = Image.fromarray(np.ascontiguousarray(np.asarray(pred, dtype=np.uint8)))
     im.putpalette([int(v) for v in palette])
     im.save(path)
+
+
+_PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+_pinned = {}
+
+
+def _png_chunk(kind, data):
+    return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(data, zlib.crc32(kind)))
+
+
+def png_container(stream_bytes, H, W, palette=None):
+    """An 8-bit PNG file around a finished zlib stream of H filtered rows of W bytes (ops.png_deflate_labels; DESIGN
+    §15): colour type 3 with a PLTE chunk for `palette` (flat R, G, B list, at most 256 entries), grey without one.
+    Pure host; the only pass over data is the CRC of the compressed bytes."""
+    if H < 1 or W < 1:
+        raise ValueError("png_container: H, W >= 1 expected, got %r x %r" % (H, W))
+    chunks = [_PNG_SIGNATURE, _png_chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 0 if palette is None else 3, 0, 0, 0))]
+    if palette is not None:
+        plte = bytes(int(v) for v in palette)
+        if len(plte) == 0 or len(plte) % 3 or len(plte) > 768:
+            raise ValueError("png_container: a palette is 1 .. 256 R, G, B triples, got %d values" % len(plte))
+        chunks.append(_png_chunk(b"PLTE", plte))
+    chunks += [_png_chunk(b"IDAT", bytes(stream_bytes)), _png_chunk(b"IEND", b"")]
+    return b"".join(chunks)
+
+
+def reverse_id_table(dataset):
+    """uint8 [256]: train id -> the dataset's label id, by the dataset's own id2trainId(reverse=True) - what
+    evaluate_test.py:153 applies to a prediction before it saves the submission PNG."""
+    return dataset.id2trainId(np.arange(256, dtype=np.uint8), reverse=True)
+
+
+def encode_label_pngs(pred, luts, palettes):
+    """pred int32 [N,H,W] on the device, luts uint8 [P,256] (tensor or array; None: the identity), palettes: P flat
+    R, G, B lists or None (grey) -> [N][P] PNG files as bytes, file [n][p] showing luts[p][pred[n] & 255].  The streams
+    are deflated on the device (ops.png_deflate_labels); two device-to-host copies per call - the P*N lengths, then
+    exactly the compressed bytes into a pinned buffer - and the map itself never leaves the device."""
+    if luts is not None and not isinstance(luts, torch.Tensor):
+        luts = torch.from_numpy(np.ascontiguousarray(np.asarray(luts, dtype=np.uint8)))
+    if luts is not None:
+        luts = luts.reshape(-1, 256).to(pred.device).contiguous()
+    P = 1 if luts is None else int(luts.shape[0])
+    if len(palettes) != P:
+        raise ValueError("encode_label_pngs: one palette (or None) per lookup table expected")
+    N, H, W = (int(v) for v in pred.shape)
+    streams, _, lengths = ops.png_deflate_labels(pred, luts)
+    lengths = lengths.cpu().tolist()                                      # copy 1 (synchronises)
+    total = int(sum(lengths))
+    key = (pred.device.index, torch.cuda.current_stream().cuda_stream)
+    host = _pinned.get(key)
+    if host is None or host.numel() < total:
+        host = _pinned[key] = torch.empty(max(total, 1 << 20), dtype=torch.uint8).pin_memory()
+    host[:total].copy_(streams[:total], non_blocking=True)                # copy 2
+    torch.cuda.current_stream().synchronize()
+    raw = host.numpy()
+    files, at = [], 0
+    for n in range(N):
+        files.append([])
+        for p in range(P):
+            s = n * P + p
+            files[n].append(png_container(raw[at:at + lengths[s]].tobytes(), H, W, palettes[p]))
+            at += lengths[s]
+    return files
+
+
+class PngWriter:
+    """Writes finished byte strings to paths on at most 4 threads of its own, so that the next batch does not wait for
+    the file system.  drain() waits for everything handed in and re-raises the first exception; leaving the `with`
+    block drains."""
+
+    def __init__(self, threads=4):
+        self.pool = ThreadPoolExecutor(max_workers=max(1, min(4, int(threads))))
+        self.pending = []
+
+    @staticmethod
+    def _write(path, data):
+        with open(path, "wb") as f:
+            f.write(data)
+
+    def write(self, path, data):
+        self.pending.append(self.pool.submit(self._write, path, data))
+
+    def drain(self):
+        pending, self.pending = self.pending, []
+        errors = []
+        for f in pending:
+            try:
+                f.result()
+            except Exception as e:  # noqa: BLE001  (every write is waited for before the first error is raised)
+                errors.append(e)
+        if errors:
+            raise errors[0]
+
+    def close(self):
+        try:
+            self.drain()
+        finally:
+            self.pool.shutdown(wait=True)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
 
 
 @torch.no_grad()

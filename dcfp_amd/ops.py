@@ -2019,6 +2019,43 @@ def label_boundary(labels, num_classes, d, background=255):
     return out
 
 
+def png_deflate_bound(H, W):
+    """The largest size in bytes of one stream of png_deflate_labels for an H x W map (host only)."""
+    return int(_lib.lib().dcfp_png_deflate_bound(int(H), int(W)))
+
+
+def png_deflate_labels(pred, luts=None):
+    """Finished zlib streams of the 8-bit PNGs of a prediction: pred int32 [N,H,W], luts uint8 [P,256]
+    (1 <= P <= 4; None: the identity table) -> (streams, offsets, lengths): stream n*P + p, the image
+    luts[p][pred[n] & 255], is streams[offsets[s] : offsets[s] + lengths[s]]; streams is a uint8 device buffer (a
+    workspace: the next call on the stream overwrites it), offsets and lengths are int64 [N*P] device tensors.  The
+    streams lie one after the other from 0 on, so sum(lengths) bytes hold them all."""
+    if not isinstance(pred, torch.Tensor) or not pred.is_cuda:
+        raise RuntimeError("dcfp_amd: pred must be a CUDA/HIP tensor (no CPU fallback exists)")
+    if pred.dtype != torch.int32 or pred.dim() != 3 or not pred.is_contiguous():
+        raise RuntimeError("png_deflate_labels: a contiguous int32 [N,H,W] prediction expected")
+    if luts is None:
+        luts = torch.arange(256, dtype=torch.uint8, device=pred.device).reshape(1, 256)
+    if not (isinstance(luts, torch.Tensor) and luts.is_cuda and luts.device == pred.device and luts.dtype == torch.uint8
+            and luts.dim() == 2 and luts.shape[1] == 256 and 1 <= luts.shape[0] <= 4 and luts.is_contiguous()):
+        raise RuntimeError("png_deflate_labels: luts must be a contiguous uint8 [P,256] tensor on pred's device, "
+                           "1 <= P <= 4")
+    N, H, W = (int(v) for v in pred.shape)
+    P = int(luts.shape[0])
+    L = _lib.lib()
+    bound = L.dcfp_png_deflate_bound(H, W)
+    ws_bytes = L.dcfp_png_deflate_workspace_bytes(N, H, W, P)
+    if N < 1 or bound == 0 or ws_bytes == 0:
+        raise RuntimeError("png_deflate_labels: N >= 1, 1 <= H <= 4096, 1 <= W <= 8192 expected, got %s"
+                           % (tuple(pred.shape),))
+    out = _workspace("png_streams", N * P * bound, pred.device)
+    ws = _workspace("png_rows", ws_bytes, pred.device)
+    meta = torch.empty((2, N * P), dtype=torch.int64, device=pred.device)
+    check(L.dcfp_png_deflate_labels_i32(_p(pred), N, H, W, _p(luts), P, _p(out), out.numel(), _p(meta[0]), _p(meta[1]),
+                                        _p(ws), ws.numel(), _stream()), "png_deflate_labels")
+    return out, meta[0], meta[1]
+
+
 def augment_batch(images, labels, records, taps, lut_a, lut_b, id_table, crop_size, ignore_label=255):
     """The device half of the training augmentation (datasets.base builds its arguments).
     images: N uint8 [H,W,3] BGR tensors, labels: N uint8 [H,W] raw-id tensors or None, all on one device and dense;

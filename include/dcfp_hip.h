@@ -743,6 +743,24 @@ int dcfp_pyramid_pool_nhwc_f16(const void* x, int N, int H, int W, int C8, int x
                                const int* sizes, void* const* y, const int* y_pitch, void* workspace,
                                size_t workspace_bytes, dcfp_stream_t stream);
 
+/* ------------------------------------------------- label maps as PNG streams (png.hip)
+ * pred int32 [N,H,W] and P lookup tables uint8 [P][256] (1 <= P <= 4) -> N*P finished zlib streams, stream n*P + p
+ * holding the 8-bit image lut[p][pred[n] & 255]: filter type Up on every row, one fixed-Huffman deflate block and an
+ * empty stored block per row (every row's piece is whole bytes), run-length matches at distance 1 by a closed-form
+ * rule per run, header 78 01, trailer 03 00 + Adler-32.  The uint8 image is never stored.  The streams lie one after
+ * the other in `out` (stream s at offsets[s], lengths[s] bytes; both device int64 [N*P]).  Integer arithmetic only,
+ * byte-identical between two calls.  H <= 4096, W <= 8192, N*P*H < 2^31, else DCFP_E_UNSUPPORTED.
+ *   dcfp_png_deflate_bound(H, W): the largest size of one stream, 2 + H * ((9*(W+1) + 13 + 7)/8 + 4) + 2 + 4
+ *       (0 for sizes the encoder refuses); out_bytes >= N*P times it, else DCFP_E_BADDESC.
+ *   dcfp_png_deflate_workspace_bytes(N, H, W, P): the workspace (4-byte aligned; 0 for arguments the encoder refuses);
+ *       a smaller one is DCFP_E_WORKSPACE.
+ * Null pointers, sizes < 1 and P outside 1 .. 4 are DCFP_E_BADDESC; all of it is checked before any HIP call. */
+size_t dcfp_png_deflate_bound(int H, int W);
+size_t dcfp_png_deflate_workspace_bytes(int N, int H, int W, int P);
+int dcfp_png_deflate_labels_i32(const int32_t* pred, int N, int H, int W, const uint8_t* luts, int P, uint8_t* out,
+                                size_t out_bytes, int64_t* offsets, int64_t* lengths, void* workspace,
+                                size_t workspace_bytes, dcfp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,8 +9,9 @@ Without `--dataset` the data are SYNTHETIC (seeded rectangles).  With `--dataset
 of `--whole True --align-corner True`, palette PNGs with `--save-predict True`, and one process per GPU under
 torchrun (`--ddp`, every file counted exactly once, the matrix summed over the ranks).  `--whole True` with more than
 one scale or with --flip then runs evaluate.predict_vote: prediction, argmax and confusion matrix are one launch after
-the network (`--fused-vote False`: the N x C x H x W path, for A/B).  The test-split submission of evaluate_test.py
-and the ADE dataset are not part of it."""
+the network (`--fused-vote False`: the N x C x H x W path, for A/B).  `--device-png True` deflates the palette PNGs
+of `--save-predict` on the device.  The test-split export is tools/evaluate_test.py, which shares
+`build_model` and `predict_batch` with this file.  The ADE dataset is not part of it."""
 import argparse
 import json
 import os
@@ -69,6 +70,8 @@ def get_parser():
     p.add_argument("--fused-vote", type=str2bool, default=None,
                    help="multi-scale / flip whole-image prediction through evaluate.predict_vote "
                         "(default: True with --dataset, False without)")
+    p.add_argument("--device-png", type=str2bool, default="False",
+                   help="deflate the PNGs of --save-predict on the device (evaluate.encode_label_pngs)")
     return p
 
 
@@ -114,6 +117,42 @@ def build_model(args):
     if args.restore_from:
         load_model(model, args.restore_from)
     return model.eval()
+
+
+def predict_batch(model, image, args, scales, fused, size, label=None, conf=None):
+    """One batch of a dataset through the prediction branch the command line selects (module docstring).  image: as
+    the loader served it; size: the files' own (H, W).  With `label` and `conf`, and where the branch allows it, the
+    confusion matrix is counted in the same launch.  -> (pred int32 [N,H,W], counted, seconds of the prediction, the
+    network's input size)."""
+    h, w = map(int, args.input_size.split(","))
+    C = args.num_classes
+    resized = args.longsize > 0 or args.shortsize > 0
+    if args.longsize > 0:
+        image = ev.generate_size_image(image, args.longsize, "long")
+    elif args.shortsize > 0:
+        image = ev.generate_size_image(image, args.shortsize, "short")
+    size_scale = tuple(image.shape[2:])
+    if args.whole and args.align_corner:
+        image = ev.pad_inf(image)
+    torch.cuda.synchronize()
+    start_time = time.perf_counter()
+    counted = False
+    if args.whole and scales == [1.0] and not args.flip and not resized:
+        pred = ev.predict_labels(model, image)[:, :size_scale[0], :size_scale[1]].contiguous()
+    elif args.whole and fused:
+        counted = not resized and conf is not None        # prediction, argmax and confusion: one launch
+        pred, scores = ev.predict_vote(model, image, scales, args.flip, args.align_corner, out_hw=size_scale,
+                                       labels=label if counted else None, conf=conf if counted else None,
+                                       want_scores=resized, ignore_index=args.ignore_label)
+        if resized:
+            pred = ops.upsample_argmax(scores, size, False)
+    else:
+        output = ev.predict_multiscale(model, image, (h, w), scales, C, args.flip, args.align_corner,
+                                       args.whole)
+        output = output[:, :, :size_scale[0], :size_scale[1]].contiguous()
+        pred = ops.upsample_argmax(output, size, not resized)   # same size, corners aligned: the plain argmax
+    torch.cuda.synchronize()
+    return pred, counted, time.perf_counter() - start_time, tuple(image.shape)
 
 
 def main(argv=None):
@@ -202,7 +241,6 @@ def main_dataset(parser, argv=None):
     backend = parser.parse_known_args(argv)[0].dist_backend
     with Engine(custom_parser=parser, backend=backend) as engine:
         args = parser.parse_args(argv)
-        h, w = map(int, args.input_size.split(","))
         scales = [float(s) for s in args.ms.split(",")]
         fused = True if args.fused_vote is None else args.fused_vote
         rank, world = (dist.get_rank(), engine.world_size) if engine.distributed else (0, 1)
@@ -221,7 +259,6 @@ def main_dataset(parser, argv=None):
         if args.save_predict:
             os.makedirs(save_path, exist_ok=True)
         boundary = args.iou_type == "boundary"
-        resized = args.longsize > 0 or args.shortsize > 0
         conf = torch.zeros((C, C + 1 if boundary else C), dtype=torch.int64, device=device)
         nbatches = len(loader)
         warmup = min(FPS_WARMUP, nbatches - 1)
@@ -229,46 +266,27 @@ def main_dataset(parser, argv=None):
         for idx, (image, label, metas) in enumerate(loader):
             size = metas[0]["size"]
             with torch.no_grad():
-                if args.longsize > 0:
-                    image = ev.generate_size_image(image, args.longsize, "long")
-                elif args.shortsize > 0:
-                    image = ev.generate_size_image(image, args.shortsize, "short")
-                size_scale = tuple(image.shape[2:])
-                if args.whole and args.align_corner:
-                    image = ev.pad_inf(image)
-                torch.cuda.synchronize()
+                pred, counted, elapsed, in_shape = predict_batch(model, image, args, scales, fused, size, label,
+                                                                 None if boundary else conf)
                 start_time = time.perf_counter()
-                counted = False
-                if args.whole and scales == [1.0] and not args.flip and not resized:
-                    pred = ev.predict_labels(model, image)[:, :size_scale[0], :size_scale[1]].contiguous()
-                elif args.whole and fused:
-                    counted = not resized and not boundary        # prediction, argmax and confusion: one launch
-                    pred, scores = ev.predict_vote(model, image, scales, args.flip, args.align_corner, out_hw=size_scale,
-                                                   labels=label if counted else None, conf=conf if counted else None,
-                                                   want_scores=resized, ignore_index=args.ignore_label)
-                    if resized:
-                        pred = ops.upsample_argmax(scores, size, False)
-                else:
-                    output = ev.predict_multiscale(model, image, (h, w), scales, C, args.flip, args.align_corner,
-                                                   args.whole)
-                    output = output[:, :, :size_scale[0], :size_scale[1]].contiguous()
-                    pred = ops.upsample_argmax(output, size, not resized)   # same size, corners aligned: the plain argmax
-                torch.cuda.synchronize()
-                elapsed = time.perf_counter() - start_time
                 if boundary:
                     ev.boundary_confusion_matrix(label, pred, C, args.dilation_ratio, args.ignore_label, out=conf)
                 elif not counted:
                     ev.get_confusion_matrix(label, pred, C, args.ignore_label, out=conf)
                 torch.cuda.synchronize()
-                metric = time.perf_counter() - start_time - elapsed
-            if args.save_predict:
+                metric = time.perf_counter() - start_time
+            if args.save_predict and args.device_png:
+                for meta, files in zip(metas, ev.encode_label_pngs(pred, None, [palette])):
+                    with open(os.path.join(save_path, meta["name"] + ".png"), "wb") as f:
+                        f.write(files[0])
+            elif args.save_predict:
                 for i, meta in enumerate(metas):
                     ev.save_palette_png(pred[i].cpu().numpy(), palette, os.path.join(save_path, meta["name"] + ".png"))
             print_str = " Iter%d/%d" % (idx + 1, nbatches)
             if idx >= warmup:
                 pure_inf_time += elapsed
                 metric_time += metric
-                timed_images += image.shape[0]
+                timed_images += in_shape[0]
                 timed_batches += 1
                 fps = timed_images / pure_inf_time
                 print_str += f" FPS: {fps:.2f} img / s, metric {metric * 1e3:.3f} ms"
