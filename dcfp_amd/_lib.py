@@ -30,6 +30,13 @@ class ConvF16Desc(C.Structure):
                  "y_pitch", "y_off", "res_pitch", "res_off", "relu")]
 
 
+class ConvF8Desc(C.Structure):
+    """DcfpConvF8Desc: one conv of the fp8 deployment engine (NHWC e4m3, packed weights)."""
+    _fields_ = [(n, C.c_int32) for n in
+                ("N", "H", "W", "Cin16", "x_pitch", "Cout", "K", "stride", "pad", "dil", "Hout", "Wout",
+                 "y_pitch", "y_off", "res_pitch", "res_off", "relu")] + [("res_mul", C.c_float)]
+
+
 class EicEntry(C.Structure):
     _fields_ = [("gamma", C.c_void_p), ("grad", C.c_void_p), ("eic", C.c_void_p),
                 ("n", C.c_int32), ("pad_", C.c_int32)]
@@ -95,6 +102,7 @@ _P, _I, _L, _F, _Z = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
 _D = C.POINTER(ConvDesc)
 _R = C.POINTER(BnRunning)
 _H = C.POINTER(ConvF16Desc)
+_H8 = C.POINTER(ConvF8Desc)
 
 # name -> (restype, argtypes); mirrors include/dcfp_hip.h one to one
 SIGNATURES = {
@@ -193,6 +201,12 @@ SIGNATURES = {
     "dcfp_avgpool_nhwc_f16": (_I, [_P, _P, _I, _L, _I, _I, _I, _P, _Z, _P]),
     "dcfp_broadcast_nhwc_f16": (_I, [_P, _I, _P, _I, _L, _I, _I, _I, _P]),
     "dcfp_nchw_f32_to_nhwc_f16": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    "dcfp_conv2d_fwd_f8_nhwc": (_I, [_H8, _P, _P, _P, _P, _P, _P, _P]),
+    "dcfp_conv2d_fwd_f8_nhwc_to_f32_nchw": (_I, [_H8, _P, _P, _P, _P, _P, _P]),
+    "dcfp_cast_nhwc_f16_to_f8": (_I, [_P, _I, _P, _I, _I, _L, _I, _F, _P]),
+    "dcfp_maxpool3x3s2_nhwc_f8": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "dcfp_avgpool_nhwc_f8_to_f16": (_I, [_P, _P, _I, _L, _I, _I, _I, _F, _P, _Z, _P]),
+    "dcfp_broadcast_nhwc_f16_to_f8": (_I, [_P, _I, _P, _I, _L, _I, _I, _I, _F, _P]),
     "dcfp_resize_bilinear_nhwc_f16": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P]),
     "dcfp_pyramid_pool_nhwc_f16_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _P]),
     "dcfp_pyramid_pool_nhwc_f16": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),

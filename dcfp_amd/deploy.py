@@ -18,6 +18,14 @@ the device and goes through the kernels of csrc/conv_f16.hip and csrc/heads_f16.
     directly, one `pyramid` node pools all levels from that slice in one sweep, a 1x1 conv per level runs on the s x s
     map and a `resize` node writes each prior into its slice.
 
+`build_engine(model, precision="fp8", amax=calibrate(fp16 engine, batches))` builds the calibrated 8-bit engine for
+`simple` and `deeplabv3` (opt-in; DESIGN.md §11a, kernels in csrc/conv_f8.hip): activations NHWC e4m3 with channels
+padded to 16 and ONE scale per buffer (the calibrated absolute maximum of the records writing it / 448), weights
+[Cout8][kh][kw][Cin16] e4m3 quantised per output channel, the epilogue acc * mul[co] + add[co] (+ res_mul * residual).
+The conv that reads the image and the image-pool branch stay fp16; a `cast` node quantises the former's output.  Such an
+engine is saved as format 2; format-1 (fp16) engines load and run as before.  `Engine.trace(image)` returns what every
+record wrote - the calibration and the per-record tests are built on it.
+
 An Engine offers what evaluate.predict_whole / predict_sliding / predict_multiscale / predict_labels ask of a net:
 engine(image) -> [logits], engine.lowres_logits(image) -> [lowres], engine.align_corner.
 """
@@ -29,13 +37,33 @@ import torch.nn as nn
 from . import _lib, ops
 from ._lib import check
 
-FORMAT = 1
+FORMAT = 1                                          # fp16 engines
+FORMAT_F8 = 2                                       # fp8 engines (meta["dtype"] == "float8_e4m3fn")
+F8 = torch.float8_e4m3fn
+F8_MAX = 448.0
 _POOL_OPS = ("maxpool", "avgpool", "broadcast")
+_GRAN = {"f16": 8, "f8": 16}                        # channel granule of a buffer: one 16-byte chunk
+_ESIZE = {"f16": 2, "f8": 1}
 PYRAMID_MAX_LEVELS, PYRAMID_MAX_SIZE = 4, 8         # what dcfp_pyramid_pool_nhwc_f16 takes
 
 
 def _r8(c):
     return (int(c) + 7) // 8 * 8
+
+
+def _rg(c, g):
+    return (int(c) + g - 1) // g * g
+
+
+def to_f8(t):
+    """The engine's one conversion rule: clamp to [-448, 448] in fp32, then round to nearest even (e4m3fn keeps its
+    subnormals; without the clamp torch turns 465 into NaN)."""
+    return t.float().clamp(-F8_MAX, F8_MAX).to(F8)
+
+
+def _f32(v):
+    """A Python float formed in fp64, rounded once to fp32 (what a kernel's float argument holds)."""
+    return float(torch.tensor(float(v), dtype=torch.float64).float())
 
 
 def fold_bn(conv, bn):
@@ -64,18 +92,44 @@ def pack_weight(w, scale, segments, cin8):
 
 
 def unpack_weight(packed, cout, segments):
-    """The inverse of pack_weight: fp16 [cout, Cin, k, k]."""
+    """The inverse of pack_weight / pack_weight_f8: [cout, Cin, k, k] in the packed dtype."""
     parts = [packed[:cout, :, :, off:off + cnt] for off, cnt in segments]
     return torch.cat(parts, dim=3).permute(0, 3, 1, 2).contiguous()
 
 
-class _Planner:
-    def __init__(self):
-        self.records, self.tensors, self.pitch, self.segments = [], [], [], []
+def pack_weight_f8(wf, segments, cin16):
+    """Folded fp64 weights [Cout, Cin, k, k] -> (e4m3 [Cout8, k, k, cin16], s_w fp64 [Cout]): quantised per output
+    channel, q = fp8(clamp(w / s_w[co])) with s_w[co] = max|w[co]| / 448 (1 for an all-zero filter); channel placement
+    and zero padding as pack_weight."""
+    cout, cin, kh, kw = wf.shape
+    amax = wf.abs().amax(dim=(1, 2, 3))
+    s_w = torch.where(amax > 0, amax / F8_MAX, torch.ones_like(amax))
+    q = to_f8(wf / s_w.view(-1, 1, 1, 1))
+    out = torch.zeros((_r8(cout), kh, kw, cin16), dtype=torch.uint8).view(F8)
+    s = 0
+    for off, cnt in segments:
+        out[:cout, :, :, off:off + cnt] = q[:, s:s + cnt].permute(0, 2, 3, 1)
+        s += cnt
+    assert s == cin, (s, cin)
+    return out.contiguous(), s_w
 
-    def buffer(self, segments, pitch=None):
-        self.pitch.append(pitch if pitch is not None else _r8(sum(c for _, c in segments)))
+
+class _Planner:
+    """fp8 = False: every buffer and record is fp16.  fp8 = True: a new buffer is fp8 (granule 16) unless asked
+    otherwise, a conv takes the format of the buffer it reads, and the fp8 records keep their folded fp64 weights until
+    finalize_f8 knows every buffer's scale."""
+
+    def __init__(self, fp8=False):
+        self.records, self.tensors, self.pitch, self.segments, self.fmt = [], [], [], [], []
+        self.fp8 = bool(fp8)
+        self.gran = _GRAN["f8" if fp8 else "f16"]    # of the buffers the plan makes by default (concat slices)
+        self.scales = None
+
+    def buffer(self, segments, pitch=None, fmt=None):
+        fmt = fmt or ("f8" if self.fp8 else "f16")
+        self.pitch.append(pitch if pitch is not None else _rg(sum(c for _, c in segments), _GRAN[fmt]))
         self.segments.append(list(segments))
+        self.fmt.append(fmt)
         return len(self.pitch) - 1
 
     def tensor(self, t):
@@ -93,20 +147,71 @@ class _Planner:
         if cin != sum(c for _, c in self.segments[src]):
             raise ValueError(f"freeze: {name} reads {cin} channels, its input holds {self.segments[src]}")
         scale, shift = fold_bn(conv, bn)
-        sh = torch.zeros(_r8(cout), dtype=torch.float32)
-        sh[:cout] = shift.float()
+        fmt = self.fmt[src]
         if dst is None:
-            dst = -1 if f32 else self.buffer([(0, cout)])
-        rec = {"op": "conv", "name": name, "src": src, "dst": dst, "res": res, "cin": int(cin), "cout": int(cout),
-               "cin8": self.pitch[src], "k": k[0], "stride": s[0], "pad": p[0], "dil": d[0], "relu": bool(relu),
-               "y_off": int(y_off), "f32": bool(f32), "segments": [list(sg) for sg in self.segments[src]],
-               "w": self.tensor(pack_weight(conv.weight, scale, self.segments[src], self.pitch[src])),
-               "shift": self.tensor(sh)}
+            dst = -1 if f32 else self.buffer([(0, cout)], fmt=fmt)
+        if fmt == "f8":
+            rec = {"op": "conv", "fmt": "f8", "name": name, "src": src, "dst": dst, "res": res, "cin": int(cin),
+                   "cout": int(cout), "cin8": self.pitch[src], "k": k[0], "stride": s[0], "pad": p[0], "dil": d[0],
+                   "relu": bool(relu), "y_off": int(y_off), "f32": bool(f32),
+                   "segments": [list(sg) for sg in self.segments[src]],
+                   "_w64": conv.weight.detach().double().cpu() * scale.view(-1, 1, 1, 1), "_shift64": shift}
+            if (dst >= 0 and self.fmt[dst] != "f8") or (res >= 0 and self.fmt[res] != "f8"):
+                raise ValueError(f"freeze: {name}: an fp8 conv writes and adds fp8 buffers only")
+        else:
+            rec = self._conv_f16(name, src, dst, res, cin, cout, k, s, p, d, relu, y_off, f32, conv, scale, shift)
         if res >= 0 and [tuple(sg) for sg in self.segments[res]] != [(0, int(cout))]:
             # (the residual keeps its own pitch - the kernel takes res_pitch - but holds the conv's channels from 0)
             raise ValueError(f"freeze: {name}: residual holds {self.segments[res]}, the conv writes {cout} channels")
         self.records.append(rec)
         return dst
+
+    def _conv_f16(self, name, src, dst, res, cin, cout, k, s, p, d, relu, y_off, f32, conv, scale, shift):
+        sh = torch.zeros(_r8(cout), dtype=torch.float32)
+        sh[:cout] = shift.float()
+        rec = {"op": "conv", "name": name, "src": src, "dst": dst, "res": res, "cin": int(cin), "cout": int(cout),
+               "cin8": self.pitch[src], "k": k[0], "stride": s[0], "pad": p[0], "dil": d[0], "relu": bool(relu),
+               "y_off": int(y_off), "f32": bool(f32), "segments": [list(sg) for sg in self.segments[src]],
+               "w": self.tensor(pack_weight(conv.weight, scale, self.segments[src], self.pitch[src])),
+               "shift": self.tensor(sh)}
+        if self.fp8:
+            rec["fmt"] = "f16"
+        return rec
+
+    def finalize_f8(self, amax):
+        """Buffer scales from the calibration maxima, then the fp8 records' packed tensors."""
+        def need(name):
+            if name not in amax:
+                raise KeyError(f"build_engine: amax has no entry for the record {name!r}")
+            return float(amax[name])
+        top = {}
+        for r in self.records:                       # the largest calibrated |output| over the records writing a buffer
+            b = r["dst"]
+            if b >= 0 and self.fmt[b] == "f8" and r["op"] != "maxpool":   # (a cast writes what its source record wrote)
+                top[b] = max(top.get(b, 0.0), need(r["amax_of"] if r["op"] == "cast" else r["name"]))
+        scales = [1.0] * len(self.pitch)
+        for b, v in top.items():
+            scales[b] = v / F8_MAX if v > 0 else 1.0
+        for r in self.records:                       # (in plan order: the pool's input is scaled by then)
+            if r["op"] == "maxpool" and self.fmt[r["dst"]] == "f8":
+                scales[r["dst"]] = scales[r["src"]]
+        for r in self.records:
+            s_x = scales[r["src"]]
+            if r["op"] == "cast" or (r["op"] == "broadcast" and r.get("fmt") == "f8"):
+                r["scale"] = _f32(1.0 / scales[r["dst"]])
+            elif r["op"] == "avgpool" and r.get("fmt") == "f8":
+                r["scale"] = _f32(s_x)
+            elif r["op"] == "conv" and r["fmt"] == "f8":
+                s_y = 1.0 if r["f32"] else scales[r["dst"]]
+                wf, shift = r.pop("_w64"), r.pop("_shift64")
+                cout = r["cout"]
+                packed, s_w = pack_weight_f8(wf, r["segments"], r["cin8"])
+                mul, add = torch.zeros(_r8(cout), dtype=torch.float32), torch.zeros(_r8(cout), dtype=torch.float32)
+                mul[:cout] = (s_w * s_x / s_y).float()
+                add[:cout] = (shift / s_y).float()
+                r["w"], r["mul"], r["add"] = self.tensor(packed), self.tensor(mul), self.tensor(add)
+                r["res_mul"] = _f32(scales[r["res"]] / s_y) if r["res"] >= 0 else 0.0
+        self.scales = scales
 
     def node(self, op, name, src, dst, y_off=0, **extra):
         self.records.append({"op": op, "name": name, "src": src, "dst": dst, "y_off": int(y_off), **extra})
@@ -132,6 +237,9 @@ def _plan_sequential(pl, prefix, mods, x, tail_bn=None):
         if last and tail_bn is not None:
             bn, relu = tail_bn, True
         x = pl.conv(name, conv, bn, x, relu, f32=(last and bn is None))
+        if pl.fp8 and x >= 0 and pl.fmt[x] == "f16":   # the conv that reads the image stays fp16; quantise its output
+            x = pl.node("cast", name + ".cast", x, pl.buffer(pl.segments[x]), amax_of=name, fmt="f8",
+                        c=sum(c for _, c in pl.segments[x]))
     return x
 
 
@@ -145,7 +253,7 @@ def _plan_backbone(pl, bb, x, tail=None):
     mp = bb.maxpool
     if not isinstance(mp, nn.MaxPool2d) or (mp.kernel_size, mp.stride, mp.padding) != (3, 2, 1):
         raise NotImplementedError(f"freeze: backbone.maxpool {mp}")
-    x = pl.node("maxpool", "backbone.maxpool", x, pl.buffer(pl.segments[x]))
+    x = pl.node("maxpool", "backbone.maxpool", x, pl.buffer(pl.segments[x]), **({"fmt": "f8"} if pl.fp8 else {}))
     feats = {}
     for li in range(1, 5):
         layer = getattr(bb, f"layer{li}")
@@ -179,14 +287,20 @@ def _plan_aspp(pl, aspp, x):
     branches = [aspp.aspp1, aspp.aspp2, aspp.aspp3, aspp.aspp4]
     widths = [m.atrous_conv.weight.shape[0] for m in branches] + [pool[1].weight.shape[0]]
     offs, o = [], 0
-    for c in widths:      # every slice starts at a multiple of 8; the gaps hold the branches' zero padding
-        offs.append(o); o += _r8(c)
+    for c in widths:      # every slice starts at a multiple of the granule; the gaps hold the branches' zero padding
+        offs.append(o); o += _rg(c, pl.gran)
     cat = pl.buffer(list(zip(offs, widths)), pitch=o)
     for i, m in enumerate(branches):
         pl.conv(f"aspp.aspp{i + 1}.atrous_conv", m.atrous_conv, m.bn, x, True, dst=cat, y_off=offs[i])
-    g = pl.node("avgpool", "aspp.global_avg_pool.0", x, pl.buffer(pl.segments[x]))
-    g = pl.conv("aspp.global_avg_pool.1", pool[1], pool[2], g, isinstance(pool[3], nn.ReLU))
-    pl.node("broadcast", "aspp.global_avg_pool.up", g, cat, y_off=offs[4])
+    if pl.fp8:            # the image-pool branch stays fp16: N pixels, and its input is a mean, not a quantised map
+        g = pl.node("avgpool", "aspp.global_avg_pool.0", x, pl.buffer(pl.segments[x], pitch=pl.pitch[x], fmt="f16"),
+                    fmt="f8")
+        g = pl.conv("aspp.global_avg_pool.1", pool[1], pool[2], g, isinstance(pool[3], nn.ReLU))
+        pl.node("broadcast", "aspp.global_avg_pool.up", g, cat, y_off=offs[4], fmt="f8", c=widths[4])
+    else:
+        g = pl.node("avgpool", "aspp.global_avg_pool.0", x, pl.buffer(pl.segments[x]))
+        g = pl.conv("aspp.global_avg_pool.1", pool[1], pool[2], g, isinstance(pool[3], nn.ReLU))
+        pl.node("broadcast", "aspp.global_avg_pool.up", g, cat, y_off=offs[4])
     return pl.conv("aspp.conv1", aspp.conv1, aspp.bn1, cat, True)
 
 
@@ -262,24 +376,33 @@ def _plan_deeplabv3p(pl, model, x):
     return _plan_sequential(pl, "decoder.last_conv", list(dec.last_conv.children()), cat)
 
 
-def _freeze(model, dtype, heads):
+def _freeze(model, dtype, heads, precision="fp16", amax=None):
     from . import networks
     if dtype != torch.float16:
-        raise NotImplementedError(f"freeze: dtype {dtype}: the engine is fp16 only")
+        raise NotImplementedError(f"freeze: dtype {dtype}: the engine is fp16 only (fp8: build_engine(precision='fp8'))")
+    if precision not in ("fp16", "fp8"):
+        raise ValueError(f"build_engine: precision {precision!r} (fp16 and fp8 are built)")
+    fp8 = precision == "fp8"
+    if fp8 and amax is None:
+        raise ValueError("build_engine: precision='fp8' needs amax, the {record name: absolute maximum} dict of "
+                         "deploy.calibrate on an fp16 engine of the same model")
     kinds = {getattr(networks, h).Seg_Model: h for h in heads}
     if type(model) not in kinds:
         raise NotImplementedError(f"freeze: {type(model).__module__}.{type(model).__name__} is not supported "
                                   f"({' and '.join('networks.' + h for h in heads)} are" +
                                   ("; deploy.build_engine freezes every head)" if len(heads) == 2 else ")"))
     kind = kinds[type(model)]
+    if fp8 and kind not in ("simple", "deeplabv3"):
+        raise NotImplementedError(f"build_engine: precision='fp8' is not built for networks.{kind}: its resize"
+                                  f"{' and pyramid' if kind == 'psp' else ''} nodes are fp16 (simple and deeplabv3 are)")
     if model.training:
         raise RuntimeError("freeze: the model is in training mode; call model.eval() first (BatchNorm is folded from "
                            "its running statistics)")
     own = {"simple": ("last_conv",), "deeplabv3": ("aspp", "last_conv"), "deeplabv3p": ("aspp", "decoder"),
            "psp": ("ppm", "last_conv")}[kind]
-    pl = _Planner()
+    pl = _Planner(fp8)
     with torch.no_grad():
-        x = pl.buffer([(0, 3)])                     # buffer 0: the converted input image
+        x = pl.buffer([(0, 3)], fmt="f16")          # buffer 0: the converted input image
         for name, _ in model.named_children():
             if name not in ("backbone", "conv_deepsup", "criterion") + own:
                 raise NotImplementedError(f"freeze: module {name} of {type(model).__module__}")
@@ -296,7 +419,12 @@ def _freeze(model, dtype, heads):
         raise NotImplementedError("freeze: last_conv does not end in a classifier conv with a bias")
     meta = {"align_corner": bool(model.align_corner), "num_classes": int(pl.records[-1]["cout"]), "in_channels": 3,
             "dtype": "float16", "model": kind}
-    return Engine({"format": FORMAT, "meta": meta, "plan": pl.records, "buffers": list(pl.pitch), "tensors": pl.tensors})
+    if not fp8:
+        return Engine({"format": FORMAT, "meta": meta, "plan": pl.records, "buffers": list(pl.pitch), "tensors": pl.tensors})
+    pl.finalize_f8(amax)
+    meta["dtype"] = "float8_e4m3fn"
+    return Engine({"format": FORMAT_F8, "meta": meta, "plan": pl.records, "buffers": list(pl.pitch),
+                   "buffer_fmt": list(pl.fmt), "scales": list(pl.scales), "tensors": pl.tensors})
 
 
 def freeze(model, dtype=torch.float16):
@@ -308,12 +436,28 @@ def freeze(model, dtype=torch.float16):
     return _freeze(model, dtype, ("deeplabv3", "simple"))
 
 
-def build_engine(model, dtype=torch.float16):
+def build_engine(model, dtype=torch.float16, precision="fp16", amax=None):
     """Freeze an eval-mode Seg_Model of networks.simple / deeplabv3 / deeplabv3p / psp into an Engine (on the CPU;
     .to(device) or load_engine(state, device) puts it on the GPU).  conv_deepsup is dropped.  What the planner does not
     know - a pyramid size outside 1 .. 8, more than 4 stages, a stage conv that is not a bias-free 1x1 - raises
-    NotImplementedError naming the module."""
-    return _freeze(model, dtype, ("deeplabv3", "simple", "deeplabv3p", "psp"))
+    NotImplementedError naming the module.
+
+    precision="fp8" (networks.simple and deeplabv3; opt-in) builds the calibrated e4m3 engine: `amax`
+    is the {record name: absolute maximum of that record's output} dict of deploy.calibrate(fp16 engine, batches); a
+    record it lacks raises KeyError naming it.  The conv that reads the image and the image-pool branch stay fp16."""
+    return _freeze(model, dtype, ("deeplabv3", "simple", "deeplabv3p", "psp"), precision, amax)
+
+
+def calibrate(engine, batches):
+    """{record name: absolute maximum of what that record wrote} of an fp16 engine on the device over an iterable of
+    float32 [N,3,H,W] images: the `amax` of build_engine(precision="fp8").  Maxima across the batches."""
+    if engine.format != FORMAT:
+        raise ValueError("calibrate: the calibration run is made on an fp16 engine")
+    amax = {}
+    for image in batches:
+        for name, t in engine.trace(image.to(engine.device)).items():
+            amax[name] = max(amax.get(name, 0.0), float(t.float().abs().amax()))
+    return amax
 
 
 def load_engine(path_or_dict, device=None):
@@ -326,16 +470,20 @@ def load_engine(path_or_dict, device=None):
 
 
 class Engine:
-    """A frozen fp16 inference program.  Holds the plan, the packed tensors and, per device, a pool of activation
+    """A frozen fp16 (format 1) or fp8 (format 2) inference program.  Holds the plan, the packed tensors and, per device, a pool of activation
     slots: buffers whose lifetimes do not overlap share a slot, a slot grows to the largest tenant seen, and the
     per-input-shape launch list is built once and reused."""
 
     def __init__(self, state):
-        if state.get("format") != FORMAT:
-            raise ValueError(f"engine format {state.get('format')}: this build reads format {FORMAT}")
+        if state.get("format") not in (FORMAT, FORMAT_F8):
+            raise ValueError(f"engine format {state.get('format')}: this build reads formats {FORMAT} and {FORMAT_F8}")
+        self.format = state["format"]
         self.meta = dict(state["meta"])
         self.plan = [dict(r) for r in state["plan"]]
         self.buffers = list(state["buffers"])
+        # format 2: the storage format of every buffer ("f16" / "f8") and its scale (real value = stored value * scale)
+        self.buffer_fmt = list(state["buffer_fmt"]) if self.format == FORMAT_F8 else ["f16"] * len(self.buffers)
+        self.scales = list(state["scales"]) if self.format == FORMAT_F8 else [1.0] * len(self.buffers)
         self.tensors = list(state["tensors"])
         self.align_corner = self.meta["align_corner"]
         self.num_classes = self.meta["num_classes"]
@@ -363,8 +511,11 @@ class Engine:
     # ---- persistence / placement
     def state_dict(self):
         """Tensors and plain Python containers only: the plan plus the packed tensors (on the CPU)."""
-        return {"format": FORMAT, "meta": dict(self.meta), "plan": [dict(r) for r in self.plan],
-                "buffers": list(self.buffers), "tensors": [t.detach().cpu() for t in self.tensors]}
+        state = {"format": self.format, "meta": dict(self.meta), "plan": [dict(r) for r in self.plan],
+                 "buffers": list(self.buffers), "tensors": [t.detach().cpu() for t in self.tensors]}
+        if self.format == FORMAT_F8:
+            state.update(buffer_fmt=list(self.buffer_fmt), scales=list(self.scales))
+        return state
 
     def to(self, device):
         device = torch.device(device)
@@ -398,6 +549,8 @@ class Engine:
                     if hw.setdefault(b, (s, s)) != (s, s):
                         raise RuntimeError(f"deploy.Engine: {r['name']} writes {(s, s)} into a {hw[b]} buffer")
                 o = (r["sizes"][0],) * 2
+            elif r["op"] == "cast":
+                o = (h, w)
             elif r["op"] in ("broadcast", "resize"):   # the destination's own size
                 if r["dst"] not in hw:
                     raise RuntimeError(f"deploy.Engine: {r['name']} writes a buffer of unknown size")
@@ -424,7 +577,7 @@ class Engine:
         for b, (h, w) in hw.items():
             if b >= 0:
                 s = self._slot_of[b]
-                need[s] = max(need[s], N * h * w * self.buffers[b] * 2)
+                need[s] = max(need[s], N * h * w * self.buffers[b] * _ESIZE[self.buffer_fmt[b]])
         grown = False
         for s, n in enumerate(need):
             if self._slots[s] is None or self._slots[s].numel() < n:
@@ -457,7 +610,42 @@ class Engine:
         for i, r in enumerate(self.plan):
             h, w = hw[r["src"]]
             name = r["name"]
-            if r["op"] == "conv":
+            f8 = r.get("fmt") == "f8"
+            if r["op"] == "conv" and f8:
+                ho, wo = hw[r["dst"]]
+                f32 = r["f32"]
+                d = _lib.ConvF8Desc(N, h, w, r["cin8"], self.buffers[r["src"]], r["cout"], r["k"], r["stride"], r["pad"],
+                                    r["dil"], ho, wo, 0 if f32 else self.buffers[r["dst"]], r["y_off"],
+                                    self.buffers[r["res"]] if r["res"] >= 0 else 0, 0, int(r["relu"]), r["res_mul"])
+                descs.append(d)
+                wt, mul, add = (C.c_void_p(self.tensors[r[k]].data_ptr()) for k in ("w", "mul", "add"))
+                if f32:
+                    out_shape = (N, r["cout"], ho, wo)
+                    out_call = (name, L.dcfp_conv2d_fwd_f8_nhwc_to_f32_nchw, (C.byref(d), ptr(r["src"]), wt, mul, add))
+                else:
+                    calls.append((name, L.dcfp_conv2d_fwd_f8_nhwc,
+                                  (C.byref(d), ptr(r["src"]), wt, mul, add,
+                                   ptr(r["res"]) if r["res"] >= 0 else None, ptr(r["dst"]))))
+            elif r["op"] == "cast":
+                calls.append((name, L.dcfp_cast_nhwc_f16_to_f8,
+                              (ptr(r["src"]), self.buffers[r["src"]], ptr(r["dst"]), self.buffers[r["dst"]], r["y_off"],
+                               N * h * w, r["c"], r["scale"])))
+            elif r["op"] == "maxpool" and f8:
+                ho, wo = hw[r["dst"]]
+                calls.append((name, L.dcfp_maxpool3x3s2_nhwc_f8,
+                              (ptr(r["src"]), ptr(r["dst"]), N, h, w, self.buffers[r["src"]], self.buffers[r["src"]],
+                               ho, wo, self.buffers[r["dst"]])))
+            elif r["op"] == "avgpool" and f8:
+                c16 = self.buffers[r["src"]]
+                calls.append((name, L.dcfp_avgpool_nhwc_f8_to_f16,
+                              (ptr(r["src"]), ptr(r["dst"]), N, h * w, c16, c16, self.buffers[r["dst"]], r["scale"],
+                               C.c_void_p(self._avg_ws.data_ptr()), ws_of[i])))
+            elif r["op"] == "broadcast" and f8:
+                ho, wo = hw[r["dst"]]
+                calls.append((name, L.dcfp_broadcast_nhwc_f16_to_f8,
+                              (ptr(r["src"]), self.buffers[r["src"]], ptr(r["dst"]), N, ho * wo, r["c"],
+                               self.buffers[r["dst"]], r["y_off"], r["scale"])))
+            elif r["op"] == "conv":
                 ho, wo = hw[r["dst"]]
                 f32 = r["f32"]
                 d = _lib.ConvF16Desc(N, h, w, r["cin8"], self.buffers[r["src"]], r["cout"] if f32 else _r8(r["cout"]),
@@ -510,9 +698,7 @@ class Engine:
         self._programs[key] = prog
         return prog
 
-    @torch.no_grad()
-    def lowres_logits(self, image, deepsup=False):
-        """[fp32 N x classes x h x w logits at 1/os resolution] (the deep-supervision head is not part of an engine)."""
+    def _check_image(self, image):
         if self.device.type != "cuda" or not isinstance(image, torch.Tensor) or not image.is_cuda:
             raise RuntimeError("deploy.Engine runs on the MI355X HIP kernels only: engine.to('cuda') and a CUDA image "
                                "(no CPU fallback exists)")
@@ -520,22 +706,72 @@ class Engine:
             raise RuntimeError(f"deploy.Engine: the engine is on {self.device}, the image on {image.device}")
         if image.dtype != torch.float32 or image.dim() != 4 or image.shape[1] != self.meta["in_channels"]:
             raise RuntimeError(f"deploy.Engine: image must be float32 [N,{self.meta['in_channels']},H,W]")
+
+    @torch.no_grad()
+    def lowres_logits(self, image, deepsup=False):
+        """[fp32 N x classes x h x w logits at 1/os resolution] (the deep-supervision head is not part of an engine)."""
+        self._check_image(image)
         image = image.contiguous()
         N, Cc, H, W = image.shape
         with torch.cuda.device(self.device):         # (the launches go to the engine's device and its current stream)
             return self._run(image, N, Cc, H, W)
 
-    def _run(self, image, N, Cc, H, W):
+    def _run(self, image, N, Cc, H, W, tap=None):
         _, calls, out_call, out_shape, _, in_ptr = self._program(N, H, W)
         L, stream = _lib.lib(), ops._stream()
         check(L.dcfp_nchw_f32_to_nhwc_f16(C.c_void_p(image.data_ptr()), in_ptr, N, Cc, H, W, self.buffers[0], stream),
               "deploy: input conversion")
-        for name, fn, args in calls:
+        for i, (name, fn, args) in enumerate(calls):
             check(fn(*args, stream), "deploy: " + name)
+            if tap is not None:
+                tap(i)
         out = torch.empty(out_shape, dtype=torch.float32, device=image.device)
         name, fn, args = out_call
         check(fn(*args, C.c_void_p(out.data_ptr()), stream), "deploy: " + name)
         return [out]
+
+    def _buffer_view(self, b, N, hw):
+        """Buffer b of the current program as an [N, h, w, pitch] tensor of its storage dtype (a view of its slot)."""
+        h, w = hw[b]
+        fmt = self.buffer_fmt[b]
+        raw = self._slots[self._slot_of[b]][:N * h * w * self.buffers[b] * _ESIZE[fmt]]
+        return raw.view(F8 if fmt == "f8" else torch.float16).view(N, h, w, self.buffers[b])
+
+    def _written(self, r, N, hw):
+        """The bytes record r wrote: its channel slice of its destination buffer."""
+        if r["op"] == "pyramid":
+            return torch.cat([self._buffer_view(b, N, hw).reshape(-1) for b in r["dsts"]])
+        y = self._buffer_view(r["dst"], N, hw)
+        g = _GRAN[self.buffer_fmt[r["dst"]]]
+        if r["op"] == "conv":
+            return y[..., r["y_off"]:r["y_off"] + _rg(r["cout"], g)]
+        if r["op"] in ("broadcast", "resize"):
+            width = _rg(r["c"], g) if "c" in r else self.buffers[r["src"]]
+            return y[..., r["y_off"]:r["y_off"] + width]
+        return y
+
+    @torch.no_grad()
+    def trace(self, image):
+        """{record name: a clone of the bytes that record wrote} of one run, in the stored dtype (fp16 / e4m3 NHWC
+        slices; the classifier's fp32 NCHW logits), plus "input": the converted image.  A debugging and testing path:
+        it runs the launch list with a clone after each call."""
+        self._check_image(image)
+        image = image.contiguous()
+        N, Cc, H, W = image.shape
+        out = {}
+        with torch.cuda.device(self.device):
+            self._program(N, H, W)                   # (sizes the slots before any view of them is taken)
+            hw = self.buffer_shapes(H, W)
+            recs = [r for r in self.plan if not (r["op"] == "conv" and r["f32"])]
+            last = [r for r in self.plan if r["op"] == "conv" and r["f32"]][-1]
+
+            def tap(i):
+                if i == 0:
+                    out["input"] = self._buffer_view(0, N, hw).clone()
+                out[recs[i]["name"]] = self._written(recs[i], N, hw).clone()
+            logits = self._run(image, N, Cc, H, W, tap)[0]
+        out[last["name"]] = logits
+        return out
 
     @torch.no_grad()
     def __call__(self, image, labels=None, deepsup=False):

@@ -743,6 +743,47 @@ int dcfp_pyramid_pool_nhwc_f16(const void* x, int N, int H, int W, int C8, int x
                                const int* sizes, void* const* y, const int* y_pitch, void* workspace,
                                size_t workspace_bytes, dcfp_stream_t stream);
 
+/* ------------------------------------------------- fp8 deployment engine (conv_f8.hip)
+ * The calibrated 8-bit inference path of dcfp_amd/deploy.py (build_engine(precision="fp8")).  Every 8-bit value is OCP
+ * e4m3fn; every conversion to it clamps the fp32 value to [-448, 448] and rounds to nearest even (subnormals kept).
+ * Activations are NHWC fp8 with a channel pitch that is a multiple of 16; weights are packed once as
+ * [Cout8][KH][KW][Cin16] fp8 (zero rows / columns in the padding); accumulation is fp32 on the fp8 matrix cores.
+ *   y[n, oy, ox, y_off + co] = fp8(relu?(acc * mul[co] + add[co] (+ res_mul * residual[n, oy, ox, res_off + co])))
+ * for co < Cout, and exact zeros for co = Cout .. Cout16-1 (Cout16 = Cout rounded up to 16).  mul and add hold Cout
+ * rounded up to 8 floats.  Geometry, alignment and size limits are those of DcfpConvF16Desc. */
+typedef struct DcfpConvF8Desc {
+    int32_t N, H, W;            /* input  [N,H,W,x_pitch], channels 0 .. Cin16-1 read                   */
+    int32_t Cin16, x_pitch;     /* multiples of 16                                                     */
+    int32_t Cout;               /* the true output channel count (w_packed has Cout rounded up to 8 rows) */
+    int32_t K, stride, pad, dil;
+    int32_t Hout, Wout;         /* (H + 2*pad - dil*(K-1) - 1)/stride + 1                               */
+    int32_t y_pitch, y_off;     /* fp8 output: channel pitch and first channel (multiples of 16)        */
+    int32_t res_pitch, res_off; /* residual (fp8 NHWC at the output's resolution), when given           */
+    int32_t relu;
+    float res_mul;              /* residual scale / output scale                                        */
+} DcfpConvF8Desc;
+int dcfp_conv2d_fwd_f8_nhwc(const DcfpConvF8Desc* d, const void* x, const void* w_packed, const float* mul,
+                            const float* add, const void* residual /* nullable */, void* y, dcfp_stream_t stream);
+/* The classifier's epilogue: y fp32 NCHW dense [N, Cout, Hout, Wout] = acc * mul + add (no clamp, ReLU or residual;
+ * y_*, res_* and relu of the descriptor are ignored). */
+int dcfp_conv2d_fwd_f8_nhwc_to_f32_nchw(const DcfpConvF8Desc* d, const void* x, const void* w_packed, const float* mul,
+                                        const float* add, float* y, dcfp_stream_t stream);
+/* y[p, y_off + c] = fp8(x[p, c] * scale) for the P pixels of an fp16 NHWC buffer and c < C; channels C .. C16-1 of the
+ * slice are zero, bytes of y outside it are not touched.  x_pitch: a multiple of 8, >= C rounded up to 8. */
+int dcfp_cast_nhwc_f16_to_f8(const void* x, int x_pitch, void* y, int y_pitch, int y_off, int64_t P, int C,
+                             float scale, dcfp_stream_t stream);
+/* nn.MaxPool2d(3, 2, 1) on NHWC fp8: compares the decoded values, exact. */
+int dcfp_maxpool3x3s2_nhwc_f8(const void* x, void* y, int N, int H, int W, int C16, int x_pitch, int Ho, int Wo,
+                              int y_pitch, dcfp_stream_t stream);
+/* nn.AdaptiveAvgPool2d(1) from NHWC fp8 to an fp16 vector: y[n, c] = fp16(mean over the HW pixels of x[n, :, c] * scale),
+ * summed in fp32 in a fixed order.  workspace: dcfp_avgpool_nhwc_f16_workspace_bytes(N, C16, HW). */
+int dcfp_avgpool_nhwc_f8_to_f16(const void* x, void* y, int N, int64_t HW, int C16, int x_pitch, int y_pitch,
+                                float scale, void* workspace, size_t workspace_bytes, dcfp_stream_t stream);
+/* y[n, p, y_off + c] = fp8(v[n, c] * scale) for the HW pixels p and c < C of an fp16 vector v (rows v_pitch apart, a
+ * multiple of 8); channels C .. C16-1 of the slice are zero, bytes of y outside it are not touched. */
+int dcfp_broadcast_nhwc_f16_to_f8(const void* v, int v_pitch, void* y, int N, int64_t HW, int C, int y_pitch,
+                                  int y_off, float scale, dcfp_stream_t stream);
+
 /* ------------------------------------------------- label maps as PNG streams (png.hip)
  * pred int32 [N,H,W] and P lookup tables uint8 [P][256] (1 <= P <= 4) -> N*P finished zlib streams, stream n*P + p
  * holding the 8-bit image lut[p][pred[n] & 255]: filter type Up on every row, one fixed-Huffman deflate block and an

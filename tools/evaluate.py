@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Evaluation driver — the command line and protocol of the reference's evaluate.py main() (evaluate.py:249-393): build
-the (optionally slimmed, optionally frozen-to-fp16) model, predict batch by batch, accumulate the confusion matrix on
+the (optionally slimmed, optionally frozen-to-fp16) model - or load a saved fp16 / fp8 engine (`--engine-file`) - predict batch by batch, accumulate the confusion matrix on
 the device, print {'meanIU', 'IU_array'} and append IoU / precision / recall / FPS to result.txt in the snapshot
 directory.  `--iou-type boundary` scores class boundaries only.
 
@@ -54,6 +54,8 @@ def get_parser():
     p.add_argument("--restore-from", type=str, default=None)
     p.add_argument("--channel-cfg", type=str, default=None, help="path to channel_cfg.")
     p.add_argument("--use-trt", type=str2bool, default="False", help="evaluate through the frozen fp16 engine")
+    p.add_argument("--engine-file", type=str, default=None,
+                   help="evaluate through an engine saved by tools/deploy.py (fp16 or fp8); no model is built")
     p.add_argument("--num-classes", type=int, default=19)
     p.add_argument("--num-images", type=int, default=40)
     p.add_argument("--seed", type=int, default=12345)
@@ -119,6 +121,15 @@ def build_model(args):
     return model.eval()
 
 
+def load_engine_file(args, device):
+    """The saved engine of --engine-file on `device`; its class count and align_corner replace the command line's."""
+    engine = deploy.load_engine(args.engine_file, device)
+    args.num_classes, args.align_corner = engine.num_classes, engine.align_corner
+    print(f"engine {args.engine_file}: format {engine.format}, {engine.meta['dtype']}, {engine.meta['model']}, "
+          f"{len(engine.plan)} layer records", flush=True)
+    return engine
+
+
 def predict_batch(model, image, args, scales, fused, size, label=None, conf=None):
     """One batch of a dataset through the prediction branch the command line selects (module docstring).  image: as
     the loader served it; size: the files' own (H, W).  With `label` and `conf`, and where the branch allows it, the
@@ -162,11 +173,14 @@ def main(argv=None):
     args = parser.parse_args(argv)
     h, w = map(int, args.input_size.split(","))
     scales = [float(s) for s in args.ms.split(",")]
-    C = args.num_classes
     device = torch.device("cuda:0")
     torch.manual_seed(args.seed)
-    model = build_model(args)
-    model = deploy.build_engine(model).to(device) if args.use_trt else model.to(device)
+    if args.engine_file:
+        model = load_engine_file(args, device)
+    else:
+        model = build_model(args)
+        model = deploy.build_engine(model).to(device) if args.use_trt else model.to(device)
+    C = args.num_classes
     dataset = SyntheticSegDataset(C, args.ignore_label, (h, w), args.seed)
     boundary = args.iou_type == "boundary"
     conf = torch.zeros((C, C + 1 if boundary else C), dtype=torch.int64, device=device)
@@ -252,8 +266,13 @@ def main_dataset(parser, argv=None):
         C = args.num_classes = dataset.num_classes
         loader = EvalLoader(dataset, max(1, args.batch_size // world), device, num_workers=args.num_workers,
                             rank=rank, world_size=world)
-        model = build_model(args)
-        model = deploy.build_engine(model).to(device) if args.use_trt else model.to(device)
+        if args.engine_file:
+            model = load_engine_file(args, device)
+            if model.num_classes != dataset.num_classes:
+                raise ValueError(f"--engine-file has {model.num_classes} classes, the dataset {dataset.num_classes}")
+        else:
+            model = build_model(args)
+            model = deploy.build_engine(model).to(device) if args.use_trt else model.to(device)
         palette = [int(v) for v in dataset.cmap_labels.reshape(-1)]
         save_path = os.path.join(args.snapshot_dir, "outputs")
         if args.save_predict:
