@@ -210,6 +210,8 @@ SIGNATURES = {
     "dcfp_resize_bilinear_nhwc_f16": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P]),
     "dcfp_pyramid_pool_nhwc_f16_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _P]),
     "dcfp_pyramid_pool_nhwc_f16": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
+    "dcfp_kd_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
+    "dcfp_kd_fwd_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _P, _Z, _P, _P, _P]),
 }
 
 

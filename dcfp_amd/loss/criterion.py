@@ -26,6 +26,8 @@ def build_criterion(loss_type, dataset, loss_para):
         cls = CriterionOhemDSN
     elif loss_type == "gsrl":
         cls = CriterionGsrlDSN
+    elif loss_type == "kd":
+        cls = CriterionKD
     else:
         raise NotImplementedError(loss_type)
     return cls(dataset=dataset, **loss_para)
@@ -135,3 +137,37 @@ class CriterionGsrlDSN(nn.Module):
 
     def forward(self, preds, labels):
         return self.forward_lowres(list(preds), labels, labels["ori"].shape[-2:], True)
+
+
+class CriterionKD(nn.Module):
+    """Distillation term of the fine-tune stage: kd_weight * ops.kd_loss(main-head logits, teacher logits) at the
+    heads' low resolution.  The teacher's logits travel with the labels, as labels['teacher']
+    (distill.Teacher makes them, tools/train.py --teacher-from puts them there); the deep-supervision head is not
+    distilled.  kd_mode "pixel": KL over the classes per pixel; "channel": KL over the positions per class plane.
+    Combined with a supervised loss as `--loss-type ce,kd` / `gsrl,kd`."""
+
+    def __init__(self, dataset=None, kd_weight=1.0, kd_T=1.0, kd_mode="pixel", **kwargs):
+        super().__init__()
+        if kd_mode not in ops.KD_MODES:
+            raise ValueError(f"CriterionKD: kd_mode {kd_mode!r} is not one of {sorted(ops.KD_MODES)}")
+        if not float(kd_T) > 0.0:
+            raise ValueError(f"CriterionKD: kd_T must be positive, got {kd_T}")
+        self.kd_weight, self.kd_T, self.kd_mode = float(kd_weight), float(kd_T), kd_mode
+
+    def _term(self, student, labels):
+        if not isinstance(labels, dict) or "teacher" not in labels:
+            raise ValueError("CriterionKD: labels must be a dict that holds the teacher's low-resolution logits under "
+                             "'teacher' (distill.Teacher; tools/train.py --teacher-from)")
+        teacher = labels["teacher"]
+        if tuple(teacher.shape) != tuple(student.shape):
+            raise ValueError(f"CriterionKD: the teacher's logits {tuple(teacher.shape)} and the student's "
+                             f"{tuple(student.shape)} differ in shape")
+        return {"loss": self.kd_weight * ops.kd_loss(student, teacher, self.kd_T, self.kd_mode)}
+
+    def forward_lowres(self, preds, labels, size, align_corner):
+        return self._term(preds[0], labels)
+
+    def forward(self, preds, labels):
+        if isinstance(preds, dict):
+            preds = [preds["pred"]]
+        return self._term(preds[0], labels)

@@ -1899,6 +1899,56 @@ def upsample_weighted_ce(logits, labels, pix_weight, size, align_corners, ignore
                                ignore_index)
 
 
+# ------------------------------------------------------------------ knowledge distillation
+KD_MODES = {"pixel": 0, "channel": 1}      # DCFP_KD_PIXEL / DCFP_KD_CHANNEL of include/dcfp_hip.h
+
+
+class KDLossFn(torch.autograd.Function):
+    """T^2-scaled KL(teacher || student) of the temperature-softened logits (kd.hip): over the classes at
+    every pixel ("pixel") or over the positions of every (n, c) plane ("channel").  The forward launch also writes
+    dL/dstudent, so backward is grad_output x that tensor; the teacher gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, student, teacher, T, mode):
+        s, t = student.contiguous(), teacher.contiguous()
+        N, Cc, h, w = s.shape
+        L = _lib.lib()
+        ws = _workspace("kd", L.dcfp_kd_workspace_bytes(mode, N, Cc, h, w), s.device)
+        out = torch.empty(1, dtype=torch.float32, device=s.device)
+        dl = torch.empty_like(s) if ctx.needs_input_grad[0] else None
+        check(L.dcfp_kd_fwd_f32(_p(s), _p(t), mode, N, Cc, h, w, T, _p(ws), ws.numel(), _p(out), _p(dl), _stream()),
+              "kd_fwd")
+        ctx.save_for_backward(dl)
+        return out.reshape(())
+
+    @staticmethod
+    def backward(ctx, gout):
+        dl, = ctx.saved_tensors
+        return dl * gout, None, None, None
+
+
+def kd_loss(student, teacher, T=1.0, mode="pixel"):
+    """Distillation loss between the fp32 [N,C,h,w] logits of a student and a frozen teacher, a 0-dim tensor:
+         pixel:    T^2/(N h w) * sum_pixels KL(softmax_c(teacher/T) || softmax_c(student/T))
+         channel:  T^2/(N C)   * sum_planes KL(softmax_yx(teacher/T) || softmax_yx(student/T))
+    The gradient goes to `student` only; a teacher that requires grad is an error (detach it)."""
+    _require(student, "student")
+    _require(teacher, "teacher")
+    if teacher.requires_grad:
+        raise RuntimeError("kd_loss: the teacher's logits must not require grad (run the teacher under no_grad)")
+    if student.dim() != 4 or tuple(student.shape) != tuple(teacher.shape):
+        raise RuntimeError(f"kd_loss: student {tuple(student.shape)} and teacher {tuple(teacher.shape)} must be the "
+                           "same [N,C,h,w]")
+    if student.device != teacher.device:
+        raise RuntimeError(f"kd_loss: student on {student.device}, teacher on {teacher.device}")
+    if mode not in KD_MODES:
+        raise ValueError(f"kd_loss: mode {mode!r} is not one of {sorted(KD_MODES)}")
+    T = float(T)
+    if not (T > 0.0 and T != float("inf")):
+        raise ValueError(f"kd_loss: the temperature must be a finite positive number, got {T}")
+    return KDLossFn.apply(student, teacher, T, KD_MODES[mode])
+
+
 # ------------------------------------------------------------------ inference / evaluation
 def conv2d_fused_infer(x, w, scale, shift, stride=1, pad=0, dil=1, residual=None, relu=False):
     """y = act(conv(x,w)*scale[co] + shift[co] (+ residual)): conv with an eval-mode BatchNorm

@@ -802,6 +802,27 @@ int dcfp_png_deflate_labels_i32(const int32_t* pred, int N, int H, int W, const 
                                 size_t out_bytes, int64_t* offsets, int64_t* lengths, void* workspace,
                                 size_t workspace_bytes, dcfp_stream_t stream);
 
+/* ------------------------------------------------- knowledge-distillation losses (kd.hip)
+ * s (student), t (teacher): fp32 NCHW [N,C,h,w], contiguous, finite; T > 0 the temperature, x' = x / T.
+ *   DCFP_KD_PIXEL    L = T^2/(N h w) * sum over pixels of KL(softmax_c(t') || softmax_c(s'))
+ *                    dL/ds = T/(N h w) * (softmax_c(s') - softmax_c(t'))
+ *   DCFP_KD_CHANNEL  L = T^2/(N C) * sum over (n, c) planes of KL(softmax_yx(t') || softmax_yx(s'))
+ *                    dL/ds = T/(N C) * (softmax_yx(s') - softmax_yx(t'))
+ * fp32 with the maximum subtracted before every exponential.  One launch writes the per-block sums of KL to the
+ * workspace and, when dlogits (nullable, [N,C,h,w]) is given, the gradient; a second adds the partials in fp64 in a
+ * fixed order into *loss_out.  No atomics: two calls on the same inputs leave the same bits.  C == 1 (pixel) and
+ * h*w == 1 (channel) give loss 0 and gradient 0 exactly, and so does t == s.
+ *   dcfp_kd_workspace_bytes: the workspace of a call (4-byte aligned; 0 for arguments the call refuses).
+ * Null s / t / loss_out, sizes < 1, T <= 0 or not finite and an unknown mode are DCFP_E_BADDESC; a workspace that is
+ * null or too small is DCFP_E_WORKSPACE; more than 2^31 - 1 blocks DCFP_E_UNSUPPORTED.  All of it is checked before
+ * any HIP call. */
+#define DCFP_KD_PIXEL 0
+#define DCFP_KD_CHANNEL 1
+size_t dcfp_kd_workspace_bytes(int mode, int N, int C, int h, int w);
+int dcfp_kd_fwd_f32(const float* s, const float* t, int mode, int N, int C, int h, int w, float T, void* workspace,
+                    size_t workspace_bytes, float* loss_out /* device scalar */, float* dlogits /* may be null */,
+                    dcfp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,7 @@ import torch  # noqa: E402
 from dcfp_amd import networks  # noqa: E402
 from dcfp_amd.pruners import init_pruned_model  # noqa: E402
 from dcfp_amd.pruners.dcfp_pruner import DCFPPruner  # noqa: E402
+from dcfp_amd.pruners.random_pruner import RandomChannelPruner  # noqa: E402
 from dcfp_amd.utils.flops_counter import get_model_complexity_info  # noqa: E402
 from dcfp_amd.utils.pyt_utils import load_model  # noqa: E402
 
@@ -42,6 +43,9 @@ def get_parser():
     p.add_argument("--model-para", type=str, default="{}")
     p.add_argument("--align-corner", type=str2bool, default="True")
     p.add_argument("--dataset", type=str, default="CS")
+    p.add_argument("--prune-type", type=str, default="dcfp", choices=["dcfp", "random"],
+                   help="dcfp: the scores of --score-path; random: the baseline that ignores the weights")
+    p.add_argument("--prune-seed", type=int, default=None, help="--prune-type random: seed of the draw")
     return p
 
 
@@ -68,7 +72,10 @@ def main(argv=None):
     load_model(seg_model, args.model_path)
     global_percent = args.start_global_percent
     while True:
-        pruner = DCFPPruner(global_percent=global_percent, layer_keep=0.02, score_file=args.score_path)
+        if args.prune_type == "random":
+            pruner = RandomChannelPruner(global_percent=global_percent, layer_keep=0.02, seed=args.prune_seed)
+        else:
+            pruner = DCFPPruner(global_percent=global_percent, layer_keep=0.02, score_file=args.score_path)
         sub_model, channel_cfg = pruner.prune_model(copy.deepcopy(seg_model), except_start_keys=["conv_deepsup"])
         torch.save(sub_model.state_dict(), os.path.join(args.save_path, "pruned.pth"))
         torch.save(channel_cfg, os.path.join(args.save_path, "channel_cfg.pth"))

@@ -3,6 +3,7 @@
 the model / optimiser / loss / pruning options).  Without --dataset it runs over SYNTHETIC Cityscapes-shaped
 batches; with --dataset CS|CTX|COCO (and the reference's data flags) it reads a list file through dcfp_amd.datasets,
 whose augmentation chain runs on the device (ADE is not built).
+`--loss-type ...,kd --teacher-from CKPT` adds the distillation term against a frozen teacher.
 One process per GPU: `python -m torch.distributed.run --nproc-per-node N tools/train.py ...`."""
 import argparse
 import json
@@ -61,6 +62,12 @@ def get_parser():
     p.add_argument("--loss-para", type=str, default="{}")
     p.add_argument("--prune-type", type=str, default=None)
     p.add_argument("--channel-cfg", type=str, default=None)
+    p.add_argument("--teacher-from", type=str, default=None,
+                   help="checkpoint of the frozen teacher of --loss-type ...,kd: same --model, --backbone and classes as "
+                        "the student, built without --channel-cfg (the dense model the student was pruned from)")
+    p.add_argument("--teacher-engine", type=str2bool, default="True",
+                   help="freeze the teacher into the fp16 deployment engine (default) or keep the fp32 model")
+    p.add_argument("--teacher-channel-cfg", type=str, default=None, help="channel_cfg.pth of a teacher that is itself slim")
     p.add_argument("--dataset", type=str, default=None,
                    help="CS, CTX or COCO: read real data through dcfp_amd.datasets (default: synthetic batches)")
     p.add_argument("--data-dir", type=str, default="train", help="name of the data split (kept for the reference's scripts)")
@@ -94,12 +101,30 @@ class SyntheticDataset:
         return images.to(device, non_blocking=True), labels.to(device, non_blocking=True)
 
 
+def check_args(args):
+    """Argument combinations that cannot run, refused before anything is built."""
+    if "kd" in args.loss_type.split(",") and not args.teacher_from:
+        raise ValueError("--loss-type %s: the kd term needs a teacher, give --teacher-from CKPT" % args.loss_type)
+
+
+def build_teacher(args, num_classes, device):
+    """The frozen teacher of the kd term (dcfp_amd.distill): the student's architecture at the checkpoint's widths."""
+    from dcfp_amd.distill import Teacher
+    net = getattr(networks, args.model).Seg_Model(
+        backbone=args.backbone, backbone_para=json.loads(args.backbone_para), model_para=json.loads(args.model_para),
+        num_classes=num_classes, align_corner=args.align_corner, criterion=None, deepsup=args.deepsup)
+    if args.teacher_channel_cfg is not None:
+        pruners.init_pruned_model(net, torch.load(args.teacher_channel_cfg, weights_only=False))
+    return Teacher.from_checkpoint(net, args.teacher_from, engine=args.teacher_engine).to(device)
+
+
 def main(argv=None):
     parser = get_parser()
     if argv is not None:
         sys.argv = [sys.argv[0]] + list(argv)
     with Engine(custom_parser=parser) as engine:
         args = parser.parse_args()
+        check_args(args)
         main_flag = (not engine.distributed) or engine.local_rank == 0
         if main_flag:
             os.makedirs(args.snapshot_dir, exist_ok=True)
@@ -134,6 +159,9 @@ def main(argv=None):
         seg_model.to(device)
         optimizer = build_optimizer(args, seg_model)
         optimizer.zero_grad()
+        # (built after the optimizer and never handed to it: the teacher's parameters stay out of the arenas)
+        wants_kd = "kd" in args.loss_type.split(",")
+        teacher = build_teacher(args, dataset.num_classes, device) if wants_kd else None
         train_pruning = pruners.dcfp_pruning(seg_model, 0.999) if args.prune_type == "dcfp" else None
         model = engine.data_parallel(seg_model)
         model.train()
@@ -164,6 +192,9 @@ def main(argv=None):
                     raise ValueError("--loss-type gsrl on --dataset needs --balance 1 or 2 (the per-crop weights)")
                 # fine-tune stage: {'ori', 'weight'} labels (datasets/Base.py:73-89); --dataset with --balance brings real ones
                 labels = {"ori": labels, "weight": 1.0 + (labels % 3 == 0).float()}
+            if teacher is not None:
+                labels = dict(labels) if isinstance(labels, dict) else {"ori": labels}
+                labels["teacher"] = teacher(images)
             optimizer.zero_grad()
             lr = adjust_learning_rate(optimizer, args.learning_rate, it, args.num_steps, args.power, args.warmup)
             loss = model(images, labels, deepsup=args.deepsup)
