@@ -93,6 +93,14 @@ class VoteMap(C.Structure):
                [("weight", C.c_float)]
 
 
+class SlidePass(C.Structure):
+    """DcfpSlidePass: the low-resolution logits of the tiles of one (scale, flip) pass of a sliding-window vote."""
+    _fields_ = [("logits", C.c_void_p)] + \
+               [(n, C.c_int32) for n in ("lh", "lw", "hs", "ws", "th", "tw", "rows", "cols", "flip")] + \
+               [("weight", C.c_float)]
+
+
+SLIDE_MAX_PASSES, SLIDE_MAX_TILES_PER_AXIS = 16, 32    # DCFP_SLIDE_MAX_* of include/dcfp_hip.h
 AUG_SATURATION, AUG_HUE = 1, 2
 SGD_CHUNK = 16384
 CONV_FWD, CONV_DGRAD, CONV_WGRAD = 0, 1, 2
@@ -180,6 +188,8 @@ SIGNATURES = {
     "dcfp_upsample_argmax_f32": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "dcfp_confusion_matrix_i64": (_I, [_P, _P, _I, _L, _I, _P, _P]),
     "dcfp_vote_multiscale_f32": (_I, [C.POINTER(VoteMap), _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P]),
+    "dcfp_gather_tiles_f32": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P]),
+    "dcfp_vote_sliding_f32": (_I, [C.POINTER(SlidePass), _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P]),
     "dcfp_label_boundary_workspace_bytes": (_Z, [_I, _I, _I]),
     "dcfp_label_boundary_i32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _Z, _P]),
     "dcfp_label_boundary_i64": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _Z, _P]),

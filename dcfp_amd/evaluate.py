@@ -1,7 +1,8 @@
 """Evaluation helpers — the device-side half of evaluate.py:113-143,145-247,340-380: whole-image, sliding-window and
 multi-scale(+flip) prediction, on-device argmax and confusion matrix, mIoU.  Inference runs the
 conv kernels with the eval-mode BatchNorm folded into their epilogues (one kernel per
-conv+BN+ReLU); `predict_labels` and `predict_vote` never materialise the full-resolution logits."""
+conv+BN+ReLU); `predict_labels`, `predict_vote` and `predict_sliding_vote` never materialise the full-resolution
+logits."""
 import struct
 import zlib
 from concurrent.futures import ThreadPoolExecutor
@@ -110,6 +111,88 @@ def predict_vote(net, image, scales, flip, align_corner, out_hw=None, labels=Non
             maps.append((net.lowres_logits(torch.flip(img, [3]))[0], (hs, ws), True, weight))
     return ops.multiscale_vote(maps, (H_, W_), (H_, W_) if out_hw is None else out_hw, align_corner, labels=labels,
                                conf=conf, want_scores=want_scores, ignore_index=ignore_index)
+
+
+def sliding_tiles(h, w, tile_size):
+    """The tile grid of predict_sliding (evaluate.py:145-184) for an h x w image -> (ys, xs): tile t = r * len(xs) + c
+    covers [ys[r], min(ys[r] + tile_h, h)) x [xs[c], min(xs[c] + tile_w, w)).  The stride ceil(tile_h * 2/3) serves both
+    axes, as in the reference.  ValueError where the reference divides 0 by 0: a grid without tiles (an image much
+    smaller than the tile) and a pixel under no tile (tile_w below the stride with more than one column)."""
+    th, tw = int(tile_size[0]), int(tile_size[1])
+    h, w = int(h), int(w)
+    stride = ceil(th * (1 - 1 / 3))
+    rows = int(ceil((h - th) / stride) + 1)
+    cols = int(ceil((w - tw) / stride) + 1)
+    what = "sliding_tiles: a %d x %d image with %d x %d tiles (stride %d)" % (h, w, th, tw, stride)
+    if rows < 1 or cols < 1:
+        raise ValueError(what + " has %d x %d tiles: the image is too small for the tile" % (rows, cols))
+    ys = [max(min(r * stride + th, h) - th, 0) for r in range(rows)]
+    xs = [max(min(c * stride + tw, w) - tw, 0) for c in range(cols)]
+    for origins, extent, size in ((ys, th, h), (xs, tw, w)):
+        covered = 0
+        for o in origins:
+            if o > covered:
+                raise ValueError(what + " leaves pixels under no tile (from %d on along an axis of %d)" % (covered, size))
+            covered = max(covered, min(o + extent, size))
+        if covered < size:
+            raise ValueError(what + " leaves pixels under no tile (from %d on along an axis of %d)" % (covered, size))
+    return ys, xs
+
+
+# predict_sliding_vote's default tile_batch: as many tile pixels per network call as a whole-image batch of four
+# 1025 x 2049 images has - the activations the tools' default --batch-size 4 already asks for with --whole True
+TILE_PIXELS_PER_CALL = 4 * 1025 * 2049
+
+
+@torch.no_grad()
+def predict_sliding_vote(net, image, tile_size, scales, flip, align_corner, out_hw=None, labels=None, conf=None,
+                         want_scores=False, ignore_index=255, tile_batch=None):
+    """predict_multiscale(whole=False) + argmax (+ confusion matrix) without any full-resolution logits: per scale the
+    resized image is cut into the tiles of predict_sliding in one launch (and once more mirrored with `flip`), the
+    network runs on the stacked tiles, at most `tile_batch` tiles x N images per call, and its low-resolution logits go
+    into one [T,N,C,lh,lw] buffer per pass; then ONE ops.sliding_vote launch over all passes.  The other
+    arguments and the result are predict_vote's.  tile_batch bounds the peak memory of the network's activations; the
+    default keeps tiles x N x tile_h x tile_w within TILE_PIXELS_PER_CALL (769 x 769 tiles: 14 for one image, 3 for
+    four).  Batching changes the network's input shape only, not its arithmetic per image.  RuntimeError where a limit
+    of the launch is exceeded (ops.SLIDE_MAX_PASSES passes, ops.SLIDE_MAX_TILES_PER_AXIS tile rows / columns); ValueError from
+    sliding_tiles.  net: a Seg_Model or a deploy.Engine."""
+    _exec.require_device(image)
+    N_, _, H_, W_ = image.shape
+    th, tw = int(tile_size[0]), int(tile_size[1])
+    n_passes = len(scales) * (2 if flip else 1)
+    if not 1 <= n_passes <= ops.SLIDE_MAX_PASSES:
+        raise RuntimeError("predict_sliding_vote: %d scales%s are %d passes, one launch takes 1 .. %d (SLIDE_MAX_PASSES)"
+                           % (len(scales), " with flip" if flip else "", n_passes, ops.SLIDE_MAX_PASSES))
+    if tile_batch is None:
+        tile_batch = TILE_PIXELS_PER_CALL // (N_ * th * tw)
+    tile_batch = max(1, int(tile_batch))
+    passes = []
+    for scale in scales:
+        scale = float(scale)
+        hs, ws = int(H_ * scale), int(W_ * scale)
+        img = ops.upsample_bilinear(image, (hs, ws), align_corner)
+        ys, xs = sliding_tiles(hs, ws, (th, tw))
+        if max(len(ys), len(xs)) > ops.SLIDE_MAX_TILES_PER_AXIS:
+            raise RuntimeError("predict_sliding_vote: %d x %d tiles at scale %g, one launch takes %d per axis "
+                               "(SLIDE_MAX_TILES_PER_AXIS)" % (len(ys), len(xs), scale, ops.SLIDE_MAX_TILES_PER_AXIS))
+        T = len(ys) * len(xs)
+        weight = (0.5 if flip else 1.0) / len(scales)
+        for mirrored in ((False, True) if flip else (False,)):
+            tiles = ops.gather_tiles(img, ys, xs, (th, tw), mirrored)
+            logits = None
+            for t0 in range(0, T, tile_batch):
+                t1 = min(T, t0 + tile_batch)
+                low = net.lowres_logits(tiles[t0:t1].reshape((t1 - t0) * N_, tiles.shape[2], th, tw))[0]
+                if t0 == 0 and t1 == T:
+                    logits = low.reshape((T, N_) + tuple(low.shape[1:]))
+                    break
+                if logits is None:
+                    logits = torch.empty((T, N_) + tuple(low.shape[1:]), dtype=torch.float32, device=image.device)
+                logits[t0:t1] = low.reshape((t1 - t0, N_) + tuple(low.shape[1:]))
+            del tiles
+            passes.append((logits, (hs, ws), (th, tw), ys, xs, mirrored, weight))
+    return ops.sliding_vote(passes, (H_, W_), (H_, W_) if out_hw is None else out_hw, align_corner, labels=labels,
+                            conf=conf, want_scores=want_scores, ignore_index=ignore_index)
 
 
 def pad_inf_size(h, w, stride=8):

@@ -2049,6 +2049,109 @@ def multiscale_vote(maps, grid_hw, out_hw, align_corners, labels=None, conf=None
     return pred, scores
 
 
+SLIDE_MAX_PASSES, SLIDE_MAX_TILES_PER_AXIS = _lib.SLIDE_MAX_PASSES, _lib.SLIDE_MAX_TILES_PER_AXIS
+_SLIDE_TABLES, _SLIDE_TABLES_KEPT = {}, 1024
+
+
+def _origins(name, v, what):
+    v = [int(o) for o in v]
+    if not 1 <= len(v) <= SLIDE_MAX_TILES_PER_AXIS:
+        raise RuntimeError("%s: 1 .. %d tile %s expected, got %d" % (name, SLIDE_MAX_TILES_PER_AXIS, what, len(v)))
+    return v
+
+
+def gather_tiles(image, ys, xs, tile_size, flip=False):
+    """All len(ys) * len(xs) zero-padded tiles of image fp32 [N,ch,h,w] in one launch (csrc/slide.hip): tile
+    t = r * len(xs) + c is image[:, :, ys[r]:ys[r]+th, xs[c]:xs[c]+tw], cut at the image border and padded with zeros at
+    the bottom / right (evaluate.pad).  flip: the tiles of torch.flip(image, [3]), which is never formed.
+    -> fp32 [T,N,ch,th,tw]."""
+    _require(image, "image")
+    if image.dim() != 4:
+        raise RuntimeError("gather_tiles: image [N,ch,h,w] expected")
+    image = image.contiguous()
+    ys, xs = _origins("gather_tiles", ys, "rows"), _origins("gather_tiles", xs, "columns")
+    th, tw = int(tile_size[0]), int(tile_size[1])
+    N, ch, h, w = image.shape
+    tiles = torch.empty((len(ys) * len(xs), N, ch, th, tw), dtype=torch.float32, device=image.device)
+    with torch.cuda.device(image.device):
+        check(_lib.lib().dcfp_gather_tiles_f32(_p(image), N, ch, h, w, (C.c_int32 * len(ys))(*ys), len(ys),
+                                               (C.c_int32 * len(xs))(*xs), len(xs), th, tw, int(bool(flip)), _p(tiles),
+                                               _stream()), "gather_tiles")
+    return tiles
+
+
+def _slide_table(geometry, device):
+    """The origin table of a vote's passes, (host ctypes array, device int32 tensor of a few KB), kept per geometry,
+    device and stream: a call with a geometry seen before neither allocates nor copies, a new one (every new image size
+    of a dataset without a common size) costs one small host-to-device copy.  Keyed by the stream like _workspace, so
+    that the table is allocated on the stream that reads it and the allocator orders the reuse of an evicted one."""
+    key = (device.index, torch.cuda.current_stream().cuda_stream, geometry)
+    hit = _SLIDE_TABLES.get(key)
+    if hit is None:
+        stride = 2 * SLIDE_MAX_TILES_PER_AXIS
+        flat = [0] * (stride * len(geometry))
+        for k, (ys, xs) in enumerate(geometry):
+            flat[k * stride:k * stride + len(ys)] = ys
+            flat[k * stride + SLIDE_MAX_TILES_PER_AXIS:k * stride + SLIDE_MAX_TILES_PER_AXIS + len(xs)] = xs
+        if len(_SLIDE_TABLES) >= _SLIDE_TABLES_KEPT:       # (a dataset of many image sizes: the oldest one goes)
+            del _SLIDE_TABLES[next(iter(_SLIDE_TABLES))]
+        hit = _SLIDE_TABLES[key] = ((C.c_int32 * len(flat))(*flat), torch.tensor(flat, dtype=torch.int32, device=device))
+    return hit
+
+
+def sliding_vote(passes, grid_hw, out_hw, align_corners, labels=None, conf=None, want_scores=False, want_pred=True,
+                 ignore_index=255):
+    """The multi-scale + flip vote of evaluate.py:198-227 with whole=False (sliding-window tiles) in one launch (DESIGN
+    §12, csrc/slide.hip).  passes: up to 16 tuples (logits fp32 [T,N,C,lh,lw], (hs, ws), (th, tw), ys, xs, flip, weight):
+    the low-resolution logits of the network on each of the T = len(ys) * len(xs) padded th x tw tiles (row-major;
+    evaluate.sliding_tiles) of the image resized to hs x ws, mirrored along x when flip.  Everything else as
+    multiscale_vote.  -> (pred int32 [N,out_h,out_w] or None, scores fp32 [N,C,out_h,out_w] or None).  Neither the
+    upsampled tiles nor the N x C x hs x ws accumulator are ever formed."""
+    passes = list(passes)
+    if not 1 <= len(passes) <= SLIDE_MAX_PASSES:
+        raise RuntimeError("sliding_vote: 1 .. %d passes expected, got %d" % (SLIDE_MAX_PASSES, len(passes)))
+    H, W = int(grid_hw[0]), int(grid_hw[1])
+    oh, ow = int(out_hw[0]), int(out_hw[1])
+    first = passes[0][0]
+    _require(first, "logits")
+    if first.dim() != 5:
+        raise RuntimeError("sliding_vote: logits [T,N,C,lh,lw] expected")
+    dev, (N, Cc) = first.device, first.shape[1:3]
+    if not (0 < oh <= H and 0 < ow <= W):
+        raise RuntimeError("sliding_vote: the output %dx%d must be a crop of the grid %dx%d" % (oh, ow, H, W))
+    recs, keep, geometry = (_lib.SlidePass * len(passes))(), [], []
+    for i, (logits, (hs, ws), (th, tw), ys, xs, flip, weight) in enumerate(passes):
+        _require(logits, "logits")
+        ys, xs = _origins("sliding_vote", ys, "rows"), _origins("sliding_vote", xs, "columns")
+        if logits.dim() != 5 or tuple(logits.shape[:3]) != (len(ys) * len(xs), N, Cc) or logits.device != dev:
+            raise RuntimeError("sliding_vote: every pass holds [rows*cols,N,C,lh,lw] logits of one batch on one device")
+        logits = logits.contiguous()
+        keep.append(logits)
+        geometry.append((tuple(ys), tuple(xs)))
+        recs[i] = _lib.SlidePass(logits.data_ptr(), logits.shape[3], logits.shape[4], int(hs), int(ws), int(th), int(tw),
+                                 len(ys), len(xs), int(bool(flip)), float(weight))
+    if (conf is None) != (labels is None):
+        raise RuntimeError("sliding_vote: labels and the confusion matrix come together")
+    if labels is not None:
+        if not (isinstance(labels, torch.Tensor) and labels.is_cuda and labels.device == dev and
+                labels.dtype == torch.int64 and tuple(labels.shape) == (N, oh, ow) and labels.is_contiguous()):
+            raise RuntimeError("sliding_vote: dense int64 [N,out_h,out_w] device labels expected")
+        if not (isinstance(conf, torch.Tensor) and conf.is_cuda and conf.device == dev and conf.dtype == torch.int64 and
+                tuple(conf.shape) == (Cc, Cc) and conf.is_contiguous()):
+            raise RuntimeError("sliding_vote: conf must be a contiguous int64 [C,C] device tensor")
+    if not (want_scores or want_pred or labels is not None):
+        raise RuntimeError("sliding_vote: nothing asked for")
+    with torch.cuda.device(dev):
+        host, table = _slide_table(tuple(geometry), dev)
+        scores = torch.empty((N, Cc, oh, ow), dtype=torch.float32, device=dev) if want_scores else None
+        pred = torch.empty((N, oh, ow), dtype=torch.int32, device=dev) if want_pred else None
+        check(_lib.lib().dcfp_vote_sliding_f32(recs, len(passes), host, _p(table), N, Cc, H, W, oh, ow,
+                                               int(bool(align_corners)), _p(scores), _p(pred), _p(labels),
+                                               int(ignore_index), _p(conf), _stream()),
+              "sliding_vote")
+    return pred, scores
+
+
 def label_boundary(labels, num_classes, d, background=255):
     """The label map with everything but the class boundaries set to `background`: a pixel with
     0 <= label < num_classes keeps its label unless the whole (2d+1)x(2d+1) window centred on it lies inside the

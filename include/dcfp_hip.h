@@ -527,6 +527,55 @@ int dcfp_vote_multiscale_f32(const DcfpVoteMap* maps, int n_maps, int N, int C,
                              int64_t* conf,         /* optional [C*C], accumulated; needs gt */
                              dcfp_stream_t stream);
 
+/* Sliding-window evaluation (evaluate.py:145-184 under evaluate.py:198-227, whole=False; slide.hip).
+ *
+ * The tile grid is separable: tile t = r * cols + c has its origin at (ys[r], xs[c]) and covers
+ * [ys[r], min(ys[r] + th, h)) x [xs[c], min(xs[c] + tw, w)); at most 32 origins per axis.
+ *
+ * dcfp_gather_tiles_f32: all rows * cols zero-padded tiles of image [N,channels,h,w] in one launch, tiles
+ * [rows*cols, N, channels, th, tw]; with flip != 0 the tiles of the image mirrored along x (which is never formed).
+ * ys / xs are HOST arrays, checked (0 <= origin < size) and passed by value.  `tiles` must be 16-byte aligned (it is
+ * written in 16-byte stores), DCFP_E_BADDESC otherwise. */
+#define DCFP_SLIDE_MAX_PASSES 16
+#define DCFP_SLIDE_MAX_TILES_PER_AXIS 32
+int dcfp_gather_tiles_f32(const float* image, int N, int channels, int h, int w,
+                          const int32_t* ys, int rows, const int32_t* xs, int cols,
+                          int th, int tw, int flip, float* tiles, dcfp_stream_t stream);
+
+/* dcfp_vote_sliding_f32: the vote of dcfp_vote_multiscale_f32 over sliding-window passes, one launch.  A pass holds
+ * the network's low-resolution logits on every padded tile of the image resized to hs x ws (mirrored along x when
+ * flip).  For y < out_h, x < out_w:
+ *   score[n,c,y,x] = sum_k weight_k * sum_{(Y,a) in lerp(y: hs_k -> H)} sum_{(X,b) in lerp(x: ws_k -> W)}
+ *                    a * b * S_k(n, c, Y, flip_k ? ws_k-1-X : X)
+ *   S_k(n,c,Y,X)   = 1/cnt_k(Y,X) * sum_{tiles t covering (Y,X)} U_kt(n, c, Y - y1_t, X - x1_t)
+ *   U_kt           = logits_k[t,n,c] resized bilinearly (lh, lw) -> (th, tw), always the full padded tile size
+ * with cnt_k the number of covering tiles (any number per axis).  scores / pred / gt / conf, the first-maximum rule,
+ * the limits on C and the bit-for-bit repeatability are those of dcfp_vote_multiscale_f32.
+ * The origins travel apart from the records: origins_host and origins_dev are the same table of n_passes x 64 int32
+ * (per pass 32 row origins, then 32 column origins, unused entries 0), once in host memory - validated here before
+ * the launch: sorted, inside the image, no pixel of [0,hs) x [0,ws) uncovered - and once in device memory, which the
+ * kernel reads.  `passes` is a HOST array of n_passes <= 16 records, passed by value.  DCFP_E_BADDESC otherwise. */
+typedef struct DcfpSlidePass {
+    const float* logits;   /* [rows*cols, N, C, lh, lw] dense fp32 */
+    int lh, lw;            /* size of one tile's logits */
+    int hs, ws;            /* size of the resized image the tiles were cut from */
+    int th, tw;            /* the (padded) tile size the network saw */
+    int rows, cols;        /* tile grid, 1 .. 32 each */
+    int flip;              /* 1: the tiles were cut from the image mirrored along x */
+    float weight;          /* 1/len(scales), or 0.5/len(scales) for each pass of a flip pair */
+} DcfpSlidePass;
+int dcfp_vote_sliding_f32(const DcfpSlidePass* passes, int n_passes,
+                          const int32_t* origins_host, const int32_t* origins_dev,
+                          int N, int C,
+                          int H, int W,          /* the grid the reference votes on */
+                          int out_h, int out_w,  /* top-left crop that is produced, <= H, W */
+                          int align_corners,
+                          float* scores,         /* optional [N, C, out_h, out_w] */
+                          int32_t* pred,         /* optional [N, out_h, out_w] */
+                          const int64_t* gt, int ignore_index,   /* optional [N, out_h, out_w] */
+                          int64_t* conf,         /* optional [C*C], accumulated; needs gt */
+                          dcfp_stream_t stream);
+
 /* Boundary IoU (evaluate.py:352-357, utils/edge_utils.py:98-127): the label map with everything but the class
  * boundaries set to `background`.  A pixel is valid if 0 <= label < num_classes; a valid pixel is interior if
  * the whole (2d+1)x(2d+1) window centred on it lies inside the image and carries its label;

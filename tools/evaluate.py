@@ -9,8 +9,9 @@ Without `--dataset` the data are SYNTHETIC (seeded rectangles).  With `--dataset
 of `--whole True --align-corner True`, palette PNGs with `--save-predict True`, and one process per GPU under
 torchrun (`--ddp`, every file counted exactly once, the matrix summed over the ranks).  `--whole True` with more than
 one scale or with --flip then runs evaluate.predict_vote: prediction, argmax and confusion matrix are one launch after
-the network (`--fused-vote False`: the N x C x H x W path, for A/B).  `--device-png True` deflates the palette PNGs
-of `--save-predict` on the device.  The test-split export is tools/evaluate_test.py, which shares
+the network (`--fused-vote False`: the N x C x H x W path, for A/B).  `--whole False --fused-sliding True` runs
+evaluate.predict_sliding_vote: the tiles of a pass as batches, then one vote launch.  `--device-png True` deflates
+the palette PNGs of `--save-predict` on the device.  The test-split export is tools/evaluate_test.py, which shares
 `build_model` and `predict_batch` with this file.  The ADE dataset is not part of it."""
 import argparse
 import json
@@ -74,6 +75,9 @@ def get_parser():
                         "(default: True with --dataset, False without)")
     p.add_argument("--device-png", type=str2bool, default="False",
                    help="deflate the PNGs of --save-predict on the device (evaluate.encode_label_pngs)")
+    p.add_argument("--fused-sliding", type=str2bool, default="False",
+                   help="sliding-window prediction (--whole False) through evaluate.predict_sliding_vote: batched "
+                        "tiles, one vote launch (DESIGN §12)")
     return p
 
 
@@ -157,6 +161,14 @@ def predict_batch(model, image, args, scales, fused, size, label=None, conf=None
                                        want_scores=resized, ignore_index=args.ignore_label)
         if resized:
             pred = ops.upsample_argmax(scores, size, False)
+    elif not args.whole and getattr(args, "fused_sliding", False):
+        counted = not resized and conf is not None        # tiles, vote, argmax and confusion: one launch after the network
+        pred, scores = ev.predict_sliding_vote(model, image, (h, w), scales, args.flip, args.align_corner,
+                                               out_hw=size_scale, labels=label if counted else None,
+                                               conf=conf if counted else None, want_scores=resized,
+                                               ignore_index=args.ignore_label)
+        if resized:
+            pred = ops.upsample_argmax(scores, size, False)
     else:
         output = ev.predict_multiscale(model, image, (h, w), scales, C, args.flip, args.align_corner,
                                        args.whole)
@@ -197,6 +209,8 @@ def main(argv=None):
                 pred = ev.predict_labels(model, image)
             elif args.whole and args.fused_vote:
                 pred, _ = ev.predict_vote(model, image, scales, args.flip, args.align_corner)
+            elif not args.whole and args.fused_sliding:
+                pred, _ = ev.predict_sliding_vote(model, image, (h, w), scales, args.flip, args.align_corner)
             else:
                 output = ev.predict_multiscale(model, image, (h, w), scales, C, args.flip, args.align_corner, args.whole)
                 pred = ops.upsample_argmax(output, (h, w), True)      # same size, corners aligned: the plain argmax
