@@ -17,8 +17,8 @@
 // The tile grid is separable (rows x cols origins), so is cnt_k.  One lane owns one output pixel and walks the origin
 // tables of a pass (any number of tiles may cover a pixel); per covering tile it has 2 x 2 taps that are reused over the
 // classes.  The summation order (passes, the two rows Y, tile rows, the two columns X, tile columns, classes) is fixed
-// and there are no float atomics: two calls give the same bits.  Confusion matrix: per-block LDS bins while
-// C*C <= 4096, global integer atomics above that, as vote.hip.
+// and there are no float atomics: two calls give the same bits.  The pixel loop, the argmax and the confusion count
+// around that sum are vote_core.h's, shared with vote.hip.
 //
 // The origins (up to 16 passes x (32 + 32)) do not fit the kernel arguments beside the descriptors: the kernel reads
 // them from a device table that the caller keeps (a copy of the host table that is validated here) and stages them in
@@ -28,18 +28,16 @@
 // Coordinate rule of all index computations: bilinear.h (lerp_of / host_scale).
 #include "common.h"
 #include "bilinear.h"
-#include <math.h>
+#include "vote_core.h"
 
 namespace {
 
 using namespace dcfp_bilinear;
+using namespace dcfp_vote;
 
-constexpr int kThreads = 256;
 constexpr int kMaxPasses = DCFP_SLIDE_MAX_PASSES;
 constexpr int kMaxAxis = DCFP_SLIDE_MAX_TILES_PER_AXIS;
 constexpr int kTabStride = 2 * kMaxAxis;          // per pass: kMaxAxis row origins, then kMaxAxis column origins
-constexpr int kLdsBins = 4096;
-constexpr int kMaxBlocks = 256 * 8;
 
 struct GatherArgs {
     int ys[kMaxAxis], xs[kMaxAxis];
@@ -128,119 +126,71 @@ __device__ __forceinline__ int cover_count(const int* org, int n, int extent, in
     return cnt;
 }
 
-// CHUNK classes are accumulated in registers at a time; the taps of a pass are recomputed per chunk (19 classes: once)
+// the taps of a pass are recomputed per chunk of classes (19 classes: once); pixel loop and epilogue: vote_core.h
 template <bool ALIGN, int CHUNK>
 __global__ void __launch_bounds__(kThreads)
-slide_vote_kernel(const SlideBatch batch, int n_passes, const int* __restrict__ table, int N, int C, int out_h, int out_w,
-                  float* __restrict__ scores, int* __restrict__ pred, const long long* __restrict__ gt, int ignore_index,
-                  unsigned long long* __restrict__ conf, int lds_bins) {
+slide_vote_kernel(const SlideBatch batch, int n_passes, const int* __restrict__ table, const VoteOut out) {
     extern __shared__ unsigned int slide_lds[];
     int* org = reinterpret_cast<int*>(slide_lds);                 // [n_passes][kTabStride]
     unsigned int* hist = slide_lds + kMaxPasses * kTabStride;     // [lds_bins]
     for (int i = threadIdx.x; i < n_passes * kTabStride; i += kThreads) org[i] = table[i];
-    for (int i = threadIdx.x; i < lds_bins; i += kThreads) hist[i] = 0;
+    bins_clear(hist, out.lds_bins);
     __syncthreads();
-    const long long total = (long long)N * out_h * out_w;
-    const long long out_plane = (long long)out_h * out_w;
-    for (long long pix = (long long)blockIdx.x * kThreads + threadIdx.x; pix < total;
-         pix += (long long)gridDim.x * kThreads) {
-        const int x = (int)(pix % out_w);
-        const long long t = pix / out_w;
-        const int y = (int)(t % out_h);
-        const int n = (int)(t / out_h);
-        float best = -INFINITY;
-        int bi = 0;
-        for (int c0 = 0; c0 < C; c0 += CHUNK) {
-            float acc[CHUNK];
+    const int N = out.N, C = out.C;
+    vote_pixels<CHUNK>(out, hist, [&](float (&acc)[CHUNK], int n, int y, int x, int c0) {
+        for (int k = 0; k < n_passes; ++k) {
+            const SlidePass& m = batch.m[k];
+            const int* ys = org + k * kTabStride;
+            const int* xs = ys + kMaxAxis;
+            const Lerp LY = lerp_of<ALIGN>(y, m.sY, m.hs), LX = lerp_of<ALIGN>(x, m.sX, m.ws);
+            const long long plane = (long long)m.lh * m.lw;
+            for (int a = 0; a < 2; ++a) {
+                const float wy = a ? LY.l1 : LY.l0;
+                // a tap of weight exactly 0 adds exact zeros for finite logits and is skipped; with an Inf or NaN
+                // logit under such a tap the chain gives NaN (0 * Inf) where this kernel gives a finite score
+                if (wy == 0.f) continue;
+                const int Y = a ? LY.i1 : LY.i0;
+                const int cnt_r = cover_count(ys, m.rows, m.th, Y);
+                if (cnt_r == 0) continue;                    // (cannot happen with a validated table)
+                const float wrow = m.weight * wy / (float)cnt_r;
+                for (int r = 0; r < m.rows; ++r) {
+                    const int oy = ys[r];
+                    if (!(oy <= Y && Y < oy + m.th)) continue;
+                    const Lerp R = lerp_of<ALIGN>(Y - oy, m.sh, m.lh);
+                    const int ro0 = R.i0 * m.lw, ro1 = R.i1 * m.lw;
+                    const float wr0 = wrow * R.l0, wr1 = wrow * R.l1;
+                    for (int b = 0; b < 2; ++b) {
+                        const float wx = b ? LX.l1 : LX.l0;
+                        if (wx == 0.f) continue;
+                        const int X0 = b ? LX.i1 : LX.i0;
+                        const int X = m.flip ? m.ws - 1 - X0 : X0;
+                        const int cnt_c = cover_count(xs, m.cols, m.tw, X);
+                        if (cnt_c == 0) continue;
+                        const float wcol = wx / (float)cnt_c;
+                        for (int c = 0; c < m.cols; ++c) {
+                            const int ox = xs[c];
+                            if (!(ox <= X && X < ox + m.tw)) continue;
+                            const Lerp Cl = lerp_of<ALIGN>(X - ox, m.sw, m.lw);
+                            const float cw0 = wcol * Cl.l0, cw1 = wcol * Cl.l1;
+                            const long long tile = (long long)r * m.cols + c;
+                            const float* base = m.p + ((tile * N + n) * C + c0) * plane;
+                            const float* r0 = base + ro0;
+                            const float* r1 = base + ro1;
 #pragma unroll
-            for (int j = 0; j < CHUNK; ++j) acc[j] = 0.f;
-            for (int k = 0; k < n_passes; ++k) {
-                const SlidePass& m = batch.m[k];
-                const int* ys = org + k * kTabStride;
-                const int* xs = ys + kMaxAxis;
-                const Lerp LY = lerp_of<ALIGN>(y, m.sY, m.hs), LX = lerp_of<ALIGN>(x, m.sX, m.ws);
-                const long long plane = (long long)m.lh * m.lw;
-                for (int a = 0; a < 2; ++a) {
-                    const float wy = a ? LY.l1 : LY.l0;
-                    // a tap of weight exactly 0 adds exact zeros for finite logits and is skipped; with an Inf or NaN
-                    // logit under such a tap the chain gives NaN (0 * Inf) where this kernel gives a finite score
-                    if (wy == 0.f) continue;
-                    const int Y = a ? LY.i1 : LY.i0;
-                    const int cnt_r = cover_count(ys, m.rows, m.th, Y);
-                    if (cnt_r == 0) continue;                    // (cannot happen with a validated table)
-                    const float wrow = m.weight * wy / (float)cnt_r;
-                    for (int r = 0; r < m.rows; ++r) {
-                        const int oy = ys[r];
-                        if (!(oy <= Y && Y < oy + m.th)) continue;
-                        const Lerp R = lerp_of<ALIGN>(Y - oy, m.sh, m.lh);
-                        const int ro0 = R.i0 * m.lw, ro1 = R.i1 * m.lw;
-                        const float wr0 = wrow * R.l0, wr1 = wrow * R.l1;
-                        for (int b = 0; b < 2; ++b) {
-                            const float wx = b ? LX.l1 : LX.l0;
-                            if (wx == 0.f) continue;
-                            const int X0 = b ? LX.i1 : LX.i0;
-                            const int X = m.flip ? m.ws - 1 - X0 : X0;
-                            const int cnt_c = cover_count(xs, m.cols, m.tw, X);
-                            if (cnt_c == 0) continue;
-                            const float wcol = wx / (float)cnt_c;
-                            for (int c = 0; c < m.cols; ++c) {
-                                const int ox = xs[c];
-                                if (!(ox <= X && X < ox + m.tw)) continue;
-                                const Lerp Cl = lerp_of<ALIGN>(X - ox, m.sw, m.lw);
-                                const float cw0 = wcol * Cl.l0, cw1 = wcol * Cl.l1;
-                                const long long tile = (long long)r * m.cols + c;
-                                const float* base = m.p + ((tile * N + n) * C + c0) * plane;
-                                const float* r0 = base + ro0;
-                                const float* r1 = base + ro1;
-#pragma unroll
-                                for (int j = 0; j < CHUNK; ++j) {
-                                    if (c0 + j < C) {
-                                        const float* q0 = r0 + j * plane;
-                                        const float* q1 = r1 + j * plane;
-                                        acc[j] += wr0 * (cw0 * q0[Cl.i0] + cw1 * q0[Cl.i1]) +
-                                                  wr1 * (cw0 * q1[Cl.i0] + cw1 * q1[Cl.i1]);
-                                    }
+                            for (int j = 0; j < CHUNK; ++j) {
+                                if (c0 + j < C) {
+                                    const float* q0 = r0 + j * plane;
+                                    const float* q1 = r1 + j * plane;
+                                    acc[j] += wr0 * (cw0 * q0[Cl.i0] + cw1 * q0[Cl.i1]) +
+                                              wr1 * (cw0 * q1[Cl.i0] + cw1 * q1[Cl.i1]);
                                 }
                             }
                         }
                     }
                 }
             }
-#pragma unroll
-            for (int j = 0; j < CHUNK; ++j) {
-                if (c0 + j < C) {
-                    if (scores) scores[((long long)n * C + c0 + j) * out_plane + (long long)y * out_w + x] = acc[j];
-                    if (acc[j] > best) { best = acc[j]; bi = c0 + j; }     // first maximum wins, like vote_kernel
-                }
-            }
         }
-        if (pred) pred[pix] = bi;
-        if (conf) {
-            const long long g = gt[pix];
-            if (g != ignore_index && g >= 0 && g < C) {
-                if (lds_bins) atomicAdd(&hist[(int)g * C + bi], 1u);
-                else atomicAdd(&conf[g * C + bi], 1ull);
-            }
-        }
-    }
-    if (lds_bins) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < lds_bins; i += kThreads)
-            if (hist[i]) atomicAdd(&conf[i], (unsigned long long)hist[i]);
-    }
-}
-
-template <bool ALIGN, int CHUNK>
-void launch_slide(const SlideBatch& batch, int n_passes, const int32_t* table, int N, int C, int out_h, int out_w,
-                  float* scores, int32_t* pred, const int64_t* gt, int ignore_index, int64_t* conf, hipStream_t st) {
-    const long long total = (long long)N * out_h * out_w;
-    long long blocks = (total + kThreads - 1) / kThreads;
-    if (blocks > kMaxBlocks) blocks = kMaxBlocks;
-    const int lds_bins = (conf && (long long)C * C <= kLdsBins) ? C * C : 0;
-    hipLaunchKernelGGL((slide_vote_kernel<ALIGN, CHUNK>), dim3((unsigned)blocks), dim3(kThreads),
-                       (size_t)(kMaxPasses * kTabStride + lds_bins) * sizeof(unsigned), st, batch, n_passes, table, N, C,
-                       out_h, out_w, scores, pred, reinterpret_cast<const long long*>(gt), ignore_index,
-                       reinterpret_cast<unsigned long long*>(conf), lds_bins);
+    });
 }
 
 // origins of one axis: 1 .. kMaxAxis of them, sorted, inside [0, size), every position of [0, size) under a tile
@@ -289,11 +239,9 @@ extern "C" int dcfp_vote_sliding_f32(const DcfpSlidePass* passes, int n_passes, 
                                      const int32_t* origins_dev, int N, int C, int H, int W, int out_h, int out_w,
                                      int align_corners, float* scores, int32_t* pred, const int64_t* gt,
                                      int ignore_index, int64_t* conf, dcfp_stream_t stream) {
-    if (!passes || !origins_host || !origins_dev || n_passes <= 0 || n_passes > kMaxPasses || N <= 0 || C <= 0 ||
-        H <= 0 || W <= 0 || out_h <= 0 || out_w <= 0 || out_h > H || out_w > W)
+    if (!passes || !origins_host || !origins_dev || n_passes <= 0 || n_passes > kMaxPasses ||
+        !vote_args_ok(N, C, H, W, out_h, out_w, scores, pred, gt, conf))
         return DCFP_E_BADDESC;
-    if ((conf && !gt) || (!scores && !pred && !conf)) return DCFP_E_BADDESC;
-    if (conf && C > 1024) return DCFP_E_BADDESC;        // as dcfp_confusion_matrix_i64
     SlideBatch batch;
     for (int k = 0; k < kMaxPasses; ++k) {
         const DcfpSlidePass& s = passes[k < n_passes ? k : 0];
@@ -315,13 +263,10 @@ extern "C" int dcfp_vote_sliding_f32(const DcfpSlidePass* passes, int n_passes, 
         m.sh = host_scale(s.lh, s.th, align_corners);
         m.sw = host_scale(s.lw, s.tw, align_corners);
     }
-    hipStream_t st = dcfp_s(stream);
-    if (C == 19) {      // Cityscapes: every class in registers, the taps of a pass computed once
-        if (align_corners) launch_slide<true, 19>(batch, n_passes, origins_dev, N, C, out_h, out_w, scores, pred, gt, ignore_index, conf, st);
-        else launch_slide<false, 19>(batch, n_passes, origins_dev, N, C, out_h, out_w, scores, pred, gt, ignore_index, conf, st);
-    } else {
-        if (align_corners) launch_slide<true, 16>(batch, n_passes, origins_dev, N, C, out_h, out_w, scores, pred, gt, ignore_index, conf, st);
-        else launch_slide<false, 16>(batch, n_passes, origins_dev, N, C, out_h, out_w, scores, pred, gt, ignore_index, conf, st);
-    }
+    const VoteLaunch L = vote_launch(N, C, out_h, out_w, scores, pred, gt, ignore_index, conf, kMaxPasses * kTabStride);
+    vote_dispatch(align_corners, C, [&](auto align, auto chunk) {
+        hipLaunchKernelGGL((slide_vote_kernel<decltype(align)::value, decltype(chunk)::value>), dim3(L.blocks),
+                           dim3(kThreads), L.lds_bytes, dcfp_s(stream), batch, n_passes, origins_dev, L.out);
+    });
     DCFP_RETURN_LAUNCH();
 }

@@ -11,12 +11,13 @@
 // Coordinate rules: bilinear.h (ATen's area_pixel_compute_scale / _source_index).
 #include "common.h"
 #include "bilinear.h"
+#include "vote_core.h"
 #include <math.h>
 #include <stdlib.h>
 
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = dcfp_vote::kThreads;   // 256; the confusion kernels share vote_core.h's bin loops
 constexpr int kLossBlocks = 2048;
 
 using namespace dcfp_bilinear;   // Lerp, lerp_of, host_scale, dst_range, tap_weight (bilinear.h)
@@ -802,23 +803,21 @@ upsample_argmax_kernel(const float* __restrict__ logits, int N, int C, int h, in
     }
 }
 
-// per-block LDS histogram (C*C <= 4096 bins), then one integer atomic per non-empty bin
+// per-block LDS histogram (C*C <= 4096 bins), then one integer atomic per non-empty bin; the bins, and the rule for a
+// label outside the classes, are vote_core.h's.  pred comes from outside: a prediction that is no class is skipped too.
 __global__ void __launch_bounds__(kThreads)
 confusion_kernel(const int* __restrict__ pred, const long long* __restrict__ gt, int ignore_index,
                  long long n, int C, unsigned long long* __restrict__ conf) {
     extern __shared__ unsigned int hist[];
     const int bins = C * C;
-    for (int i = threadIdx.x; i < bins; i += kThreads) hist[i] = 0;
+    dcfp_vote::bins_clear(hist, bins);
     __syncthreads();
     for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n;
          i += (long long)gridDim.x * kThreads) {
-        const long long g = gt[i];
         const int p = pred[i];
-        if (g != ignore_index && g >= 0 && g < C && p >= 0 && p < C) atomicAdd(&hist[(int)g * C + p], 1u);
+        if (p >= 0 && p < C) dcfp_vote::bins_count(hist, bins, conf, gt[i], p, C, ignore_index);
     }
-    __syncthreads();
-    for (int i = threadIdx.x; i < bins; i += kThreads)
-        if (hist[i]) atomicAdd(&conf[i], (unsigned long long)hist[i]);
+    dcfp_vote::bins_flush(hist, bins, conf);
 }
 
 __global__ void __launch_bounds__(kThreads)
@@ -826,9 +825,8 @@ confusion_global_kernel(const int* __restrict__ pred, const long long* __restric
                         long long n, int C, unsigned long long* __restrict__ conf) {
     for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n;
          i += (long long)gridDim.x * kThreads) {
-        const long long g = gt[i];
         const int p = pred[i];
-        if (g != ignore_index && g >= 0 && g < C && p >= 0 && p < C) atomicAdd(&conf[g * C + p], 1ull);
+        if (p >= 0 && p < C) dcfp_vote::bins_count(nullptr, 0, conf, gt[i], p, C, ignore_index);
     }
 }
 

@@ -11,22 +11,20 @@
 // with U_k the bilinear value of logits_k[n,c] resized (h_k, w_k) -> (hs_k, ws_k).  One lane owns one output pixel,
 // computes the 4 row and 4 column taps of a map once and reuses them over the classes; the maps are small beside L2.
 // The full-resolution logits never exist.  The summation order (maps, then rows, then columns) is fixed and there are
-// no float atomics: two calls give the same bits.  The confusion matrix is counted in per-block LDS bins while
-// C*C <= 4096 and with global integer atomics above that, like confusion_kernel / confusion_global_kernel.
+// no float atomics: two calls give the same bits.  The pixel loop, the argmax and the confusion count around that sum
+// are vote_core.h's, shared with slide.hip.
 //
 // Coordinate rule of all four index computations: bilinear.h (lerp_of / host_scale).
 #include "common.h"
 #include "bilinear.h"
-#include <math.h>
+#include "vote_core.h"
 
 namespace {
 
 using namespace dcfp_bilinear;
+using namespace dcfp_vote;
 
-constexpr int kThreads = 256;
 constexpr int kMaxMaps = 16;
-constexpr int kLdsBins = 4096;
-constexpr int kMaxBlocks = 256 * 8;
 
 struct VoteMap {
     const float* p;
@@ -39,94 +37,44 @@ struct VoteBatch {
     VoteMap m[kMaxMaps];
 };
 
-// CHUNK classes are accumulated in registers at a time; the taps of a map are recomputed per chunk (19 classes: once)
+// the taps of a map are recomputed per chunk of classes (19 classes: once); pixel loop and epilogue: vote_core.h
 template <bool ALIGN, int CHUNK>
 __global__ void __launch_bounds__(kThreads)
-vote_kernel(const VoteBatch batch, int n_maps, int N, int C, int out_h, int out_w,
-            float* __restrict__ scores, int* __restrict__ pred, const long long* __restrict__ gt, int ignore_index,
-            unsigned long long* __restrict__ conf, int lds_bins) {
+vote_kernel(const VoteBatch batch, int n_maps, const VoteOut out) {
     extern __shared__ unsigned int vote_hist[];
-    if (lds_bins) {
-        for (int i = threadIdx.x; i < lds_bins; i += kThreads) vote_hist[i] = 0;
-        __syncthreads();
-    }
-    const long long total = (long long)N * out_h * out_w;
-    const long long out_plane = (long long)out_h * out_w;
-    for (long long pix = (long long)blockIdx.x * kThreads + threadIdx.x; pix < total;
-         pix += (long long)gridDim.x * kThreads) {
-        const int x = (int)(pix % out_w);
-        const long long t = pix / out_w;
-        const int y = (int)(t % out_h);
-        const int n = (int)(t / out_h);
-        float best = -INFINITY;
-        int bi = 0;
-        for (int c0 = 0; c0 < C; c0 += CHUNK) {
-            float acc[CHUNK];
-#pragma unroll
-            for (int j = 0; j < CHUNK; ++j) acc[j] = 0.f;
-            for (int k = 0; k < n_maps; ++k) {
-                const VoteMap& m = batch.m[k];
-                const Lerp LY = lerp_of<ALIGN>(y, m.sY, m.hs), LX = lerp_of<ALIGN>(x, m.sX, m.ws);
-                const Lerp R0 = lerp_of<ALIGN>(LY.i0, m.sh, m.h), R1 = lerp_of<ALIGN>(LY.i1, m.sh, m.h);
-                const int x0 = m.flip ? m.ws - 1 - LX.i0 : LX.i0, x1 = m.flip ? m.ws - 1 - LX.i1 : LX.i1;
-                const Lerp C0 = lerp_of<ALIGN>(x0, m.sw, m.w), C1 = lerp_of<ALIGN>(x1, m.sw, m.w);
-                const int ro[4] = {R0.i0 * m.w, R0.i1 * m.w, R1.i0 * m.w, R1.i1 * m.w};
-                const float wy0 = m.weight * LY.l0, wy1 = m.weight * LY.l1;
-                const float rw[4] = {wy0 * R0.l0, wy0 * R0.l1, wy1 * R1.l0, wy1 * R1.l1};
-                const int co[4] = {C0.i0, C0.i1, C1.i0, C1.i1};
-                const float cw[4] = {LX.l0 * C0.l0, LX.l0 * C0.l1, LX.l1 * C1.l0, LX.l1 * C1.l1};
-                const long long plane = (long long)m.h * m.w;
-                const float* base = m.p + ((long long)n * C + c0) * plane;
-#pragma unroll
-                for (int j = 0; j < CHUNK; ++j) {
-                    if (c0 + j < C) {
-                        const float* p = base + j * plane;
-                        float s = 0.f;
-#pragma unroll
-                        for (int a = 0; a < 4; ++a) {
-                            const float* r = p + ro[a];
-                            const float row = (cw[0] * r[co[0]] + cw[1] * r[co[1]]) + (cw[2] * r[co[2]] + cw[3] * r[co[3]]);
-                            s += rw[a] * row;
-                        }
-                        acc[j] += s;
-                    }
-                }
-            }
+    bins_clear(vote_hist, out.lds_bins);
+    __syncthreads();
+    const int C = out.C;
+    vote_pixels<CHUNK>(out, vote_hist, [&](float (&acc)[CHUNK], int n, int y, int x, int c0) {
+        for (int k = 0; k < n_maps; ++k) {
+            const VoteMap& m = batch.m[k];
+            const Lerp LY = lerp_of<ALIGN>(y, m.sY, m.hs), LX = lerp_of<ALIGN>(x, m.sX, m.ws);
+            const Lerp R0 = lerp_of<ALIGN>(LY.i0, m.sh, m.h), R1 = lerp_of<ALIGN>(LY.i1, m.sh, m.h);
+            const int x0 = m.flip ? m.ws - 1 - LX.i0 : LX.i0, x1 = m.flip ? m.ws - 1 - LX.i1 : LX.i1;
+            const Lerp C0 = lerp_of<ALIGN>(x0, m.sw, m.w), C1 = lerp_of<ALIGN>(x1, m.sw, m.w);
+            const int ro[4] = {R0.i0 * m.w, R0.i1 * m.w, R1.i0 * m.w, R1.i1 * m.w};
+            const float wy0 = m.weight * LY.l0, wy1 = m.weight * LY.l1;
+            const float rw[4] = {wy0 * R0.l0, wy0 * R0.l1, wy1 * R1.l0, wy1 * R1.l1};
+            const int co[4] = {C0.i0, C0.i1, C1.i0, C1.i1};
+            const float cw[4] = {LX.l0 * C0.l0, LX.l0 * C0.l1, LX.l1 * C1.l0, LX.l1 * C1.l1};
+            const long long plane = (long long)m.h * m.w;
+            const float* base = m.p + ((long long)n * C + c0) * plane;
 #pragma unroll
             for (int j = 0; j < CHUNK; ++j) {
                 if (c0 + j < C) {
-                    if (scores) scores[((long long)n * C + c0 + j) * out_plane + (long long)y * out_w + x] = acc[j];
-                    if (acc[j] > best) { best = acc[j]; bi = c0 + j; }     // first maximum wins, like upsample_argmax_kernel
+                    const float* p = base + j * plane;
+                    float s = 0.f;
+#pragma unroll
+                    for (int a = 0; a < 4; ++a) {
+                        const float* r = p + ro[a];
+                        const float row = (cw[0] * r[co[0]] + cw[1] * r[co[1]]) + (cw[2] * r[co[2]] + cw[3] * r[co[3]]);
+                        s += rw[a] * row;
+                    }
+                    acc[j] += s;
                 }
             }
         }
-        if (pred) pred[pix] = bi;
-        if (conf) {
-            const long long g = gt[pix];
-            if (g != ignore_index && g >= 0 && g < C) {
-                if (lds_bins) atomicAdd(&vote_hist[(int)g * C + bi], 1u);
-                else atomicAdd(&conf[g * C + bi], 1ull);
-            }
-        }
-    }
-    if (lds_bins) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < lds_bins; i += kThreads)
-            if (vote_hist[i]) atomicAdd(&conf[i], (unsigned long long)vote_hist[i]);
-    }
-}
-
-template <bool ALIGN, int CHUNK>
-void launch_vote(const VoteBatch& batch, int n_maps, int N, int C, int out_h, int out_w, float* scores,
-                 int32_t* pred, const int64_t* gt, int ignore_index, int64_t* conf, hipStream_t st) {
-    const long long total = (long long)N * out_h * out_w;
-    long long blocks = (total + kThreads - 1) / kThreads;
-    if (blocks > kMaxBlocks) blocks = kMaxBlocks;
-    const int lds_bins = (conf && (long long)C * C <= kLdsBins) ? C * C : 0;
-    hipLaunchKernelGGL((vote_kernel<ALIGN, CHUNK>), dim3((unsigned)blocks), dim3(kThreads),
-                       (size_t)lds_bins * sizeof(unsigned), st, batch, n_maps, N, C, out_h, out_w, scores, pred,
-                       reinterpret_cast<const long long*>(gt), ignore_index,
-                       reinterpret_cast<unsigned long long*>(conf), lds_bins);
+    });
 }
 
 }  // namespace
@@ -134,11 +82,8 @@ void launch_vote(const VoteBatch& batch, int n_maps, int N, int C, int out_h, in
 extern "C" int dcfp_vote_multiscale_f32(const DcfpVoteMap* maps, int n_maps, int N, int C, int H, int W, int out_h,
                                         int out_w, int align_corners, float* scores, int32_t* pred, const int64_t* gt,
                                         int ignore_index, int64_t* conf, dcfp_stream_t stream) {
-    if (!maps || n_maps <= 0 || n_maps > kMaxMaps || N <= 0 || C <= 0 || H <= 0 || W <= 0 || out_h <= 0 || out_w <= 0 ||
-        out_h > H || out_w > W)
+    if (!maps || n_maps <= 0 || n_maps > kMaxMaps || !vote_args_ok(N, C, H, W, out_h, out_w, scores, pred, gt, conf))
         return DCFP_E_BADDESC;
-    if ((conf && !gt) || (!scores && !pred && !conf)) return DCFP_E_BADDESC;
-    if (conf && C > 1024) return DCFP_E_BADDESC;        // as dcfp_confusion_matrix_i64
     VoteBatch batch;
     for (int k = 0; k < kMaxMaps; ++k) {
         const DcfpVoteMap& s = maps[k < n_maps ? k : 0];
@@ -156,13 +101,10 @@ extern "C" int dcfp_vote_multiscale_f32(const DcfpVoteMap* maps, int n_maps, int
         m.sh = host_scale(s.h, s.hs, align_corners);
         m.sw = host_scale(s.w, s.ws, align_corners);
     }
-    hipStream_t st = dcfp_s(stream);
-    if (C == 19) {      // Cityscapes: every class in registers, the taps of a map computed once
-        if (align_corners) launch_vote<true, 19>(batch, n_maps, N, C, out_h, out_w, scores, pred, gt, ignore_index, conf, st);
-        else launch_vote<false, 19>(batch, n_maps, N, C, out_h, out_w, scores, pred, gt, ignore_index, conf, st);
-    } else {
-        if (align_corners) launch_vote<true, 16>(batch, n_maps, N, C, out_h, out_w, scores, pred, gt, ignore_index, conf, st);
-        else launch_vote<false, 16>(batch, n_maps, N, C, out_h, out_w, scores, pred, gt, ignore_index, conf, st);
-    }
+    const VoteLaunch L = vote_launch(N, C, out_h, out_w, scores, pred, gt, ignore_index, conf, 0);
+    vote_dispatch(align_corners, C, [&](auto align, auto chunk) {
+        hipLaunchKernelGGL((vote_kernel<decltype(align)::value, decltype(chunk)::value>), dim3(L.blocks), dim3(kThreads),
+                           L.lds_bytes, dcfp_s(stream), batch, n_maps, L.out);
+    });
     DCFP_RETURN_LAUNCH();
 }

@@ -89,6 +89,16 @@ def predict_multiscale(net, image, tile_size, scales, classes, flip_evaluation, 
     return full
 
 
+def _vote_scales(image, scales, flip, align_corner):
+    """Per scale of a fused vote, as predict_multiscale steps through them: (the image resized to the scale, its size
+    (hs, ws), the weight of each of the scale's passes - the plain one and, with `flip`, the mirrored one)."""
+    H_, W_ = image.shape[2:]
+    for scale in scales:
+        scale = float(scale)
+        hs, ws = int(H_ * scale), int(W_ * scale)
+        yield ops.upsample_bilinear(image, (hs, ws), align_corner), (hs, ws), (0.5 if flip else 1.0) / len(scales)
+
+
 @torch.no_grad()
 def predict_vote(net, image, scales, flip, align_corner, out_hw=None, labels=None, conf=None, want_scores=False,
                  ignore_index=255):
@@ -101,14 +111,10 @@ def predict_vote(net, image, scales, flip, align_corner, out_hw=None, labels=Non
     _exec.require_device(image)
     H_, W_ = image.shape[2:]
     maps = []
-    for scale in scales:
-        scale = float(scale)
-        hs, ws = int(H_ * scale), int(W_ * scale)
-        img = ops.upsample_bilinear(image, (hs, ws), align_corner)
-        weight = (0.5 if flip else 1.0) / len(scales)
-        maps.append((net.lowres_logits(img)[0], (hs, ws), False, weight))
+    for img, hw, weight in _vote_scales(image, scales, flip, align_corner):
+        maps.append((net.lowres_logits(img)[0], hw, False, weight))
         if flip:
-            maps.append((net.lowres_logits(torch.flip(img, [3]))[0], (hs, ws), True, weight))
+            maps.append((net.lowres_logits(torch.flip(img, [3]))[0], hw, True, weight))
     return ops.multiscale_vote(maps, (H_, W_), (H_, W_) if out_hw is None else out_hw, align_corner, labels=labels,
                                conf=conf, want_scores=want_scores, ignore_index=ignore_index)
 
@@ -167,16 +173,13 @@ def predict_sliding_vote(net, image, tile_size, scales, flip, align_corner, out_
         tile_batch = TILE_PIXELS_PER_CALL // (N_ * th * tw)
     tile_batch = max(1, int(tile_batch))
     passes = []
-    for scale in scales:
-        scale = float(scale)
-        hs, ws = int(H_ * scale), int(W_ * scale)
-        img = ops.upsample_bilinear(image, (hs, ws), align_corner)
+    for scale, (img, (hs, ws), weight) in zip(scales, _vote_scales(image, scales, flip, align_corner)):
         ys, xs = sliding_tiles(hs, ws, (th, tw))
         if max(len(ys), len(xs)) > ops.SLIDE_MAX_TILES_PER_AXIS:
             raise RuntimeError("predict_sliding_vote: %d x %d tiles at scale %g, one launch takes %d per axis "
-                               "(SLIDE_MAX_TILES_PER_AXIS)" % (len(ys), len(xs), scale, ops.SLIDE_MAX_TILES_PER_AXIS))
+                               "(SLIDE_MAX_TILES_PER_AXIS)" % (len(ys), len(xs), float(scale),
+                                                               ops.SLIDE_MAX_TILES_PER_AXIS))
         T = len(ys) * len(xs)
-        weight = (0.5 if flip else 1.0) / len(scales)
         for mirrored in ((False, True) if flip else (False,)):
             tiles = ops.gather_tiles(img, ys, xs, (th, tw), mirrored)
             logits = None

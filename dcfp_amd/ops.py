@@ -1999,6 +1999,46 @@ def confusion_matrix(pred, gt, num_classes, ignore_index=255, out=None):
 VOTE_MAX_MAPS = 16
 
 
+def _fused_vote(name, entry, items, limit, what, layout, records, grid_hw, out_hw, align_corners, labels, conf,
+                want_scores, want_pred, ignore_index):
+    """What multiscale_vote and sliding_vote share: every check but those on a pass's own record, the outputs and the
+    launch.  items: the maps / passes (at most `limit`), logits first, of shape `layout` (N, C in front of the last two
+    dimensions); records(items, dev, N, C) checks them and returns a callable that gives, on the logits' device, the
+    arguments of the C entry `entry` in front of N (it keeps the tensors they point to alive)."""
+    items = list(items)
+    if not 1 <= len(items) <= limit:
+        raise RuntimeError("%s: 1 .. %d %s expected, got %d" % (name, limit, what, len(items)))
+    H, W = int(grid_hw[0]), int(grid_hw[1])
+    oh, ow = int(out_hw[0]), int(out_hw[1])
+    first = items[0][0]
+    _require(first, "logits")
+    dims = layout.count(",") + 1
+    if first.dim() != dims:
+        raise RuntimeError("%s: logits %s expected" % (name, layout))
+    dev, (N, Cc) = first.device, first.shape[dims - 4:dims - 2]
+    if not (0 < oh <= H and 0 < ow <= W):
+        raise RuntimeError("%s: the output %dx%d must be a crop of the grid %dx%d" % (name, oh, ow, H, W))
+    lead = records(items, dev, N, Cc)
+    if (conf is None) != (labels is None):
+        raise RuntimeError("%s: labels and the confusion matrix come together" % name)
+    if labels is not None:
+        if not (isinstance(labels, torch.Tensor) and labels.is_cuda and labels.device == dev and
+                labels.dtype == torch.int64 and tuple(labels.shape) == (N, oh, ow) and labels.is_contiguous()):
+            raise RuntimeError("%s: dense int64 [N,out_h,out_w] device labels expected" % name)
+        if not (isinstance(conf, torch.Tensor) and conf.is_cuda and conf.device == dev and conf.dtype == torch.int64 and
+                tuple(conf.shape) == (Cc, Cc) and conf.is_contiguous()):
+            raise RuntimeError("%s: conf must be a contiguous int64 [C,C] device tensor" % name)
+    if not (want_scores or want_pred or labels is not None):
+        raise RuntimeError("%s: nothing asked for" % name)
+    with torch.cuda.device(dev):
+        head = lead()          # (lead stays bound: it keeps the records' tensors alive over the launch)
+        scores = torch.empty((N, Cc, oh, ow), dtype=torch.float32, device=dev) if want_scores else None
+        pred = torch.empty((N, oh, ow), dtype=torch.int32, device=dev) if want_pred else None
+        check(getattr(_lib.lib(), entry)(*head, N, Cc, H, W, oh, ow, int(bool(align_corners)), _p(scores), _p(pred),
+                                         _p(labels), int(ignore_index), _p(conf), _stream()), name)
+    return pred, scores
+
+
 def multiscale_vote(maps, grid_hw, out_hw, align_corners, labels=None, conf=None, want_scores=False, want_pred=True,
                     ignore_index=255):
     """The multi-scale + flip vote of evaluate.py:198-227 (whole=True) in one launch (csrc/vote.hip).
@@ -2007,46 +2047,19 @@ def multiscale_vote(maps, grid_hw, out_hw, align_corners, labels=None, conf=None
     pass back to; out_hw: the top-left crop of that grid that is produced.  labels int64 [N,out_h,out_w] and conf int64
     [C,C] (accumulated, given together) count the confusion matrix in the same launch.  -> (pred int32 [N,out_h,out_w] or None, scores
     fp32 [N,C,out_h,out_w] or None).  The N x C x hs x ws logits are never formed."""
-    maps = list(maps)
-    if not 1 <= len(maps) <= VOTE_MAX_MAPS:
-        raise RuntimeError("multiscale_vote: 1 .. %d maps expected, got %d" % (VOTE_MAX_MAPS, len(maps)))
-    H, W = int(grid_hw[0]), int(grid_hw[1])
-    oh, ow = int(out_hw[0]), int(out_hw[1])
-    first = maps[0][0]
-    _require(first, "logits")
-    if first.dim() != 4:
-        raise RuntimeError("multiscale_vote: logits [N,C,h,w] expected")
-    dev, (N, Cc) = first.device, first.shape[:2]
-    if not (0 < oh <= H and 0 < ow <= W):
-        raise RuntimeError("multiscale_vote: the output %dx%d must be a crop of the grid %dx%d" % (oh, ow, H, W))
-    recs, keep = (_lib.VoteMap * len(maps))(), []
-    for i, (logits, (hs, ws), flip, weight) in enumerate(maps):
-        _require(logits, "logits")
-        if logits.dim() != 4 or tuple(logits.shape[:2]) != (N, Cc) or logits.device != dev:
-            raise RuntimeError("multiscale_vote: every map holds [N,C,h,w] logits of one batch on one device")
-        logits = logits.contiguous()
-        keep.append(logits)
-        recs[i] = _lib.VoteMap(logits.data_ptr(), logits.shape[2], logits.shape[3], int(hs), int(ws), int(bool(flip)),
-                               float(weight))
-    if (conf is None) != (labels is None):
-        raise RuntimeError("multiscale_vote: labels and the confusion matrix come together")
-    if labels is not None:
-        if not (isinstance(labels, torch.Tensor) and labels.is_cuda and labels.device == dev and
-                labels.dtype == torch.int64 and tuple(labels.shape) == (N, oh, ow) and labels.is_contiguous()):
-            raise RuntimeError("multiscale_vote: dense int64 [N,out_h,out_w] device labels expected")
-        if not (isinstance(conf, torch.Tensor) and conf.is_cuda and conf.device == dev and conf.dtype == torch.int64 and
-                tuple(conf.shape) == (Cc, Cc) and conf.is_contiguous()):
-            raise RuntimeError("multiscale_vote: conf must be a contiguous int64 [C,C] device tensor")
-    if not (want_scores or want_pred or labels is not None):
-        raise RuntimeError("multiscale_vote: nothing asked for")
-    scores = torch.empty((N, Cc, oh, ow), dtype=torch.float32, device=dev) if want_scores else None
-    pred = torch.empty((N, oh, ow), dtype=torch.int32, device=dev) if want_pred else None
-    with torch.cuda.device(dev):
-        check(_lib.lib().dcfp_vote_multiscale_f32(recs, len(maps), N, Cc, H, W, oh, ow, int(bool(align_corners)),
-                                                  _p(scores), _p(pred), _p(labels), int(ignore_index), _p(conf),
-                                                  _stream()),
-              "multiscale_vote")
-    return pred, scores
+    def records(maps, dev, N, Cc):
+        recs, keep = (_lib.VoteMap * len(maps))(), []
+        for i, (logits, (hs, ws), flip, weight) in enumerate(maps):
+            _require(logits, "logits")
+            if logits.dim() != 4 or tuple(logits.shape[:2]) != (N, Cc) or logits.device != dev:
+                raise RuntimeError("multiscale_vote: every map holds [N,C,h,w] logits of one batch on one device")
+            logits = logits.contiguous()
+            keep.append(logits)
+            recs[i] = _lib.VoteMap(logits.data_ptr(), logits.shape[2], logits.shape[3], int(hs), int(ws),
+                                   int(bool(flip)), float(weight))
+        return lambda: (recs, len(keep))
+    return _fused_vote("multiscale_vote", "dcfp_vote_multiscale_f32", maps, VOTE_MAX_MAPS, "maps", "[N,C,h,w]",
+                       records, grid_hw, out_hw, align_corners, labels, conf, want_scores, want_pred, ignore_index)
 
 
 SLIDE_MAX_PASSES, SLIDE_MAX_TILES_PER_AXIS = _lib.SLIDE_MAX_PASSES, _lib.SLIDE_MAX_TILES_PER_AXIS
@@ -2107,49 +2120,27 @@ def sliding_vote(passes, grid_hw, out_hw, align_corners, labels=None, conf=None,
     evaluate.sliding_tiles) of the image resized to hs x ws, mirrored along x when flip.  Everything else as
     multiscale_vote.  -> (pred int32 [N,out_h,out_w] or None, scores fp32 [N,C,out_h,out_w] or None).  Neither the
     upsampled tiles nor the N x C x hs x ws accumulator are ever formed."""
-    passes = list(passes)
-    if not 1 <= len(passes) <= SLIDE_MAX_PASSES:
-        raise RuntimeError("sliding_vote: 1 .. %d passes expected, got %d" % (SLIDE_MAX_PASSES, len(passes)))
-    H, W = int(grid_hw[0]), int(grid_hw[1])
-    oh, ow = int(out_hw[0]), int(out_hw[1])
-    first = passes[0][0]
-    _require(first, "logits")
-    if first.dim() != 5:
-        raise RuntimeError("sliding_vote: logits [T,N,C,lh,lw] expected")
-    dev, (N, Cc) = first.device, first.shape[1:3]
-    if not (0 < oh <= H and 0 < ow <= W):
-        raise RuntimeError("sliding_vote: the output %dx%d must be a crop of the grid %dx%d" % (oh, ow, H, W))
-    recs, keep, geometry = (_lib.SlidePass * len(passes))(), [], []
-    for i, (logits, (hs, ws), (th, tw), ys, xs, flip, weight) in enumerate(passes):
-        _require(logits, "logits")
-        ys, xs = _origins("sliding_vote", ys, "rows"), _origins("sliding_vote", xs, "columns")
-        if logits.dim() != 5 or tuple(logits.shape[:3]) != (len(ys) * len(xs), N, Cc) or logits.device != dev:
-            raise RuntimeError("sliding_vote: every pass holds [rows*cols,N,C,lh,lw] logits of one batch on one device")
-        logits = logits.contiguous()
-        keep.append(logits)
-        geometry.append((tuple(ys), tuple(xs)))
-        recs[i] = _lib.SlidePass(logits.data_ptr(), logits.shape[3], logits.shape[4], int(hs), int(ws), int(th), int(tw),
-                                 len(ys), len(xs), int(bool(flip)), float(weight))
-    if (conf is None) != (labels is None):
-        raise RuntimeError("sliding_vote: labels and the confusion matrix come together")
-    if labels is not None:
-        if not (isinstance(labels, torch.Tensor) and labels.is_cuda and labels.device == dev and
-                labels.dtype == torch.int64 and tuple(labels.shape) == (N, oh, ow) and labels.is_contiguous()):
-            raise RuntimeError("sliding_vote: dense int64 [N,out_h,out_w] device labels expected")
-        if not (isinstance(conf, torch.Tensor) and conf.is_cuda and conf.device == dev and conf.dtype == torch.int64 and
-                tuple(conf.shape) == (Cc, Cc) and conf.is_contiguous()):
-            raise RuntimeError("sliding_vote: conf must be a contiguous int64 [C,C] device tensor")
-    if not (want_scores or want_pred or labels is not None):
-        raise RuntimeError("sliding_vote: nothing asked for")
-    with torch.cuda.device(dev):
-        host, table = _slide_table(tuple(geometry), dev)
-        scores = torch.empty((N, Cc, oh, ow), dtype=torch.float32, device=dev) if want_scores else None
-        pred = torch.empty((N, oh, ow), dtype=torch.int32, device=dev) if want_pred else None
-        check(_lib.lib().dcfp_vote_sliding_f32(recs, len(passes), host, _p(table), N, Cc, H, W, oh, ow,
-                                               int(bool(align_corners)), _p(scores), _p(pred), _p(labels),
-                                               int(ignore_index), _p(conf), _stream()),
-              "sliding_vote")
-    return pred, scores
+    def records(passes, dev, N, Cc):
+        recs, keep, geometry = (_lib.SlidePass * len(passes))(), [], []
+        for i, (logits, (hs, ws), (th, tw), ys, xs, flip, weight) in enumerate(passes):
+            _require(logits, "logits")
+            ys, xs = _origins("sliding_vote", ys, "rows"), _origins("sliding_vote", xs, "columns")
+            if logits.dim() != 5 or tuple(logits.shape[:3]) != (len(ys) * len(xs), N, Cc) or logits.device != dev:
+                raise RuntimeError("sliding_vote: every pass holds [rows*cols,N,C,lh,lw] logits of one batch on one "
+                                   "device")
+            logits = logits.contiguous()
+            keep.append(logits)
+            geometry.append((tuple(ys), tuple(xs)))
+            recs[i] = _lib.SlidePass(logits.data_ptr(), logits.shape[3], logits.shape[4], int(hs), int(ws), int(th),
+                                     int(tw), len(ys), len(xs), int(bool(flip)), float(weight))
+
+        def lead():
+            host, table = _slide_table(tuple(geometry), dev)
+            return recs, len(keep), host, _p(table)
+        return lead
+    return _fused_vote("sliding_vote", "dcfp_vote_sliding_f32", passes, SLIDE_MAX_PASSES, "passes",
+                       "[T,N,C,lh,lw]", records, grid_hw, out_hw, align_corners, labels, conf, want_scores, want_pred,
+                       ignore_index)
 
 
 def label_boundary(labels, num_classes, d, background=255):

@@ -5,12 +5,13 @@ hands out prepared low-resolution logits, upsampled to the tile size as a model'
 A `pass` is (scale, logits [T,N,C,lh,lw], logits of the mirrored image's tiles or None); the stub is called per scale
 for the plain pass's tiles row-major, then for the mirrored pass's.  `chain(..., torch.float64)` is the truth,
 `chain(..., torch.float32)` the reference's own arithmetic; `tolerance` is what a test may allow the kernel (the rule of
-tests/_vote_ref.py)."""
+tests/_vote_common.py)."""
 from math import ceil
 
 import torch
 import torch.nn.functional as F
 
+from _vote_common import tolerance_of
 from oracle import evalmetrics
 
 SIX_SCALES = (0.5, 0.75, 1.0, 1.25, 1.5, 1.75)
@@ -96,10 +97,7 @@ def to_passes(passes, grid_hw, tile, device):
 
 
 def tolerance(passes, grid_hw, out_hw, tile, align_corners):
-    """-> (truth fp64, tol, e_ref, M): tol = 4 * e_ref + 2^-23 * M with e_ref = max |fp32 chain - fp64 chain| and
-    M = max |logits| (tests/_vote_ref.py gives the reasons for the two terms)."""
-    truth = chain(passes, grid_hw, out_hw, tile, align_corners, torch.float64)
-    ref32 = chain(passes, grid_hw, out_hw, tile, align_corners, torch.float32)
-    e_ref = float((ref32.double() - truth).abs().max())
-    M = max(float(t.abs().max()) for _, a, b in passes for t in (a, b) if t is not None)
-    return truth, 4.0 * e_ref + 2.0 ** -23 * M, e_ref, M
+    """-> (truth fp64, tol, e_ref, M) by the rule of _vote_common.tolerance_of."""
+    return tolerance_of(chain(passes, grid_hw, out_hw, tile, align_corners, torch.float64),
+                        chain(passes, grid_hw, out_hw, tile, align_corners, torch.float32),
+                        [t for _, a, b in passes for t in (a, b)])

@@ -7,6 +7,8 @@ truth, `chain(..., torch.float32)` the reference's own arithmetic; `tolerance` i
 import torch
 import torch.nn.functional as F
 
+from _vote_common import tolerance_of
+
 SIX_SCALES = (0.5, 0.75, 1.0, 1.25, 1.5, 1.75)
 
 
@@ -53,11 +55,7 @@ def to_maps(passes, device):
 
 
 def tolerance(passes, grid_hw, out_hw, align_corners):
-    """-> (truth fp64, tol, e_ref, M): tol = 4 * e_ref + 2^-23 * M with e_ref = max |fp32 chain - fp64 chain| and
-    M = max |logits|.  4: the kernel sums in another order than the two-pass chain; the second term is one fp32 unit of
-    the largest input, so that a luckily rounded reference does not demand more than fp32 holds."""
-    truth = chain(passes, grid_hw, out_hw, align_corners, torch.float64)
-    ref32 = chain(passes, grid_hw, out_hw, align_corners, torch.float32)
-    e_ref = float((ref32.double() - truth).abs().max())
-    M = max(float(t.abs().max()) for _, a, b in passes for t in (a, b) if t is not None)
-    return truth, 4.0 * e_ref + 2.0 ** -23 * M, e_ref, M
+    """-> (truth fp64, tol, e_ref, M) by the rule of _vote_common.tolerance_of."""
+    return tolerance_of(chain(passes, grid_hw, out_hw, align_corners, torch.float64),
+                        chain(passes, grid_hw, out_hw, align_corners, torch.float32),
+                        [t for _, a, b in passes for t in (a, b)])

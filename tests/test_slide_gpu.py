@@ -2,9 +2,10 @@
 of tools/evaluate.py's predict_batch against the reference's sliding-window chain in float64 (tests/_slide_ref.py).
 
 Tolerance, per case, from the reference itself on the same inputs: tol = 4 * e_ref + 2^-23 * M (e_ref = max |fp32 chain -
-fp64 chain|, M = max |logits|; _slide_ref.tolerance).  Scores lie within tol of float64; pred equals the float64 argmax
-wherever the float64 top-two gap exceeds 2 * tol, and the pixels left out are at most 0.5 % of a case; the fused
-confusion matrix equals ops.confusion_matrix of the kernel's own pred.
+fp64 chain|, M = max |logits|; _vote_common.tolerance_of).  Scores lie within tol of float64; pred equals the float64
+argmax wherever the float64 top-two gap exceeds 2 * tol, and the pixels left out are at most 0.5 % of a case
+(_vote_common.held_to_truth); the fused confusion matrix equals ops.confusion_matrix of the kernel's own pred.  The
+behaviour both votes share (labels, accumulation, refused arguments): tests/test_vote_shared_gpu.py.
 
 The stride comes from the tile height as the reference computes it, ceil(th * (1 - 1/3)) in double precision: 12 for
 17, 23 for 33 and 7 for 9 (9 * (1 - 1/3) is 6.000000000000001)."""
@@ -15,6 +16,7 @@ import pytest
 import torch
 
 import _slide_ref as sr
+from _vote_common import held_to_truth, labels_for
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
@@ -32,29 +34,6 @@ CASES = {
     "c2": (2, 2, (33, 41), (30, 37), (17, 17), True, (0.75, 1.0), True),
     "crop_1x1": (1, 19, (33, 41), (1, 1), (17, 17), True, (1.0, 1.5), True),
 }
-
-
-def labels_for(seed, N, C, out_hw, ignore=255):
-    g = torch.Generator().manual_seed(seed)
-    gt = torch.randint(0, C, (N,) + tuple(out_hw), generator=g)
-    gt[torch.rand(gt.shape, generator=g) < 0.1] = ignore
-    return gt
-
-
-def held_to_truth(what, scores, pred, truth, tol, e_ref, M):
-    err = float((scores.double().cpu() - truth).abs().max())
-    if truth.shape[1] > 1:
-        top = truth.topk(2, dim=1).values
-        decided = (top[:, 0] - top[:, 1]) > 2 * tol
-    else:
-        decided = torch.ones_like(truth[:, 0], dtype=torch.bool)
-    left_out = 1.0 - float(decided.float().mean())
-    wrong = int((pred.cpu().long() != truth.argmax(1))[decided].sum())
-    print(f"{what}: e_ref {e_ref:.3e} M {M:.2f} tol {tol:.3e} kernel err {err:.3e} left out {left_out:.5f} wrong {wrong}")
-    assert not bool(torch.isnan(truth).any())
-    assert err <= tol
-    assert wrong == 0
-    assert left_out <= 0.005
 
 
 @pytest.mark.parametrize("tag", list(CASES))
@@ -97,82 +76,6 @@ def test_gather_tiles_is_the_slicing_chain(hw, tile, flip, cuda):
     want = torch_tiles(image, tile, flip)
     assert tuple(got.shape) == (len(ys) * len(xs), 2, 3) + tile
     assert torch.equal(got.view(torch.int32), want.view(torch.int32))
-
-
-@pytest.fixture(scope="module")
-def small(cuda):
-    N, C, grid, crop, tile = 2, 19, (33, 41), (30, 37), (17, 17)
-    passes = sr.make_passes(5, N, C, grid, tile, (0.75, 1.0), True)
-    return N, C, grid, crop, sr.to_passes(passes, grid, tile, cuda)
-
-
-def test_all_ignore_leaves_conf_unchanged(small, cuda):
-    from dcfp_amd import ops
-    N, C, grid, crop, passes = small
-    conf = torch.arange(C * C, dtype=torch.int64, device=cuda).view(C, C).contiguous()
-    before = conf.clone()
-    gt = torch.full((N,) + crop, 255, dtype=torch.int64, device=cuda)
-    ops.sliding_vote(passes, grid, crop, True, labels=gt, conf=conf)
-    assert torch.equal(conf, before)
-
-
-def test_labels_outside_the_classes_are_skipped(small, cuda):
-    from dcfp_amd import ops
-    N, C, grid, crop, passes = small
-    gt = labels_for(3, N, C, crop)
-    g = torch.Generator().manual_seed(4)
-    r = torch.rand(gt.shape, generator=g)
-    gt[r < 0.1] = C            # no class, not ignore
-    gt[(r >= 0.1) & (r < 0.2)] = 254
-    gt[(r >= 0.2) & (r < 0.3)] = -1
-    gt = gt.to(cuda)
-    conf = torch.zeros((C, C), dtype=torch.int64, device=cuda)
-    pred, _ = ops.sliding_vote(passes, grid, crop, True, labels=gt, conf=conf)
-    assert int(conf.sum()) == int(((gt >= 0) & (gt < C)).sum())
-    assert torch.equal(conf, ops.confusion_matrix(pred, gt, C))
-    conf3 = torch.zeros((C, C), dtype=torch.int64, device=cuda)
-    ops.sliding_vote(passes, grid, crop, True, labels=gt, conf=conf3, ignore_index=3)
-    assert int(conf3.sum()) == int(((gt >= 0) & (gt < C) & (gt != 3)).sum())
-
-
-def test_two_calls_accumulate_and_repeat_bit_for_bit(small, cuda):
-    from dcfp_amd import ops
-    N, C, grid, crop, passes = small
-    gt = labels_for(9, N, C, crop).to(cuda)
-    conf = torch.zeros((C, C), dtype=torch.int64, device=cuda)
-    pred1, scores1 = ops.sliding_vote(passes, grid, crop, True, labels=gt, conf=conf, want_scores=True)
-    once = conf.clone()
-    pred2, scores2 = ops.sliding_vote(passes, grid, crop, True, labels=gt, conf=conf, want_scores=True)
-    assert torch.equal(conf, 2 * once)
-    assert torch.equal(pred1, pred2) and torch.equal(scores1.view(torch.int32), scores2.view(torch.int32))
-    fresh = torch.zeros((C, C), dtype=torch.int64, device=cuda)
-    ops.sliding_vote(passes, grid, crop, True, labels=gt, conf=fresh, want_pred=False)
-    assert torch.equal(fresh, once)
-
-
-def test_sliding_vote_argument_checks(small, cuda):
-    from dcfp_amd import ops
-    N, C, grid, crop, passes = small
-    with pytest.raises(RuntimeError):
-        ops.sliding_vote([], grid, crop, True)
-    with pytest.raises(RuntimeError):
-        ops.sliding_vote((passes * 5)[:17], grid, crop, True)                 # 17 passes
-    logits, hw, tile, ys, xs, flip, weight = passes[0]
-    with pytest.raises(RuntimeError):                                         # 33 tile rows
-        many = torch.zeros((33 * len(xs),) + tuple(logits.shape[1:]), device=cuda)
-        ops.sliding_vote([(many, hw, tile, list(range(33)), xs, flip, weight)], grid, crop, True)
-    with pytest.raises(RuntimeError):
-        ops.sliding_vote(passes, grid, (grid[0] + 1, grid[1]), True)
-    with pytest.raises(RuntimeError):
-        ops.sliding_vote(passes, grid, crop, True, conf=torch.zeros((C, C), dtype=torch.int64, device=cuda))
-    with pytest.raises(RuntimeError):
-        ops.sliding_vote([(logits.cpu(),) + passes[0][1:]], grid, crop, True)
-    with pytest.raises(RuntimeError):
-        ops.sliding_vote(passes, grid, crop, True, want_pred=False)
-    with pytest.raises(RuntimeError):                                         # a row of pixels under no tile
-        gap = [0] + [tile[0] + 1] * (len(ys) - 1)                              # row tile[0] is skipped
-        assert len(ys) == 2 and gap[1] < hw[0]
-        ops.sliding_vote([(logits, hw, tile, gap, xs, flip, weight)], grid, crop, True)
 
 
 class _Recorder:

@@ -154,19 +154,14 @@ def predict_batch(model, image, args, scales, fused, size, label=None, conf=None
     counted = False
     if args.whole and scales == [1.0] and not args.flip and not resized:
         pred = ev.predict_labels(model, image)[:, :size_scale[0], :size_scale[1]].contiguous()
-    elif args.whole and fused:
-        counted = not resized and conf is not None        # prediction, argmax and confusion: one launch
-        pred, scores = ev.predict_vote(model, image, scales, args.flip, args.align_corner, out_hw=size_scale,
-                                       labels=label if counted else None, conf=conf if counted else None,
-                                       want_scores=resized, ignore_index=args.ignore_label)
-        if resized:
-            pred = ops.upsample_argmax(scores, size, False)
-    elif not args.whole and getattr(args, "fused_sliding", False):
-        counted = not resized and conf is not None        # tiles, vote, argmax and confusion: one launch after the network
-        pred, scores = ev.predict_sliding_vote(model, image, (h, w), scales, args.flip, args.align_corner,
-                                               out_hw=size_scale, labels=label if counted else None,
-                                               conf=conf if counted else None, want_scores=resized,
-                                               ignore_index=args.ignore_label)
+    elif (fused if args.whole else getattr(args, "fused_sliding", False)):
+        counted = not resized and conf is not None        # vote, argmax and confusion: one launch after the network
+        outputs = dict(out_hw=size_scale, labels=label if counted else None, conf=conf if counted else None,
+                       want_scores=resized, ignore_index=args.ignore_label)
+        if args.whole:
+            pred, scores = ev.predict_vote(model, image, scales, args.flip, args.align_corner, **outputs)
+        else:
+            pred, scores = ev.predict_sliding_vote(model, image, (h, w), scales, args.flip, args.align_corner, **outputs)
         if resized:
             pred = ops.upsample_argmax(scores, size, False)
     else:
