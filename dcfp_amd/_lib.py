@@ -48,6 +48,24 @@ class SgdEntry(C.Structure):
                 ("weight_decay", C.c_float), ("pad_", C.c_int32)]
 
 
+class GateEntry(C.Structure):
+    """DcfpGateEntry: one scored BatchNorm layer of the gate kernels (Taylor score, slimming L1 term)."""
+    _fields_ = [("gamma", C.c_void_p), ("beta", C.c_void_p), ("ggrad", C.c_void_p), ("bgrad", C.c_void_p),
+                ("score", C.c_void_p), ("n", C.c_int32), ("pad_", C.c_int32)]
+
+
+class FilterEntry(C.Structure):
+    """DcfpFilterEntry: one matrix of `rows` rows of K contiguous floats of a filter_reduce launch."""
+    _fields_ = [("w", C.c_void_p), ("g", C.c_void_p), ("out", C.c_void_p), ("rows", C.c_int32), ("K", C.c_int32),
+                ("first_unit", C.c_int64)]
+
+
+class FpgmEntry(C.Structure):
+    """DcfpFpgmEntry: one matrix [C, K] of an fpgm call."""
+    _fields_ = [("w", C.c_void_p), ("out", C.c_void_p), ("C", C.c_int32), ("K", C.c_int32),
+                ("first_tile", C.c_int64), ("ws_off", C.c_int64)]
+
+
 class AdamEntry(C.Structure):
     """DcfpAdamEntry: one tensor of a multi-tensor AdamW launch."""
     _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
@@ -103,6 +121,8 @@ class SlidePass(C.Structure):
 SLIDE_MAX_PASSES, SLIDE_MAX_TILES_PER_AXIS = 16, 32    # DCFP_SLIDE_MAX_* of include/dcfp_hip.h
 AUG_SATURATION, AUG_HUE = 1, 2
 SGD_CHUNK = 16384
+FILTER_ABS_SUM, FILTER_L2, FILTER_DOT_SQ_ACC = 0, 1, 2    # DCFP_FILTER_* of include/dcfp_hip.h
+FPGM_TILE = 64                                            # DCFP_FPGM_TILE
 CONV_FWD, CONV_DGRAD, CONV_WGRAD = 0, 1, 2
 E_BADDESC, E_UNSUPPORTED, E_WORKSPACE = -1, -2, -3   # DCFP_E_* of include/dcfp_hip.h
 
@@ -222,6 +242,12 @@ SIGNATURES = {
     "dcfp_pyramid_pool_nhwc_f16": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
     "dcfp_kd_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
     "dcfp_kd_fwd_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _P, _Z, _P, _P, _P]),
+    "dcfp_gate_taylor_f32": (_I, [_P, _I, _P]),
+    "dcfp_gate_l1reg_f32": (_I, [_P, _I, _F, _P]),
+    "dcfp_filter_reduce_units": (_L, [_I, _I]),
+    "dcfp_filter_reduce_f32": (_I, [_P, _I, _L, _I, _P]),
+    "dcfp_fpgm_workspace_bytes": (_Z, [_I]),
+    "dcfp_fpgm_f32": (_I, [_P, _I, _L, _P, _Z, _P]),
 }
 
 

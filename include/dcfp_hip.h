@@ -872,6 +872,75 @@ int dcfp_kd_fwd_f32(const float* s, const float* t, int mode, int N, int C, int 
                     size_t workspace_bytes, float* loss_out /* device scalar */, float* dlogits /* may be null */,
                     dcfp_stream_t stream);
 
+/* ------------------------------------------------ baseline pruning criteria (csrc/score.hip)
+ * One fp32 score per output channel of every scored BatchNorm layer; larger means keep.  Every entry point takes a
+ * DEVICE array of records (built on the host, uploaded once), returns DCFP_OK for a count of 0 and DCFP_E_BADDESC for a
+ * null table with a positive count or a negative count (checked before any HIP call), uses no atomics and combines in
+ * a fixed order: two calls on the same inputs leave the same bits.
+ *
+ * Gate kernels: one launch for all layers, one block per layer, n floats each.
+ *   dcfp_gate_taylor_f32   t = fadd(fmul(gamma, ggrad), fmul(beta, bgrad)); score = fadd(score, fmul(t, t))
+ *                          (Molchanov et al. 2019 on the BN gate; the caller divides by its step count)
+ *   dcfp_gate_l1reg_f32    ggrad = fadd(ggrad, fmul(lambda, sign(gamma))), sign(0) = 0 and ggrad then stays as it is
+ *                          (the sparsity term of Liu et al. 2017, added to the gradient before the optimizer step)
+ * Every product and sum is rounded on its own, in this order: a float32 restatement done one operation at a time gives
+ * the same bits, and exact zeros stay exact (the contract of dcfp_eic_update_f32). */
+typedef struct DcfpGateEntry {
+    const float* gamma;
+    const float* beta;
+    float* ggrad; /* written by dcfp_gate_l1reg_f32 only */
+    const float* bgrad;
+    float* score; /* dcfp_gate_taylor_f32 only; dcfp_gate_l1reg_f32 reads gamma and ggrad alone */
+    int32_t n;
+    int32_t pad_;
+} DcfpGateEntry;
+int dcfp_gate_taylor_f32(const DcfpGateEntry* table, int n_layers, dcfp_stream_t stream);
+int dcfp_gate_l1reg_f32(const DcfpGateEntry* table, int n_layers, float lambda, dcfp_stream_t stream);
+
+/* Row reductions over MANY matrices in one launch: entry = `rows` rows of K contiguous floats (a conv weight
+ * [C, Cin, kh, kw] is C rows of K = Cin*kh*kw), any 4-byte aligned base, any K >= 1.
+ *   DCFP_FILTER_ABS_SUM     out[r]  = sum_k |w[r,k]|            (g unused, may be null)
+ *   DCFP_FILTER_L2          out[r]  = sqrt(sum_k w[r,k]^2)      (g unused, may be null)
+ *   DCFP_FILTER_DOT_SQ_ACC  out[r] += (sum_k w[r,k]*g[r,k])^2   (first-order Taylor on the filter)
+ * The split rule: a row is summed by a GROUP of G lanes, G = 8 for K <= 32, 16 for K <= 128, 64 for K <= 1024 and 256
+ * above; a block of 256 threads is one UNIT of 256/G rows.  dcfp_filter_reduce_units(rows, K) is the unit count of an
+ * entry (0 for sizes < 1); first_unit is the prefix sum of it over the earlier entries and total_units the sum over
+ * all.  Units past an entry's rows do nothing, so a wrong prefix gives wrong sums but touches no other memory. */
+#define DCFP_FILTER_ABS_SUM 0
+#define DCFP_FILTER_L2 1
+#define DCFP_FILTER_DOT_SQ_ACC 2
+typedef struct DcfpFilterEntry {
+    const float* w;
+    const float* g;
+    float* out;
+    int32_t rows;
+    int32_t K;
+    int64_t first_unit;
+} DcfpFilterEntry;
+int64_t dcfp_filter_reduce_units(int rows, int K);
+int dcfp_filter_reduce_f32(const DcfpFilterEntry* table, int n_entries, int64_t total_units, int op,
+                           dcfp_stream_t stream);
+
+/* FPGM (He et al. 2019): out[i] = sum_j sqrt(sum_k (w[i,k] - w[j,k])^2) for MANY matrices [C, K] in two launches.
+ * Distances are sums of squared DIFFERENCES (never n_i + n_j - 2 G_ij): equal rows are at distance exactly 0, no
+ * distance is NaN for finite input, C = 1 gives 0.  Launch 1: one block per (i tile, j tile) of DCFP_FPGM_TILE rows
+ * each, K in LDS chunks, writes the row sums over its j tile to the workspace; launch 2: one block per matrix adds
+ * them, j tiles ascending.  An entry's tiles number ceil(C/TILE)^2: first_tile is the prefix sum over the earlier
+ * entries, total_tiles the sum.  ws_off: the entry's offset into the workspace in floats, the prefix sum of
+ * dcfp_fpgm_workspace_bytes(C) / 4 (a multiple of 64 floats; 0 bytes for C < 1). */
+#define DCFP_FPGM_TILE 64
+typedef struct DcfpFpgmEntry {
+    const float* w;
+    float* out;
+    int32_t C;
+    int32_t K;
+    int64_t first_tile;
+    int64_t ws_off;
+} DcfpFpgmEntry;
+size_t dcfp_fpgm_workspace_bytes(int C);
+int dcfp_fpgm_f32(const DcfpFpgmEntry* table, int n_entries, int64_t total_tiles, void* workspace,
+                  size_t workspace_bytes, dcfp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,7 @@ import torch  # noqa: E402
 
 from dcfp_amd import networks  # noqa: E402
 from dcfp_amd.pruners import init_pruned_model  # noqa: E402
+from dcfp_amd.pruners.baseline_pruner import SCORE_NORMS, ScorePruner  # noqa: E402
 from dcfp_amd.pruners.dcfp_pruner import DCFPPruner  # noqa: E402
 from dcfp_amd.pruners.random_pruner import RandomChannelPruner  # noqa: E402
 from dcfp_amd.utils.flops_counter import get_model_complexity_info  # noqa: E402
@@ -46,6 +47,9 @@ def get_parser():
     p.add_argument("--prune-type", type=str, default="dcfp", choices=["dcfp", "random"],
                    help="dcfp: the scores of --score-path; random: the baseline that ignores the weights")
     p.add_argument("--prune-seed", type=int, default=None, help="--prune-type random: seed of the draw")
+    p.add_argument("--score-norm", type=str, default="none", choices=list(SCORE_NORMS),
+                   help="rescale the scores of --score-path per layer before the global thresholds: l2 (s / ||s||) or "
+                        "mean (s / mean(s)), for criteria whose scale depends on the layer (filter norms, fpgm)")
     return p
 
 
@@ -74,6 +78,9 @@ def main(argv=None):
     while True:
         if args.prune_type == "random":
             pruner = RandomChannelPruner(global_percent=global_percent, layer_keep=0.02, seed=args.prune_seed)
+        elif args.score_norm != "none":
+            pruner = ScorePruner(global_percent=global_percent, layer_keep=0.02, score_file=args.score_path,
+                                 score_norm=args.score_norm)
         else:
             pruner = DCFPPruner(global_percent=global_percent, layer_keep=0.02, score_file=args.score_path)
         sub_model, channel_cfg = pruner.prune_model(copy.deepcopy(seg_model), except_start_keys=["conv_deepsup"])

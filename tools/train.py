@@ -4,6 +4,8 @@ the model / optimiser / loss / pruning options).  Without --dataset it runs over
 batches; with --dataset CS|CTX|COCO (and the reference's data flags) it reads a list file through dcfp_amd.datasets,
 whose augmentation chain runs on the device (ADE is not built).
 `--loss-type ...,kd --teacher-from CKPT` adds the distillation term against a frozen teacher.
+`--prune-type taylor | taylor_w` scores by first-order Taylor instead of `dcfp`, `--slim-lambda` adds the Network
+Slimming L1 term to the BN weight gradients (the baseline criteria).
 One process per GPU: `python -m torch.distributed.run --nproc-per-node N tools/train.py ...`."""
 import argparse
 import json
@@ -60,7 +62,12 @@ def get_parser():
     p.add_argument("--deepsup", type=str2bool, default="True")
     p.add_argument("--loss-type", type=str, default="ce")
     p.add_argument("--loss-para", type=str, default="{}")
-    p.add_argument("--prune-type", type=str, default=None)
+    p.add_argument("--prune-type", type=str, default=None,
+                   help="score while training and write score.pth: dcfp (the EIC score), taylor (first-order Taylor on "
+                        "the BN gate) or taylor_w (on the filters); DESIGN §17")
+    p.add_argument("--slim-lambda", type=float, default=0.0,
+                   help="Network Slimming: add lambda * sign(gamma) to the BN weight gradients before every optimizer "
+                        "step (0 = off), in any --prune-type")
     p.add_argument("--channel-cfg", type=str, default=None)
     p.add_argument("--teacher-from", type=str, default=None,
                    help="checkpoint of the frozen teacher of --loss-type ...,kd: same --model, --backbone and classes as "
@@ -101,10 +108,17 @@ class SyntheticDataset:
         return images.to(device, non_blocking=True), labels.to(device, non_blocking=True)
 
 
+TAYLOR_TYPES = {"taylor": "gate", "taylor_w": "weight"}      # --prune-type -> pruners.taylor_pruning(mode=...)
+
+
 def check_args(args):
     """Argument combinations that cannot run, refused before anything is built."""
     if "kd" in args.loss_type.split(",") and not args.teacher_from:
         raise ValueError("--loss-type %s: the kd term needs a teacher, give --teacher-from CKPT" % args.loss_type)
+    if args.prune_type is not None and args.prune_type.startswith("taylor") and args.prune_type not in TAYLOR_TYPES:
+        raise ValueError("--prune-type %s: the Taylor scorers are %s" % (args.prune_type, ", ".join(sorted(TAYLOR_TYPES))))
+    if not args.slim_lambda >= 0.0:
+        raise ValueError("--slim-lambda %r: the sparsity weight is >= 0 (0 = off)" % args.slim_lambda)
 
 
 def build_teacher(args, num_classes, device):
@@ -163,6 +177,9 @@ def main(argv=None):
         wants_kd = "kd" in args.loss_type.split(",")
         teacher = build_teacher(args, dataset.num_classes, device) if wants_kd else None
         train_pruning = pruners.dcfp_pruning(seg_model, 0.999) if args.prune_type == "dcfp" else None
+        if args.prune_type in TAYLOR_TYPES:
+            train_pruning = pruners.taylor_pruning(seg_model, TAYLOR_TYPES[args.prune_type])
+        slimming = pruners.slimming_regularizer(seg_model, args.slim_lambda) if args.slim_lambda > 0 else None
         model = engine.data_parallel(seg_model)
         model.train()
         per_rank = max(1, args.batch_size // engine.world_size)
@@ -208,6 +225,8 @@ def main(argv=None):
             loss["loss"].backward()
             if train_pruning is not None:
                 train_pruning.step(seg_model)
+            if slimming is not None:
+                slimming.step(seg_model)
             optimizer.step()
             if args.log_time:
                 torch.cuda.synchronize()
