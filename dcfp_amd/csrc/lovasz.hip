@@ -1,0 +1,599 @@
+// lovasz.hip — Lovasz-Softmax loss (Berman, Triki, Blaschko, CVPR 2018; classes = 'present') of the bilinearly
+// upsampled low-resolution logits, without a sort and without the N x C x H x W probabilities.
+//
+// Per valid pixel (label in [0, C), not ignore_index) and class c:  z = bilinear upsample of the logits (bilinear.h, the
+// interpolation expression of upsample_ce_fwd_kernel),  p = exp(z - lse),  e = (label == c) ? 1 - p : p,
+//     q = min(2^20, floor(e * 2^20 + 0.5)),      b = min(B - 1, q >> (20 - log2 B)),       B = bins.
+// Per class and bin four integers: nF / nB count the foreground (label == c) / background pixels of the bin, SF / SB
+// add their q.  With G = sum_b nF[b] (> 0: the class is present) and F_above / G_above the foreground / background
+// counts of all higher bins,
+//     I0 = G - F_above,  U0 = G + G_above,  I1 = I0 - nF[b],  U1 = U0 + nB[b],
+//     wF[b] = (1/U0 + 1/U1) / 2,     wB[b] = (I0 + I1) / (2 U0 U1)
+// - the mean of the exact Lovasz gradients of the two sort orders of a tied bin (foreground first, background first) -
+//     loss_c = 2^-20 * sum_b (wF[b] SF[b] + wB[b] SB[b]),        loss = mean of loss_c over the present classes.
+// The weights are locally constant in the logits:  dloss/dz_k = p_k (a_k - sum_c a_c p_c),  a_c = -wF[b]/P for the
+// label's class, +wB[b]/P for any other present class, 0 for an absent one; then the bilinear adjoint.
+//
+// Kernels.  lovasz_term() below is the only place that computes z, p, q and b; every kernel calls it, and fp contraction
+// is off in this file, so forward and backward put every (pixel, class) into the same bin bit for bit.
+//   histogram  a workgroup owns a tile of pixels: writes their log-sum-exp, then loops over chunks of classes whose
+//              accumulators fit its 64 KiB of LDS (4096 / B classes): zero, one 64-bit LDS add per (pixel, class)
+//              (count in the high word, the sum of q - (b << shift) in the low word: at most 2^14 per pixel and 2^16
+//              pixels per tile), then one integer atomic per non-empty accumulator into the global table.  Integer
+//              adds only: the table does not depend on the order of arrival.
+//   scan       one workgroup per class: suffix sums over the bins, the weights and loss_c in fp64 in a fixed order;
+//              a last kernel counts the present classes P, writes the loss and the fp32 table [C][B][2] = (wF, wB) / P.
+//   backward   one pass writes A = sum_c a_c p_c per pixel; a gather organised by cells, in the manner of
+//              upsample_ce_bwd_cells_chunk_kernel, adds wy wx p_c (a_c - A) over the destination pixels of every
+//              low-resolution element, each pixel evaluated once per window of 20 classes.  No atomics.
+//   errors     q of every (n, c, Y, X) as uint32, 0xFFFFFFFF at invalid pixels: for tests and for looking at the
+//              error distribution, never part of a training step.
+#include <math.h>
+
+#include "bilinear.h"
+#include "common.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+using namespace dcfp_bilinear;
+
+constexpr int kQ = 20;                       // q = e * 2^20, rounded
+constexpr int kThreads = 256;
+constexpr int kHistThreads = 512;
+constexpr int kHistSlots = 4096;             // (class, bin) pairs of a chunk: 4096 x 2 x 8 B = 64 KiB of LDS
+constexpr long long kTileMin = 2048, kTileMax = 65536;      // pixels per histogram workgroup (low word: 2^16 * 2^14)
+constexpr int kMaxBlocks = 1 << 16;
+
+// the stencil of a destination pixel: four offsets into a class plane and the four lerp factors
+struct Tap {
+    int o00, o01, o10, o11;
+    float h0, h1, w0, w1;
+};
+
+__device__ __forceinline__ Tap tap_of(const Lerp& Lh, const Lerp& Lw, int w) {
+    Tap t;
+    t.o00 = Lh.i0 * w + Lw.i0; t.o01 = Lh.i0 * w + Lw.i1;
+    t.o10 = Lh.i1 * w + Lw.i0; t.o11 = Lh.i1 * w + Lw.i1;
+    t.h0 = Lh.l0; t.h1 = Lh.l1; t.w0 = Lw.l0; t.w1 = Lw.l1;
+    return t;
+}
+
+__device__ __forceinline__ float logit_at(const float* __restrict__ p, const Tap& t) {
+    return t.h0 * (t.w0 * p[t.o00] + t.w1 * p[t.o01]) + t.h1 * (t.w0 * p[t.o10] + t.w1 * p[t.o11]);
+}
+
+struct Term {
+    float z, p;
+    unsigned q;
+    int b;
+};
+
+// (pixel, class) -> z, p, q, b from the class's four stencil values; shift = 20 - log2 B.  The interpolation is the
+// expression of logit_at() on the same values, so it does not matter whether a kernel holds them in registers.
+__device__ __forceinline__ Term lovasz_term(float v00, float v01, float v10, float v11, float h0, float h1, float w0,
+                                            float w1, float lse, bool fg, int shift, int last_bin) {
+    Term r;
+    r.z = h0 * (w0 * v00 + w1 * v01) + h1 * (w0 * v10 + w1 * v11);
+    r.p = expf(r.z - lse);
+    const float e = fg ? 1.0f - r.p : r.p;
+    const float s = floorf(e * (float)(1 << kQ) + 0.5f);          // exact: a power-of-two scale, then |x| < 2^23
+    r.q = s <= 0.0f ? 0u : (s >= (float)(1 << kQ) ? (1u << kQ) : (unsigned)s);
+    const int b = (int)(r.q >> shift);
+    r.b = b > last_bin ? last_bin : b;
+    return r;
+}
+
+// the same from the class's low-resolution plane
+__device__ __forceinline__ Term lovasz_term(const float* __restrict__ plane, const Tap& t, float lse, bool fg,
+                                            int shift, int last_bin) {
+    return lovasz_term(plane[t.o00], plane[t.o01], plane[t.o10], plane[t.o11], t.h0, t.h1, t.w0, t.w1, lse, fg, shift,
+                       last_bin);
+}
+
+// log-sum-exp of the pixel's C interpolated logits (the running form of upsample_ce_fwd_kernel)
+__device__ __forceinline__ float lse_at(const float* __restrict__ base, long long plane, int C, const Tap& t) {
+    float m = -INFINITY, s = 0.f;
+    for (int c = 0; c < C; ++c) {
+        const float z = logit_at(base + c * plane, t);
+        if (z > m) {
+            s = s * expf(m - z) + 1.f;
+            m = z;
+        } else {
+            s += expf(z - m);
+        }
+    }
+    return m + logf(s);
+}
+
+__device__ __forceinline__ bool label_valid(long long label, int C, int ignore_index) {
+    return label >= 0 && label < C && label != ignore_index;
+}
+
+struct Pix {
+    int n, Y, X;
+};
+
+__device__ __forceinline__ Pix pix_of(long long pix, int H, int W) {
+    Pix r;
+    r.X = (int)(pix % W);
+    const long long t = pix / W;
+    r.Y = (int)(t % H);
+    r.n = (int)(t / H);
+    return r;
+}
+
+// ------------------------------------------------------------------------------------------------ histogram
+template <bool ALIGN>
+__global__ void __launch_bounds__(kHistThreads)
+lovasz_hist_kernel(const float* __restrict__ logits, const long long* __restrict__ labels, int ignore_index, int N, int C,
+                   int h, int w, int H, int W, float sh, float sw, int log2B, int chunk, long long tile,
+                   float* lse_out, unsigned long long* __restrict__ SF, unsigned long long* __restrict__ SB,
+                   unsigned int* __restrict__ nF, unsigned int* __restrict__ nB) {
+    __shared__ unsigned long long acc[kHistSlots][2];       // [class of the chunk * B + bin][foreground, background]
+    const int B = 1 << log2B, shift = kQ - log2B;
+    const long long total = (long long)N * H * W, plane = (long long)h * w;
+    const long long start = (long long)blockIdx.x * tile;
+    const long long end = start + tile < total ? start + tile : total;
+    const int tid = threadIdx.x;
+
+    for (long long pix = start + tid; pix < end; pix += kHistThreads) {
+        const Pix P = pix_of(pix, H, W);
+        const Tap t = tap_of(lerp_of<ALIGN>(P.Y, sh, h), lerp_of<ALIGN>(P.X, sw, w), w);
+        lse_out[pix] = lse_at(logits + (long long)P.n * C * plane, plane, C, t);
+    }
+    for (int c0 = 0; c0 < C; c0 += chunk) {
+        const int nc = C - c0 < chunk ? C - c0 : chunk;
+        for (int i = tid; i < nc * B; i += kHistThreads) acc[i][0] = acc[i][1] = 0ull;
+        __syncthreads();
+        for (long long pix = start + tid; pix < end; pix += kHistThreads) {       // the pixels this thread wrote lse for
+            const long long label = labels[pix];
+            if (!label_valid(label, C, ignore_index)) continue;
+            const Pix P = pix_of(pix, H, W);
+            const Tap t = tap_of(lerp_of<ALIGN>(P.Y, sh, h), lerp_of<ALIGN>(P.X, sw, w), w);
+            const float lse = lse_out[pix];
+            const float* base = logits + ((long long)P.n * C + c0) * plane;
+            for (int k = 0; k < nc; ++k) {
+                const bool fg = label == c0 + k;
+                const Term r = lovasz_term(base + k * plane, t, lse, fg, shift, B - 1);
+                const unsigned low = r.q - ((unsigned)r.b << shift);              // <= 2^shift <= 2^14
+                atomicAdd(&acc[k * B + r.b][fg ? 0 : 1], (1ull << 32) | low);
+            }
+        }
+        __syncthreads();
+        for (int i = tid; i < nc * B; i += kHistThreads) {
+            const unsigned long long base_q = (unsigned long long)(i & (B - 1)) << shift;
+            const long long g = (long long)c0 * B + i;
+            const unsigned long long f = acc[i][0], bk = acc[i][1];
+            if (f) {
+                atomicAdd(&nF[g], (unsigned)(f >> 32));
+                atomicAdd(&SF[g], (f & 0xffffffffull) + (f >> 32) * base_q);
+            }
+            if (bk) {
+                atomicAdd(&nB[g], (unsigned)(bk >> 32));
+                atomicAdd(&SB[g], (bk & 0xffffffffull) + (bk >> 32) * base_q);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ scan
+// One workgroup per class.  Thread t owns the B / nthr bins from t * per; wraw[c][b] = (wF, wB) in fp64.
+__global__ void __launch_bounds__(kThreads)
+lovasz_scan_kernel(const unsigned int* __restrict__ nF, const unsigned int* __restrict__ nB,
+                   const unsigned long long* __restrict__ SF, const unsigned long long* __restrict__ SB, int log2B,
+                   double* __restrict__ wraw, double* __restrict__ loss_c, long long* __restrict__ fg_count) {
+    __shared__ long long tF[kThreads], tB[kThreads];
+    __shared__ double part[kThreads];
+    const int B = 1 << log2B, c = blockIdx.x, t = threadIdx.x;
+    const int per = B > kThreads ? B / kThreads : 1, nthr = B / per;
+    const long long row = (long long)c * B;
+    long long f = 0, g = 0;
+    if (t < nthr)
+        for (int b = t * per; b < (t + 1) * per; ++b) {
+            f += nF[row + b];
+            g += nB[row + b];
+        }
+    tF[t] = f; tB[t] = g;
+    __syncthreads();
+    long long G = 0, Fa = 0, Ga = 0;            // G: the class's foreground pixels; Fa / Ga: counts of the bins above mine
+    for (int u = 0; u < nthr; ++u) {
+        G += tF[u];
+        if (u > t) { Fa += tF[u]; Ga += tB[u]; }
+    }
+    double acc = 0.0;
+    if (t < nthr) {
+        for (int b = (t + 1) * per - 1; b >= t * per; --b) {
+            double wf = 0.0, wb = 0.0;
+            const long long cf = nF[row + b], cb = nB[row + b];
+            if (G > 0) {
+                const long long I0 = G - Fa, U0 = G + Ga, I1 = I0 - cf, U1 = U0 + cb;
+                wf = (1.0 / (double)U0 + 1.0 / (double)U1) / 2.0;
+                wb = (double)(I0 + I1) / (2.0 * (double)U0 * (double)U1);
+                acc += wf * (double)SF[row + b] + wb * (double)SB[row + b];
+            }
+            wraw[(row + b) * 2 + 0] = wf;
+            wraw[(row + b) * 2 + 1] = wb;
+            Fa += cf; Ga += cb;
+        }
+    }
+    part[t] = acc;
+    __syncthreads();
+    if (t == 0) {
+        double s = 0.0;
+        for (int u = nthr - 1; u >= 0; --u) s += part[u];        // from the highest bins down, always in this order
+        loss_c[c] = s * (1.0 / (double)(1 << kQ));
+        fg_count[c] = G;
+    }
+}
+
+// P = present classes; loss = sum_c loss_c / P (block 0); table = (float)(wraw / P), zeros where P == 0
+__global__ void __launch_bounds__(kThreads)
+lovasz_final_kernel(const double* __restrict__ wraw, const double* __restrict__ loss_c,
+                    const long long* __restrict__ fg_count, int C, long long n_table, float* __restrict__ table,
+                    float* __restrict__ loss_out) {
+    __shared__ int present;
+    if (threadIdx.x == 0) {
+        int P = 0;
+        for (int c = 0; c < C; ++c) P += fg_count[c] > 0 ? 1 : 0;
+        present = P;
+        if (blockIdx.x == 0) {
+            double s = 0.0;
+            for (int c = 0; c < C; ++c)
+                if (fg_count[c] > 0) s += loss_c[c];
+            loss_out[0] = P > 0 ? (float)(s / (double)P) : 0.0f;
+        }
+    }
+    __syncthreads();
+    const int P = present;
+    for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n_table; i += (long long)gridDim.x * kThreads)
+        table[i] = P > 0 ? (float)(wraw[i] / (double)P) : 0.0f;
+}
+
+// ------------------------------------------------------------------------------------------------ backward
+// a_c of a (pixel, class): -wF[b] for the label's class, +wB[b] otherwise (the table is divided by P, 0 when absent)
+__device__ __forceinline__ float coeff_of(const float* __restrict__ table, int c, int B, const Term& r, bool fg) {
+    const float v = table[((long long)c * B + r.b) * 2 + (fg ? 0 : 1)];
+    return fg ? -v : v;
+}
+
+template <bool ALIGN>
+__global__ void __launch_bounds__(kThreads)
+lovasz_asum_kernel(const float* __restrict__ logits, const long long* __restrict__ labels, int ignore_index, int N, int C,
+                   int h, int w, int H, int W, float sh, float sw, int log2B, const float* __restrict__ lse,
+                   const float* __restrict__ table, float* __restrict__ asum) {
+    const int B = 1 << log2B, shift = kQ - log2B;
+    const long long total = (long long)N * H * W, plane = (long long)h * w;
+    for (long long pix = (long long)blockIdx.x * kThreads + threadIdx.x; pix < total;
+         pix += (long long)gridDim.x * kThreads) {
+        const long long label = labels[pix];
+        float A = 0.f;
+        if (label_valid(label, C, ignore_index)) {
+            const Pix P = pix_of(pix, H, W);
+            const Tap t = tap_of(lerp_of<ALIGN>(P.Y, sh, h), lerp_of<ALIGN>(P.X, sw, w), w);
+            const float* base = logits + (long long)P.n * C * plane;
+            const float ls = lse[pix];
+            for (int c = 0; c < C; ++c) {
+                const bool fg = label == c;
+                const Term r = lovasz_term(base + c * plane, t, ls, fg, shift, B - 1);
+                A += coeff_of(table, c, B, r, fg) * r.p;
+            }
+        }
+        asum[pix] = A;
+    }
+}
+
+// The gather, organised by CELLS as upsample_ce_bwd_cells_chunk_kernel is.  The cell of a destination pixel is the
+// low-resolution position (i0, j0) its stencil starts at; a pixel lies in exactly one cell and touches only that cell's
+// four corners.  A lane pair owns a cell and a window of CT classes [c0, c0 + CT): it holds the four corner logit vectors
+// in registers, evaluates each destination pixel of the cell once (label, lse, A and the stencil once per pixel, not
+// once per class and corner) and accumulates the four corner sums.  A workgroup covers 7 x 15 low-resolution outputs =
+// 8 x 16 cells (one halo row and column recomputed by the neighbour), parks the corner sums in LDS and adds, per output
+// and class, the <= 4 (cell, corner) terms that land on it in a fixed order: no atomics, two calls leave the same bits.
+// A phantom class of the tail window is never loaded, evaluated or stored.
+constexpr int kCellTH = 7, kCellTW = 15, kCellThreads = 256;
+constexpr int kCellCount = (kCellTH + 1) * (kCellTW + 1);
+constexpr int kCellCT = 20;            // classes per window: 19 in one, 4 x 20 accumulators and corners per lane
+
+template <bool ALIGN, int CT, bool TAIL>
+__device__ __forceinline__ void lovasz_bwd_cells_body(
+    float (*corner)[4][CT + 1], const float* __restrict__ base /* logits of (n, c0) */,
+    const long long* __restrict__ lab, const float* __restrict__ ls, const float* __restrict__ as,
+    const float* __restrict__ table /* of class c0 */, int ignore_index, int C, int c0, int nc, int h, int w, int H, int W,
+    float sh, float sw, int shift, int B, float gs, float* __restrict__ out /* dlogits of (n, c0) */, int I0, int J0) {
+    const int tid = threadIdx.x;
+    const long long plane = (long long)h * w;
+    const int cell = tid >> 1, part = tid & 1;
+    if (cell < kCellCount) {
+        const int ci = I0 - 1 + cell / (kCellTW + 1), cj = J0 - 1 + cell % (kCellTW + 1);
+        float a00[CT], a01[CT], a10[CT], a11[CT];
+#pragma unroll
+        for (int c = 0; c < CT; ++c) a00[c] = a01[c] = a10[c] = a11[c] = 0.f;
+        if (ci >= 0 && ci < h && cj >= 0 && cj < w) {
+            const int i1 = ci + (ci < h - 1 ? 1 : 0), j1 = cj + (cj < w - 1 ? 1 : 0);
+            float p00[CT], p01[CT], p10[CT], p11[CT];
+#pragma unroll
+            for (int c = 0; c < CT; ++c) {
+                p00[c] = p01[c] = p10[c] = p11[c] = 0.f;
+                if (TAIL && c >= nc) continue;
+                const float* p = base + c * plane;
+                p00[c] = p[ci * w + cj]; p01[c] = p[ci * w + j1];
+                p10[c] = p[i1 * w + cj]; p11[c] = p[i1 * w + j1];
+            }
+            int ylo, yhi, xlo, xhi;
+            dst_range<ALIGN>(ci, sh, H, ylo, yhi);
+            dst_range<ALIGN>(cj, sw, W, xlo, xhi);
+            for (int Y = ylo + part; Y <= yhi; Y += 2) {
+                const Lerp Lh = lerp_of<ALIGN>(Y, sh, h);
+                if (Lh.i0 != ci) continue;
+                for (int X = xlo; X <= xhi; ++X) {
+                    const Lerp Lw = lerp_of<ALIGN>(X, sw, w);
+                    if (Lw.i0 != cj) continue;
+                    const long long q = (long long)Y * W + X;
+                    const long long label = lab[q];
+                    if (!label_valid(label, C, ignore_index)) continue;
+                    const float lq = ls[q], Aq = as[q];
+                    const long long lrel = label - c0;      // the label's position in this window, if it is in it
+                    const float w00 = Lh.l0 * Lw.l0, w01 = Lh.l0 * Lw.l1;
+                    const float w10 = Lh.l1 * Lw.l0, w11 = Lh.l1 * Lw.l1;
+#pragma unroll
+                    for (int c = 0; c < CT; ++c) {
+                        if (TAIL && c >= nc) continue;
+                        const bool fg = lrel == c;
+                        const Term r = lovasz_term(p00[c], p01[c], p10[c], p11[c], Lh.l0, Lh.l1, Lw.l0, Lw.l1, lq, fg,
+                                                   shift, B - 1);
+                        const float g = r.p * (coeff_of(table, c, B, r, fg) - Aq);
+                        a00[c] += w00 * g; a01[c] += w01 * g;
+                        a10[c] += w10 * g; a11[c] += w11 * g;
+                    }
+                }
+            }
+        }
+        // the two lanes of a cell: even rows + odd rows, always in that order
+#pragma unroll
+        for (int c = 0; c < CT; ++c) {
+            a00[c] += __shfl_xor(a00[c], 1, 64); a01[c] += __shfl_xor(a01[c], 1, 64);
+            a10[c] += __shfl_xor(a10[c], 1, 64); a11[c] += __shfl_xor(a11[c], 1, 64);
+        }
+        if (part == 0) {
+#pragma unroll
+            for (int c = 0; c < CT; ++c) {
+                corner[cell][0][c] = a00[c]; corner[cell][1][c] = a01[c];
+                corner[cell][2][c] = a10[c]; corner[cell][3][c] = a11[c];
+            }
+        }
+    }
+    __syncthreads();
+    // output (i, j) collects corner (a, b) of cell (ci, cj) wherever ci + (a && ci < h-1) == i and
+    // cj + (b && cj < w-1) == j; candidates are ci in {i-1, i}, cj in {j-1, j}; fixed visiting order
+    for (int o = tid; o < kCellTH * kCellTW * nc; o += kCellThreads) {
+        const int c = o / (kCellTH * kCellTW);
+        const int r = o - c * (kCellTH * kCellTW);
+        const int li = r / kCellTW, lj = r - li * kCellTW;
+        const int i = I0 + li, j = J0 + lj;
+        if (i >= h || j >= w) continue;
+        float acc = 0.f;
+#pragma unroll
+        for (int di = 0; di < 2; ++di) {
+            const int ci = i - 1 + di;
+            if (ci < 0) continue;
+#pragma unroll
+            for (int a = 0; a < 2; ++a) {
+                if (ci + ((a && ci < h - 1) ? 1 : 0) != i) continue;
+#pragma unroll
+                for (int dj = 0; dj < 2; ++dj) {
+                    const int cj = j - 1 + dj;
+                    if (cj < 0) continue;
+#pragma unroll
+                    for (int bb = 0; bb < 2; ++bb) {
+                        if (cj + ((bb && cj < w - 1) ? 1 : 0) != j) continue;
+                        acc += corner[(li + di) * (kCellTW + 1) + (lj + dj)][a * 2 + bb][c];
+                    }
+                }
+            }
+        }
+        out[c * plane + (long long)i * w + j] = acc * gs;
+    }
+}
+
+// block <-> (image, tile row, tile column, class window); the window varies fastest, so the blocks that read the same
+// tile's labels, lse and A are neighbours in dispatch order
+template <bool ALIGN, int CT>
+__global__ void __launch_bounds__(kCellThreads, 2)
+lovasz_bwd_cells_kernel(const float* __restrict__ logits, const long long* __restrict__ labels, int ignore_index, int N,
+                        int C, int h, int w, int H, int W, float sh, float sw, int log2B, const float* __restrict__ lse,
+                        const float* __restrict__ table, const float* __restrict__ asum,
+                        const float* __restrict__ grad_scale, float* __restrict__ dlogits, int tiles_w, int tiles_h,
+                        int chunks) {
+    __shared__ float corner[kCellCount][4][CT + 1];
+    const int B = 1 << log2B, shift = kQ - log2B;
+    long long b = blockIdx.x;
+    const int chunk = (int)(b % chunks);
+    b /= chunks;
+    const int tw = (int)(b % tiles_w);
+    b /= tiles_w;
+    const int th = (int)(b % tiles_h);
+    const int n = (int)(b / tiles_h);
+    const int c0 = chunk * CT;
+    const int nc = C - c0 < CT ? C - c0 : CT;
+    const long long plane = (long long)h * w, img = (long long)n * H * W;
+    const float* base = logits + ((long long)n * C + c0) * plane;
+    float* out = dlogits + ((long long)n * C + c0) * plane;
+    const float* tab = table + (long long)c0 * B * 2;
+    const float gs = grad_scale[0];
+    if (nc == CT)
+        lovasz_bwd_cells_body<ALIGN, CT, false>(corner, base, labels + img, lse + img, asum + img, tab, ignore_index, C,
+                                                c0, nc, h, w, H, W, sh, sw, shift, B, gs, out, th * kCellTH,
+                                                tw * kCellTW);
+    else
+        lovasz_bwd_cells_body<ALIGN, CT, true>(corner, base, labels + img, lse + img, asum + img, tab, ignore_index, C,
+                                               c0, nc, h, w, H, W, sh, sw, shift, B, gs, out, th * kCellTH,
+                                               tw * kCellTW);
+}
+
+// ------------------------------------------------------------------------------------------------ error dump
+template <bool ALIGN>
+__global__ void __launch_bounds__(kThreads)
+lovasz_errors_kernel(const float* __restrict__ logits, const long long* __restrict__ labels, int ignore_index, int N,
+                     int C, int h, int w, int H, int W, float sh, float sw, unsigned int* __restrict__ out) {
+    const long long total = (long long)N * H * W, plane = (long long)h * w, HW = (long long)H * W;
+    for (long long pix = (long long)blockIdx.x * kThreads + threadIdx.x; pix < total;
+         pix += (long long)gridDim.x * kThreads) {
+        const long long label = labels[pix];
+        const Pix P = pix_of(pix, H, W);
+        unsigned int* o = out + (long long)P.n * C * HW + (pix - (long long)P.n * HW);
+        if (!label_valid(label, C, ignore_index)) {
+            for (int c = 0; c < C; ++c) o[c * HW] = 0xFFFFFFFFu;
+            continue;
+        }
+        const Tap t = tap_of(lerp_of<ALIGN>(P.Y, sh, h), lerp_of<ALIGN>(P.X, sw, w), w);
+        const float* base = logits + (long long)P.n * C * plane;
+        const float ls = lse_at(base, plane, C, t);
+        for (int c = 0; c < C; ++c) o[c * HW] = lovasz_term(base + c * plane, t, ls, label == c, 0, 1 << kQ).q;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ host side
+int log2_bins(int bins) {        // log2 B for a power of two in [64, 4096], else -1
+    for (int k = 6; k <= 12; ++k)
+        if (bins == (1 << k)) return k;
+    return -1;
+}
+
+// workspace: SF, SB (uint64 [C*B] each), nF, nB (uint32 [C*B] each), wraw (fp64 [C*B*2]), loss_c (fp64 [C]),
+// fg_count (int64 [C]); every part starts 8-byte aligned
+struct Workspace {
+    unsigned long long *SF, *SB;
+    unsigned int *nF, *nB;
+    double *wraw, *loss_c;
+    long long* fg_count;
+    size_t bytes, hist_bytes;
+};
+
+Workspace carve(void* ws, int C, int bins) {
+    const size_t cb = (size_t)C * bins;
+    char* p = static_cast<char*>(ws);
+    Workspace r;
+    r.SF = reinterpret_cast<unsigned long long*>(p);
+    r.SB = r.SF + cb;
+    r.nF = reinterpret_cast<unsigned int*>(r.SB + cb);
+    r.nB = r.nF + cb;
+    r.hist_bytes = cb * 24;
+    r.wraw = reinterpret_cast<double*>(p + r.hist_bytes);
+    r.loss_c = r.wraw + cb * 2;
+    r.fg_count = reinterpret_cast<long long*>(r.loss_c + C);
+    r.bytes = r.hist_bytes + cb * 16 + (size_t)C * 16;
+    return r;
+}
+
+int check_shape(int N, int C, int h, int w, int H, int W) {
+    if (N < 1 || C < 1 || h < 1 || w < 1 || H < 1 || W < 1) return DCFP_E_BADDESC;
+    if (C > 255 || (long long)N * H * W >= (1LL << 31)) return DCFP_E_UNSUPPORTED;
+    return DCFP_OK;
+}
+
+unsigned grid_for(long long items) {
+    const long long blocks = (items + kThreads - 1) / kThreads;
+    return (unsigned)(blocks < 1 ? 1 : (blocks > kMaxBlocks ? kMaxBlocks : blocks));
+}
+
+}  // namespace
+
+extern "C" size_t dcfp_lovasz_workspace_bytes(int C, int bins) {
+    if (C < 1 || C > 255 || log2_bins(bins) < 0) return 0;
+    return carve(nullptr, C, bins).bytes;
+}
+
+extern "C" int dcfp_lovasz_hist_f32(const float* logits, const int64_t* labels, int ignore_index, int N, int C, int h,
+                                    int w, int H, int W, int align_corners, int bins, float* lse, void* workspace,
+                                    size_t workspace_bytes, dcfp_stream_t stream) {
+    const int log2B = log2_bins(bins);
+    if (!logits || !labels || !lse || log2B < 0) return DCFP_E_BADDESC;
+    if (const int e = check_shape(N, C, h, w, H, W)) return e;
+    if (!workspace || workspace_bytes < dcfp_lovasz_workspace_bytes(C, bins)) return DCFP_E_WORKSPACE;
+    const Workspace ws = carve(workspace, C, bins);
+    hipStream_t st = dcfp_s(stream);
+    if (hipMemsetAsync(workspace, 0, ws.hist_bytes, st) != hipSuccess) DCFP_RETURN_LAUNCH();
+    const long long total = (long long)N * H * W;
+    const long long want = 4LL * dcfp_num_cus();
+    long long tile = (total + want - 1) / want;
+    tile = (tile + kHistThreads - 1) / kHistThreads * kHistThreads;
+    tile = tile < kTileMin ? kTileMin : (tile > kTileMax ? kTileMax : tile);
+    const unsigned blocks = (unsigned)((total + tile - 1) / tile);
+    const int chunk = kHistSlots / bins;                   // classes whose accumulators share the LDS: 64 ... 1
+    const float sh = host_scale(h, H, align_corners), sw = host_scale(w, W, align_corners);
+    const long long* lab = reinterpret_cast<const long long*>(labels);
+    if (align_corners)
+        hipLaunchKernelGGL(lovasz_hist_kernel<true>, dim3(blocks), dim3(kHistThreads), 0, st, logits, lab, ignore_index,
+                           N, C, h, w, H, W, sh, sw, log2B, chunk, tile, lse, ws.SF, ws.SB, ws.nF, ws.nB);
+    else
+        hipLaunchKernelGGL(lovasz_hist_kernel<false>, dim3(blocks), dim3(kHistThreads), 0, st, logits, lab, ignore_index,
+                           N, C, h, w, H, W, sh, sw, log2B, chunk, tile, lse, ws.SF, ws.SB, ws.nF, ws.nB);
+    DCFP_RETURN_LAUNCH();
+}
+
+extern "C" int dcfp_lovasz_scan_f32(int C, int bins, void* workspace, size_t workspace_bytes, float* loss_out,
+                                    float* weights, dcfp_stream_t stream) {
+    const int log2B = log2_bins(bins);
+    if (!loss_out || !weights || C < 1 || log2B < 0) return DCFP_E_BADDESC;
+    if (C > 255) return DCFP_E_UNSUPPORTED;
+    if (!workspace || workspace_bytes < dcfp_lovasz_workspace_bytes(C, bins)) return DCFP_E_WORKSPACE;
+    const Workspace ws = carve(workspace, C, bins);
+    hipStream_t st = dcfp_s(stream);
+    hipLaunchKernelGGL(lovasz_scan_kernel, dim3(C), dim3(kThreads), 0, st, ws.nF, ws.nB, ws.SF, ws.SB, log2B, ws.wraw,
+                       ws.loss_c, ws.fg_count);
+    const long long n_table = (long long)C * bins * 2;
+    hipLaunchKernelGGL(lovasz_final_kernel, dim3(grid_for((n_table + 3) / 4)), dim3(kThreads), 0, st, ws.wraw, ws.loss_c,
+                       ws.fg_count, C, n_table, weights, loss_out);
+    DCFP_RETURN_LAUNCH();
+}
+
+extern "C" int dcfp_lovasz_bwd_f32(const float* logits, const int64_t* labels, int ignore_index, int N, int C, int h,
+                                   int w, int H, int W, int align_corners, int bins, const float* lse,
+                                   const float* weights, const float* grad_scale, float* asum, float* dlogits,
+                                   dcfp_stream_t stream) {
+    const int log2B = log2_bins(bins);
+    if (!logits || !labels || !lse || !weights || !grad_scale || !asum || !dlogits || log2B < 0) return DCFP_E_BADDESC;
+    if (const int e = check_shape(N, C, h, w, H, W)) return e;
+    if ((long long)N * ((h + kCellTH - 1) / kCellTH) * ((w + kCellTW - 1) / kCellTW) * ((C + kCellCT - 1) / kCellCT) >
+        0x7fffffffLL)
+        return DCFP_E_UNSUPPORTED;
+    hipStream_t st = dcfp_s(stream);
+    const float sh = host_scale(h, H, align_corners), sw = host_scale(w, W, align_corners);
+    const long long* lab = reinterpret_cast<const long long*>(labels);
+    const int tiles_h = (h + kCellTH - 1) / kCellTH, tiles_w = (w + kCellTW - 1) / kCellTW;
+    const int chunks = (C + kCellCT - 1) / kCellCT;
+    const unsigned g1 = grid_for((long long)N * H * W), g2 = (unsigned)((long long)N * tiles_h * tiles_w * chunks);
+    if (align_corners) {
+        hipLaunchKernelGGL(lovasz_asum_kernel<true>, dim3(g1), dim3(kThreads), 0, st, logits, lab, ignore_index, N, C, h,
+                           w, H, W, sh, sw, log2B, lse, weights, asum);
+        hipLaunchKernelGGL((lovasz_bwd_cells_kernel<true, kCellCT>), dim3(g2), dim3(kCellThreads), 0, st, logits, lab,
+                           ignore_index, N, C, h, w, H, W, sh, sw, log2B, lse, weights, asum, grad_scale, dlogits, tiles_w,
+                           tiles_h, chunks);
+    } else {
+        hipLaunchKernelGGL(lovasz_asum_kernel<false>, dim3(g1), dim3(kThreads), 0, st, logits, lab, ignore_index, N, C, h,
+                           w, H, W, sh, sw, log2B, lse, weights, asum);
+        hipLaunchKernelGGL((lovasz_bwd_cells_kernel<false, kCellCT>), dim3(g2), dim3(kCellThreads), 0, st, logits, lab,
+                           ignore_index, N, C, h, w, H, W, sh, sw, log2B, lse, weights, asum, grad_scale, dlogits, tiles_w,
+                           tiles_h, chunks);
+    }
+    DCFP_RETURN_LAUNCH();
+}
+
+extern "C" int dcfp_lovasz_errors_u32(const float* logits, const int64_t* labels, int ignore_index, int N, int C, int h,
+                                      int w, int H, int W, int align_corners, uint32_t* errors, dcfp_stream_t stream) {
+    if (!logits || !labels || !errors) return DCFP_E_BADDESC;
+    if (const int e = check_shape(N, C, h, w, H, W)) return e;
+    const float sh = host_scale(h, H, align_corners), sw = host_scale(w, W, align_corners);
+    const long long* lab = reinterpret_cast<const long long*>(labels);
+    const unsigned g = grid_for((long long)N * H * W);
+    if (align_corners)
+        hipLaunchKernelGGL(lovasz_errors_kernel<true>, dim3(g), dim3(kThreads), 0, dcfp_s(stream), logits, lab,
+                           ignore_index, N, C, h, w, H, W, sh, sw, errors);
+    else
+        hipLaunchKernelGGL(lovasz_errors_kernel<false>, dim3(g), dim3(kThreads), 0, dcfp_s(stream), logits, lab,
+                           ignore_index, N, C, h, w, H, W, sh, sw, errors);
+    DCFP_RETURN_LAUNCH();
+}

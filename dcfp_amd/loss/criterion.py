@@ -28,6 +28,8 @@ def build_criterion(loss_type, dataset, loss_para):
         cls = CriterionGsrlDSN
     elif loss_type == "kd":
         cls = CriterionKD
+    elif loss_type == "lovasz":
+        cls = CriterionLovasz
     else:
         raise NotImplementedError(loss_type)
     return cls(dataset=dataset, **loss_para)
@@ -171,3 +173,34 @@ class CriterionKD(nn.Module):
         if isinstance(preds, dict):
             preds = [preds["pred"]]
         return self._term(preds[0], labels)
+
+
+class CriterionLovasz(nn.Module):
+    """Lovasz-Softmax term of the fine-tune stage: lovasz_weight * ops.lovasz_softmax(main-head logits, labels), the
+    convex surrogate of the per-class Jaccard index (Berman et al. 2018) over the classes present in the batch, computed
+    from the low-resolution logits with `lovasz_bins` error bins in place of a sort.  Only the main head
+    gets the term; every rank takes the loss of its own batch (no histogram is shared between data-parallel ranks), and
+    the paper's per_image and classes='all' modes are not offered.  Combined with a supervised loss as
+    `--loss-type ce,lovasz` / `gsrl,lovasz`; labels may be the tensor or the dict (labels['ori'])."""
+
+    def __init__(self, dataset=None, lovasz_weight=1.0, lovasz_bins=1024, **kwargs):
+        super().__init__()
+        if isinstance(lovasz_bins, bool) or lovasz_bins not in ops.LOVASZ_BINS:
+            raise ValueError(f"CriterionLovasz: lovasz_bins must be a power of two in 64 .. 4096, got {lovasz_bins!r}")
+        if not float(lovasz_weight) >= 0.0:
+            raise ValueError(f"CriterionLovasz: lovasz_weight must not be negative, got {lovasz_weight}")
+        self.lovasz_weight, self.lovasz_bins = float(lovasz_weight), int(lovasz_bins)
+        self.ignore_index = dataset.ignore_label
+
+    def forward_lowres(self, preds, labels, size, align_corner):
+        if isinstance(labels, dict):
+            labels = labels["ori"]
+        term = ops.lovasz_softmax(preds[0], labels, size, align_corner, self.ignore_index, self.lovasz_bins)
+        return {"loss": self.lovasz_weight * term}
+
+    def forward(self, preds, labels):
+        if isinstance(preds, dict):
+            preds = [preds["pred"]]
+        if isinstance(labels, dict):
+            labels = labels["ori"]
+        return self.forward_lowres(list(preds), labels, labels.shape[-2:], True)

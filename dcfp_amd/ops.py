@@ -1949,6 +1949,106 @@ def kd_loss(student, teacher, T=1.0, mode="pixel"):
     return KDLossFn.apply(student, teacher, T, KD_MODES[mode])
 
 
+# ------------------------------------------------------------------ Lovasz-Softmax
+LOVASZ_Q = 20                              # errors are quantised to q = round(e * 2^20) (csrc/lovasz.hip)
+LOVASZ_BINS = (64, 128, 256, 512, 1024, 2048, 4096)
+
+
+def _lovasz_args(name, logits, labels, size, bins):
+    _require(logits, "logits")
+    if logits.dim() != 4:
+        raise RuntimeError(f"{name}: logits must be [N,C,h,w], got {tuple(logits.shape)}")
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64 or not labels.is_cuda:
+        raise RuntimeError(f"{name}: labels must be a CUDA int64 tensor [N,H,W]")
+    if labels.device != logits.device:
+        raise RuntimeError(f"{name}: logits on {logits.device}, labels on {labels.device}")
+    N, Cc, h, w = logits.shape
+    H, W = int(size[0]), int(size[1])
+    if tuple(labels.shape) != (N, H, W):
+        raise RuntimeError(f"{name}: labels shape {tuple(labels.shape)} != {(N, H, W)}")
+    if bins not in LOVASZ_BINS:
+        raise ValueError(f"{name}: bins must be a power of two in 64 .. 4096, got {bins!r}")
+    if Cc > 255:
+        raise ValueError(f"{name}: at most 255 classes, got {Cc}")
+    return N, Cc, h, w, H, W
+
+
+def _lovasz_hist(logits, labels, N, Cc, h, w, H, W, ac, ignore_index, bins):
+    """-> (lse [N,H,W], workspace that holds the histogram): dcfp_lovasz_hist_f32 on contiguous inputs"""
+    L = _lib.lib()
+    ws = _workspace("lovasz", L.dcfp_lovasz_workspace_bytes(Cc, bins), logits.device)
+    lse = torch.empty((N, H, W), dtype=torch.float32, device=logits.device)
+    check(L.dcfp_lovasz_hist_f32(_p(logits), _p(labels), int(ignore_index), N, Cc, h, w, H, W, ac, bins, _p(lse),
+                                 _p(ws), ws.numel(), _stream()), "lovasz_hist")
+    return lse, ws
+
+
+class LovaszSoftmaxFn(torch.autograd.Function):
+    """Lovasz-Softmax loss of the bilinearly upsampled logits over the classes present in the labels (lovasz.hip,
+    DESIGN §18).  Forward keeps the per-pixel log-sum-exp and the weight table [C, bins, 2]; the table is this node's
+    own tensor, the histogram workspace is free for the next call as soon as forward returns."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, H, W, align_corners, ignore_index, bins):
+        logits, labels = logits.contiguous(), labels.contiguous()
+        N, Cc, h, w = logits.shape
+        ac = int(bool(align_corners))
+        lse, ws = _lovasz_hist(logits, labels, N, Cc, h, w, H, W, ac, ignore_index, bins)
+        out = torch.empty(1, dtype=torch.float32, device=logits.device)
+        table = torch.empty((Cc, bins, 2), dtype=torch.float32, device=logits.device)
+        check(_lib.lib().dcfp_lovasz_scan_f32(Cc, bins, _p(ws), ws.numel(), _p(out), _p(table), _stream()),
+              "lovasz_scan")
+        ctx.save_for_backward(logits, labels, lse, table)
+        ctx.cfg = (H, W, ac, int(ignore_index), bins)
+        return out.reshape(())
+
+    @staticmethod
+    def backward(ctx, gout):
+        logits, labels, lse, table = ctx.saved_tensors
+        H, W, ac, ignore, bins = ctx.cfg
+        N, Cc, h, w = logits.shape
+        scale = gout.reshape(1).to(torch.float32).contiguous()
+        asum = torch.empty_like(lse)
+        dl = torch.empty_like(logits)
+        check(_lib.lib().dcfp_lovasz_bwd_f32(_p(logits), _p(labels), ignore, N, Cc, h, w, H, W, ac, bins, _p(lse),
+                                             _p(table), _p(scale), _p(asum), _p(dl), _stream()), "lovasz_bwd")
+        return dl, None, None, None, None, None, None
+
+
+def lovasz_softmax(logits, labels, size, align_corners, ignore_index=255, bins=1024):
+    """Lovasz-Softmax loss (Berman et al. 2018, classes='present') of softmax(F.interpolate(logits, size)) against
+    `labels`, a 0-dim tensor.  logits fp32 [N,C,h,w], labels int64 [N,H,W]; a pixel counts when its label is a class
+    and not ignore_index.  Errors are quantised to 2^-20 and binned into `bins` bins instead of sorted: the loss lies
+    within [L - 1/bins - 2^-21, L + 2^-21] of the exact loss L, two calls give the same bits, and nothing of size
+    N x C x H x W is allocated.  No class present: 0, with a zero gradient."""
+    N, Cc, h, w, H, W = _lovasz_args("lovasz_softmax", logits, labels, size, bins)
+    return LovaszSoftmaxFn.apply(logits, labels, H, W, align_corners, int(ignore_index), int(bins))
+
+
+def lovasz_histogram(logits, labels, size, align_corners, ignore_index=255, bins=1024):
+    """-> (nF, nB, SF, SB), each [C, bins]: per class and error bin the number of foreground / background pixels (int32)
+    and the sums of their quantised errors q (int64) - what lovasz_softmax scans."""
+    N, Cc, h, w, H, W = _lovasz_args("lovasz_histogram", logits, labels, size, bins)
+    _, ws = _lovasz_hist(logits.detach().contiguous(), labels.contiguous(), N, Cc, h, w, H, W,
+                         int(bool(align_corners)), ignore_index, int(bins))
+    cb = Cc * bins
+    sums = ws[:16 * cb].view(torch.int64).reshape(2, Cc, bins).clone()
+    counts = ws[16 * cb:24 * cb].view(torch.int32).reshape(2, Cc, bins).clone()
+    return counts[0], counts[1], sums[0], sums[1]
+
+
+def lovasz_errors(logits, labels, size, align_corners, ignore_index=255):
+    """-> q [N,C,H,W]: the quantised error min(2^20, floor(e * 2^20 + 0.5)) of every pixel and class, e = 1 - p for the
+    label's class and p otherwise, as int64; 0xFFFFFFFF where the pixel does not count.  For tests and for a look at the
+    error distribution: it writes N x C x H x W values and has no place in a training step."""
+    N, Cc, h, w, H, W = _lovasz_args("lovasz_errors", logits, labels, size, LOVASZ_BINS[0])
+    out = torch.empty((N, Cc, H, W), dtype=torch.int32, device=logits.device)
+    logits, labels = logits.detach().contiguous(), labels.contiguous()
+    check(_lib.lib().dcfp_lovasz_errors_u32(_p(logits), _p(labels), int(ignore_index), N, Cc, h, w, H, W,
+                                            int(bool(align_corners)), _p(out), _stream()), "lovasz_errors")
+    return out.to(torch.int64) & 0xFFFFFFFF
+
+
 # ------------------------------------------------------------------ inference / evaluation
 def conv2d_fused_infer(x, w, scale, shift, stride=1, pad=0, dil=1, residual=None, relu=False):
     """y = act(conv(x,w)*scale[co] + shift[co] (+ residual)): conv with an eval-mode BatchNorm

@@ -941,6 +941,40 @@ size_t dcfp_fpgm_workspace_bytes(int C);
 int dcfp_fpgm_f32(const DcfpFpgmEntry* table, int n_entries, int64_t total_tiles, void* workspace,
                   size_t workspace_bytes, dcfp_stream_t stream);
 
+/* ------------------------------------------------ Lovasz-Softmax loss (csrc/lovasz.hip)
+ * The Lovasz-Softmax loss (Berman et al. 2018, classes = 'present') of the bilinearly upsampled logits, with the sort
+ * replaced by an integer histogram of quantised errors.  Arguments as dcfp_upsample_ce_*: logits fp32 [N,C,h,w], labels
+ * int64 [N,H,W]; a pixel counts when its label lies in [0, C) and is not ignore_index.  bins = B, a power of two in
+ * 64 .. 4096.  Per valid pixel and class, with p = exp(z - lse) of the interpolated logits z:
+ *     e = (label == c) ? 1 - p : p,   q = min(2^20, floor(e * 2^20 + 0.5)),   b = min(B - 1, q >> (20 - log2 B)).
+ *   dcfp_lovasz_hist_f32    writes lse [N,H,W] and, into the workspace, per (class, bin) the counts nF / nB of the
+ *                           foreground / background pixels and the sums SF / SB of their q.  Integer atomics only: two
+ *                           calls leave the same bits.
+ *   dcfp_lovasz_scan_f32    from that workspace: the loss (device scalar) and the weight table fp32 [C][B][2] =
+ *                           (wF, wB) / P, P the number of present classes (zeros for an absent class; P == 0 gives
+ *                           loss 0 and a zero table); fp64 in a fixed order.
+ *   dcfp_lovasz_bwd_f32     dlogits [N,C,h,w] = *grad_scale x dloss/dlogits from logits, labels, lse and the table;
+ *                           asum: fp32 [N,H,W] scratch (sum_c a_c p_c per pixel).  A gather, no atomics.
+ *   dcfp_lovasz_errors_u32  q of every (n, c, Y, X) as uint32 [N,C,H,W], 0xFFFFFFFF at pixels that do not count.
+ * Workspace of dcfp_lovasz_workspace_bytes(C, bins) bytes (0 for arguments the calls refuse), 8-byte aligned, with
+ * CB = C * bins:   SF uint64 [CB] | SB uint64 [CB] | nF uint32 [CB] | nB uint32 [CB] | fp64 [CB][2] raw weights |
+ * fp64 [C] loss per class | int64 [C] foreground pixels per class.  hist zero-fills and fills the first four, scan
+ * reads them and fills the rest.
+ * Null pointers, sizes < 1 and bins that are no power of two in 64 .. 4096 are DCFP_E_BADDESC; C > 255 or
+ * N*H*W >= 2^31 DCFP_E_UNSUPPORTED; a workspace that is null or too small DCFP_E_WORKSPACE.  All of it is checked before
+ * any HIP call. */
+size_t dcfp_lovasz_workspace_bytes(int C, int bins);
+int dcfp_lovasz_hist_f32(const float* logits, const int64_t* labels, int ignore_index, int N, int C, int h, int w, int H,
+                         int W, int align_corners, int bins, float* lse, void* workspace, size_t workspace_bytes,
+                         dcfp_stream_t stream);
+int dcfp_lovasz_scan_f32(int C, int bins, void* workspace, size_t workspace_bytes, float* loss_out /* device scalar */,
+                         float* weights, dcfp_stream_t stream);
+int dcfp_lovasz_bwd_f32(const float* logits, const int64_t* labels, int ignore_index, int N, int C, int h, int w, int H,
+                        int W, int align_corners, int bins, const float* lse, const float* weights,
+                        const float* grad_scale /* device scalar */, float* asum, float* dlogits, dcfp_stream_t stream);
+int dcfp_lovasz_errors_u32(const float* logits, const int64_t* labels, int ignore_index, int N, int C, int h, int w,
+                           int H, int W, int align_corners, uint32_t* errors, dcfp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,8 @@ the model / optimiser / loss / pruning options).  Without --dataset it runs over
 batches; with --dataset CS|CTX|COCO (and the reference's data flags) it reads a list file through dcfp_amd.datasets,
 whose augmentation chain runs on the device (ADE is not built).
 `--loss-type ...,kd --teacher-from CKPT` adds the distillation term against a frozen teacher.
+`--loss-type ce,lovasz` / `gsrl,lovasz` adds the Lovasz-Softmax term on the main head, the surrogate of the per-class IoU
+(DESIGN §18); `--loss-para '{"lovasz_weight": 1.0, "lovasz_bins": 1024}'` sets its weight and its error bins.
 `--prune-type taylor | taylor_w` scores by first-order Taylor instead of `dcfp`, `--slim-lambda` adds the Network
 Slimming L1 term to the BN weight gradients (the baseline criteria).
 One process per GPU: `python -m torch.distributed.run --nproc-per-node N tools/train.py ...`."""
@@ -60,8 +62,11 @@ def get_parser():
     p.add_argument("--betas", type=str, default="0.9,0.999")
     p.add_argument("--warmup", type=int, default=-1)
     p.add_argument("--deepsup", type=str2bool, default="True")
-    p.add_argument("--loss-type", type=str, default="ce")
-    p.add_argument("--loss-para", type=str, default="{}")
+    p.add_argument("--loss-type", type=str, default="ce",
+                   help="ce, ohem, gsrl, kd or lovasz, or several joined by commas and summed: ce,kd / gsrl,lovasz")
+    p.add_argument("--loss-para", type=str, default="{}",
+                   help="JSON of the criteria's keyword arguments: ds_weight, kd_weight, kd_T, kd_mode, lovasz_weight, "
+                        "lovasz_bins (a power of two in 64 .. 4096), ...")
     p.add_argument("--prune-type", type=str, default=None,
                    help="score while training and write score.pth: dcfp (the EIC score), taylor (first-order Taylor on "
                         "the BN gate) or taylor_w (on the filters); DESIGN §17")
