@@ -242,6 +242,9 @@ SIGNATURES = {
     "dcfp_pyramid_pool_nhwc_f16": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
     "dcfp_kd_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
     "dcfp_kd_fwd_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _P, _Z, _P, _P, _P]),
+    "dcfp_pairwise_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I, _I]),
+    "dcfp_pairwise_fwd_f32": (_I, [_P, _P, _I, _L, _I, _I, _I, _I, _I, _I, _P, _Z, _P, _I, _P]),
+    "dcfp_pairwise_bwd_f32": (_I, [_I, _I, _I, _I, _I, _I, _P, _Z, _P, _P, _P]),
     "dcfp_lovasz_workspace_bytes": (_Z, [_I, _I]),
     "dcfp_lovasz_hist_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _Z, _P]),
     "dcfp_lovasz_scan_f32": (_I, [_I, _I, _P, _Z, _P, _P, _P]),

@@ -750,6 +750,39 @@ class Engine:
             return y[..., r["y_off"]:r["y_off"] + width]
         return y
 
+    def backbone_record(self):
+        """Index (among the launch list) and record of the conv whose output is the backbone's last tensor: the last
+        `backbone.layer4.*.conv3`, which carries the block's residual add and ReLU."""
+        recs = [r for r in self.plan if not (r["op"] == "conv" and r["f32"])]
+        hits = [i for i, r in enumerate(recs) if r["op"] == "conv" and r["name"].startswith("backbone.layer4.")
+                and r["name"].endswith(".conv3")]
+        if not hits:
+            raise NotImplementedError("deploy.Engine: the plan holds no backbone.layer4.*.conv3 record")
+        return hits[-1], recs[hits[-1]]
+
+    @torch.no_grad()
+    def lowres_logits_and_feature(self, image):
+        """(fp32 low-resolution logits, feature, channels) of ONE run: `feature` is a contiguous fp16 NHWC clone
+        [N, h, w, pitch] of what backbone_record() wrote - the stage output the head reads, for networks.psp a channel
+        slice of the concat buffer - taken right after that launch; its first `channels` channels are the feature, the
+        rest is the granule's padding.  An fp8 engine stores e4m3 there and is refused."""
+        if self.format == FORMAT_F8:
+            raise NotImplementedError("deploy.Engine: the feature of an fp8 engine is e4m3; build the teacher as fp16")
+        self._check_image(image)
+        image = image.contiguous()
+        N, Cc, H, W = image.shape
+        at, rec = self.backbone_record()
+        got = []
+        with torch.cuda.device(self.device):
+            self._program(N, H, W)                   # (sizes the slots before any view of them is taken)
+            hw = self.buffer_shapes(H, W)
+
+            def tap(i):
+                if i == at:
+                    got.append(self._written(rec, N, hw).clone(memory_format=torch.contiguous_format))
+            logits = self._run(image, N, Cc, H, W, tap)[0]
+        return logits, got[0], rec["cout"]
+
     @torch.no_grad()
     def trace(self, image):
         """{record name: a clone of the bytes that record wrote} of one run, in the stored dtype (fp16 / e4m3 NHWC

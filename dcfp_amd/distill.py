@@ -55,8 +55,51 @@ class Teacher:
         return [] if self.is_engine else list(self.net.parameters())
 
     @torch.no_grad()
-    def __call__(self, images):
+    def __call__(self, images, feature=False):
+        """The main head's low-resolution logits; with feature=True `(logits, feature)` of the same run, `feature` is
+        the backbone's last tensor, the one FeatureTap takes from the student, as ops.pairwise_kd_loss
+        takes it: fp32 [N,C,h,w] from a Seg_Model; from an engine the fp16 [N,h,w,C] view of a contiguous clone of its
+        NHWC buffer slice (the pixel pitch may exceed C: the granule's padding is not part of the view)."""
         if not self.is_engine and self.net.training:
             self.net.eval()                 # (a model.train() on an enclosing module must not thaw the BatchNorms)
         # both kinds allocate their result per call (Engine._run, the head's last conv): the caller owns it
-        return self.net.lowres_logits(images)[0]
+        if not feature:
+            return self.net.lowres_logits(images)[0]
+        if self.is_engine:
+            logits, feat, channels = self.net.lowres_logits_and_feature(images)
+            return logits, feat[..., :channels]
+        got = []
+        hook = self.net.backbone.register_forward_hook(lambda mod, args, out: got.append(_last(out)))
+        try:
+            logits = self.net.lowres_logits(images)[0]
+        finally:
+            hook.remove()
+        return logits, got[0].detach().clone()      # (the caller owns it, as it owns the logits)
+
+
+def _last(out):
+    return out[-1] if isinstance(out, (tuple, list)) else out
+
+
+class FeatureTap:
+    """Takes the student's distilled feature out of a training forward without changing any network's signature: a
+    forward hook on `seg_model.backbone` keeps the last tensor the backbone returns - the stage output ASPP / PPM / the
+    simple head reads - when grad is enabled and the model is training, and only then.  pop() hands the graph tensor
+    out and drops the reference, so that no feature outlives its step."""
+
+    def __init__(self, seg_model):
+        if not hasattr(seg_model, "backbone"):
+            raise TypeError("FeatureTap: the model has no .backbone")
+        self._model, self._kept = seg_model, None
+        self._hook = seg_model.backbone.register_forward_hook(self._keep)
+
+    def _keep(self, module, args, out):
+        self._kept = _last(out) if (torch.is_grad_enabled() and self._model.training) else None
+
+    def pop(self):
+        kept, self._kept = self._kept, None
+        return kept
+
+    def remove(self):
+        self._hook.remove()
+        self._kept = None

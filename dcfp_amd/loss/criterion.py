@@ -28,6 +28,8 @@ def build_criterion(loss_type, dataset, loss_para):
         cls = CriterionGsrlDSN
     elif loss_type == "kd":
         cls = CriterionKD
+    elif loss_type == "kdpa":
+        cls = CriterionKDPairwise
     elif loss_type == "lovasz":
         cls = CriterionLovasz
     else:
@@ -54,6 +56,13 @@ class CombinedCriterion(nn.Module):
     def __init__(self, loss_types, dataset=None, loss_para={}):
         super().__init__()
         self.criterions = [build_criterion(t, dataset, loss_para) for t in loss_types.split(",")]
+
+    def attach(self, seg_model):
+        """Hand the bare model to the criteria that tap it (CriterionKDPairwise)."""
+        for c in self.criterions:
+            if hasattr(c, "attach"):
+                c.attach(seg_model)
+        return self
 
     def forward(self, preds, labels):
         loss, total = {}, 0.0
@@ -173,6 +182,51 @@ class CriterionKD(nn.Module):
         if isinstance(preds, dict):
             preds = [preds["pred"]]
         return self._term(preds[0], labels)
+
+
+class CriterionKDPairwise(nn.Module):
+    """Pair-wise similarity distillation of the fine-tune stage: pa_weight * ops.pairwise_kd_loss(student
+    feature, teacher feature, pa_pool) on the backbone's last tensor.  The student's feature does not travel with the
+    predictions: attach(seg_model) puts a distill.FeatureTap on the bare model and every call pops it; the teacher's
+    travels with the labels, as labels['teacher_feat'] (distill.Teacher(images, feature=True); tools/train.py
+    --teacher-from).  The two may differ in channels.  Combined with a supervised loss as `--loss-type gsrl,kdpa` /
+    `gsrl,kd,kdpa`; every rank takes the loss of its own batch."""
+
+    def __init__(self, dataset=None, pa_weight=1.0, pa_pool=2, **kwargs):
+        super().__init__()
+        if not float(pa_weight) >= 0.0:
+            raise ValueError(f"CriterionKDPairwise: pa_weight must not be negative, got {pa_weight}")
+        if isinstance(pa_pool, bool) or not isinstance(pa_pool, int) or pa_pool < 1:
+            raise ValueError(f"CriterionKDPairwise: pa_pool must be an int >= 1, got {pa_pool!r}")
+        self.pa_weight, self.pa_pool = float(pa_weight), pa_pool
+        self._tap = None
+
+    def attach(self, seg_model):
+        """Tap the backbone output of `seg_model` (the bare Seg_Model, under any wrapper)."""
+        from ..distill import FeatureTap
+        if self._tap is not None:
+            self._tap.remove()
+        self._tap = FeatureTap(seg_model)
+        return self
+
+    def _term(self, labels):
+        if self._tap is None:
+            raise ValueError("CriterionKDPairwise: attach(seg_model) first - the student's feature comes from a tap on "
+                             "its backbone")
+        if not isinstance(labels, dict) or "teacher_feat" not in labels:
+            raise ValueError("CriterionKDPairwise: labels must be a dict that holds the teacher's feature under "
+                             "'teacher_feat' (distill.Teacher(images, feature=True); tools/train.py --teacher-from)")
+        student = self._tap.pop()
+        if student is None:
+            raise ValueError("CriterionKDPairwise: the tap holds no feature - the attached model made no training-mode "
+                             "forward with grad enabled since the last call")
+        return {"loss": self.pa_weight * ops.pairwise_kd_loss(student, labels["teacher_feat"], self.pa_pool)}
+
+    def forward_lowres(self, preds, labels, size, align_corner):
+        return self._term(labels)
+
+    def forward(self, preds, labels):
+        return self._term(labels)
 
 
 class CriterionLovasz(nn.Module):

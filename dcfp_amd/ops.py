@@ -1949,6 +1949,98 @@ def kd_loss(student, teacher, T=1.0, mode="pixel"):
     return KDLossFn.apply(student, teacher, T, KD_MODES[mode])
 
 
+# ------------------------------------------------------------------ pair-wise similarity distillation
+PA_F32_NCHW, PA_F16_NHWC = 0, 1            # DCFP_PA_F32_NCHW / DCFP_PA_F16_NHWC of include/dcfp_hip.h
+
+
+class PairwiseKDFn(torch.autograd.Function):
+    """Mean squared difference of the student's and the teacher's node-similarity matrices (pairwise.hip).
+    When a gradient is wanted the forward call leaves the student's node matrix and the difference matrix in a workspace
+    of its own, which the graph keeps; backward runs the gradient kernels on it with grad_output as their last factor
+    and writes dL/dstudent once.  A loss-only call uses the shared scratch.  The teacher gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, student, teacher, layout, pitch, Ct, pool):
+        s = student.contiguous()
+        N, Cs, h, w = s.shape
+        L = _lib.lib()
+        want = ctx.needs_input_grad[0]
+        nbytes = L.dcfp_pairwise_workspace_bytes(N, Cs, Ct, h, w, pool, int(want))
+        if nbytes == 0:
+            raise RuntimeError(f"pairwise_kd_loss: student {tuple(s.shape)} with pool {pool} is beyond the kernels' "
+                               "launch limits")
+        if want:
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=s.device)
+        else:
+            ws = _workspace("pairwise", nbytes, s.device)
+        out = torch.empty(1, dtype=torch.float32, device=s.device)
+        check(L.dcfp_pairwise_fwd_f32(_p(s), _p(teacher), layout, pitch, N, Cs, Ct, h, w, pool, _p(ws), ws.numel(),
+                                      _p(out), int(want), _stream()), "pairwise_fwd")
+        ctx.save_for_backward(ws if want else None)
+        ctx.cfg = (N, Cs, Ct, h, w, pool)
+        return out.reshape(())
+
+    @staticmethod
+    def backward(ctx, gout):
+        ws, = ctx.saved_tensors
+        N, Cs, Ct, h, w, pool = ctx.cfg
+        g = gout.to(torch.float32).contiguous()
+        ds = torch.empty((N, Cs, h, w), dtype=torch.float32, device=ws.device)
+        check(_lib.lib().dcfp_pairwise_bwd_f32(N, Cs, Ct, h, w, pool, _p(ws), ws.numel(), _p(g), _p(ds), _stream()),
+              "pairwise_bwd")
+        return ds, None, None, None, None, None
+
+
+def pairwise_kd_loss(student, teacher, pool=2, teacher_channels=None):
+    """Pair-wise similarity distillation (Liu et al. 2019) between a feature map of the student, fp32 [N,Cs,h,w], and
+    of a frozen teacher over the same N, h, w, a 0-dim fp32 tensor:  nodes are the means of the pool x pool windows
+    (avg_pool2d with ceil_mode, count_include_pad False), normalised over the channels (a node with squared norm
+    <= 1e-12 is dead: zero, no gradient);  L = 1/(N P^2) * sum (f^S_p . f^S_q - f^T_p . f^T_q)^2 over images and node
+    pairs.  The teacher is fp32 [N,Ct,h,w] or, as a deploy.Engine holds it, fp16 [N,h,w,pitch] with unit stride in the
+    last dimension, of which the first `teacher_channels` (default: all) are read; Ct need not equal Cs.  The gradient
+    goes to `student` only; a teacher that requires grad is an error (detach it)."""
+    _require(student, "student")
+    if not isinstance(teacher, torch.Tensor) or not teacher.is_cuda:
+        raise RuntimeError("dcfp_amd: teacher must be a CUDA/HIP tensor (no CPU fallback exists)")
+    if teacher.requires_grad:
+        raise RuntimeError("pairwise_kd_loss: the teacher's feature must not require grad (run the teacher under no_grad)")
+    if isinstance(pool, bool) or not isinstance(pool, int) or pool < 1:
+        raise ValueError(f"pairwise_kd_loss: pool must be an int >= 1, got {pool!r}")
+    if student.dim() != 4 or teacher.dim() != 4:
+        raise RuntimeError(f"pairwise_kd_loss: student {tuple(student.shape)} and teacher {tuple(teacher.shape)} must be "
+                           "4-dimensional")
+    if student.device != teacher.device:
+        raise RuntimeError(f"pairwise_kd_loss: student on {student.device}, teacher on {teacher.device}")
+    N, _, h, w = student.shape
+    if teacher.dtype == torch.float32:
+        if teacher_channels is not None and int(teacher_channels) != teacher.shape[1]:
+            raise ValueError(f"pairwise_kd_loss: teacher_channels {teacher_channels} on an fp32 teacher of "
+                             f"{teacher.shape[1]} channels")
+        nhw, Ct, layout, pitch = (teacher.shape[0], teacher.shape[2], teacher.shape[3]), teacher.shape[1], PA_F32_NCHW, 0
+        teacher = teacher.contiguous()
+    elif teacher.dtype == torch.float16:
+        nhw, width = tuple(teacher.shape[:3]), teacher.shape[3]
+        if nhw != (N, h, w):
+            raise RuntimeError(f"pairwise_kd_loss: student {tuple(student.shape)} [N,C,h,w] and teacher "
+                               f"{tuple(teacher.shape)} [N,h,w,pitch] must cover the same N, h, w")
+        Ct = width if teacher_channels is None else int(teacher_channels)
+        if not 1 <= Ct <= width:
+            raise ValueError(f"pairwise_kd_loss: teacher_channels {teacher_channels} of a {width}-channel wide teacher")
+        st = teacher.stride()                # (the stride of a dimension of size 1 says nothing)
+        pitch = st[2] if w > 1 else st[1] if h > 1 else st[0] if N > 1 else width
+        if not ((width == 1 or st[3] == 1) and pitch >= width and (h == 1 or st[1] == w * pitch)
+                and (N == 1 or st[0] == h * w * pitch)):
+            raise RuntimeError("pairwise_kd_loss: an fp16 teacher is [N,h,w,pitch] with unit stride in the last dimension "
+                               f"and dense pixels, got strides {tuple(teacher.stride())}")
+        layout = PA_F16_NHWC
+    else:
+        raise RuntimeError(f"dcfp_amd: teacher must be float32 [N,C,h,w] or float16 [N,h,w,pitch], got {teacher.dtype}")
+    if nhw != (N, h, w):
+        raise RuntimeError(f"pairwise_kd_loss: student {tuple(student.shape)} and teacher {tuple(teacher.shape)} must "
+                           "cover the same N, h, w")
+    return PairwiseKDFn.apply(student, teacher, layout, int(pitch), int(Ct), pool)
+
+
 # ------------------------------------------------------------------ Lovasz-Softmax
 LOVASZ_Q = 20                              # errors are quantised to q = round(e * 2^20) (csrc/lovasz.hip)
 LOVASZ_BINS = (64, 128, 256, 512, 1024, 2048, 4096)

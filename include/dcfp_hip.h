@@ -872,6 +872,35 @@ int dcfp_kd_fwd_f32(const float* s, const float* t, int mode, int N, int C, int 
                     size_t workspace_bytes, float* loss_out /* device scalar */, float* dlogits /* may be null */,
                     dcfp_stream_t stream);
 
+/* ------------------------------------------- pair-wise similarity distillation (pairwise.hip)
+ * s (student): fp32 NCHW [N,Cs,h,w], contiguous.  t (teacher) over the same N, h, w with Ct channels (Ct != Cs allowed):
+ *   DCFP_PA_F32_NCHW  fp32 NCHW [N,Ct,h,w], contiguous (t_pitch is not read)
+ *   DCFP_PA_F16_NHWC  fp16 NHWC, pixel (n,y,x) at t + ((n h + y) w + x) * t_pitch halves, t_pitch >= Ct; only the Ct
+ *                     channels from t on are read (a channel offset is part of the pointer)
+ * Nodes: the mean of every pool x pool window (the last ones clipped to the map; P = ceil(h/pool) ceil(w/pool)),
+ * normalised over the channels, f_p = u_p / r_p, and f_p = 0 where r_p^2 <= 1e-12 (a dead node: no gradient).
+ *   L = 1/(N P^2) * sum_n sum_pq (f^S_p . f^S_q - f^T_p . f^T_q)^2,  diagonal included
+ * fp32 on the f32-input matrix cores; the loss partials are added in fp64 in a fixed order.  No atomics: two calls leave
+ * the same bits.  t == s (the same fp32 tensor) gives loss 0 and gradient 0 exactly.
+ *   dcfp_pairwise_fwd_f32: the loss into *loss_out.  with_grad != 0 also leaves in the workspace what the backward call
+ *     reads (the node matrix, its scales and the N x Ppad x Ppad difference matrix, Ppad = P rounded up to 128).
+ *   dcfp_pairwise_bwd_f32: on the workspace of a with_grad forward call with the same sizes, untouched since:
+ *     dstudent [N,Cs,h,w] = dL/ds * grad_out[0] (grad_out: device scalar, null = 1), every element written once; the
+ *     scalar is the last factor, so the result is the unscaled one times it, bit for bit.
+ *   dcfp_pairwise_workspace_bytes: the workspace of a forward call (with_grad != 0: of a forward + backward pair); 0
+ *     for arguments the calls refuse.
+ * Null s / t / loss_out / dstudent, sizes or pool < 1, an unknown layout and t_pitch < Ct are DCFP_E_BADDESC; a workspace
+ * that is null, too small or not 16-byte aligned DCFP_E_WORKSPACE; N > 65535, h w or a launch grid beyond 2^31 - 1
+ * DCFP_E_UNSUPPORTED.  All of it is checked before any HIP call. */
+#define DCFP_PA_F32_NCHW 0
+#define DCFP_PA_F16_NHWC 1
+size_t dcfp_pairwise_workspace_bytes(int N, int Cs, int Ct, int h, int w, int pool, int with_grad);
+int dcfp_pairwise_fwd_f32(const float* s, const void* t, int t_layout, long long t_pitch, int N, int Cs, int Ct, int h,
+                          int w, int pool, void* workspace, size_t workspace_bytes, float* loss_out /* device scalar */,
+                          int with_grad, dcfp_stream_t stream);
+int dcfp_pairwise_bwd_f32(int N, int Cs, int Ct, int h, int w, int pool, void* workspace, size_t workspace_bytes,
+                          const float* grad_out /* device scalar, may be null */, float* dstudent, dcfp_stream_t stream);
+
 /* ------------------------------------------------ baseline pruning criteria (csrc/score.hip)
  * One fp32 score per output channel of every scored BatchNorm layer; larger means keep.  Every entry point takes a
  * DEVICE array of records (built on the host, uploaded once), returns DCFP_OK for a count of 0 and DCFP_E_BADDESC for a

@@ -4,6 +4,8 @@ the model / optimiser / loss / pruning options).  Without --dataset it runs over
 batches; with --dataset CS|CTX|COCO (and the reference's data flags) it reads a list file through dcfp_amd.datasets,
 whose augmentation chain runs on the device (ADE is not built).
 `--loss-type ...,kd --teacher-from CKPT` adds the distillation term against a frozen teacher.
+`--loss-type gsrl,kdpa` / `gsrl,kd,kdpa` adds the pair-wise similarity term on the backbone's last feature against the same
+teacher; `--loss-para '{"pa_weight": 1.0, "pa_pool": 2}'` sets its weight and its pooling window.
 `--loss-type ce,lovasz` / `gsrl,lovasz` adds the Lovasz-Softmax term on the main head, the surrogate of the per-class IoU
 (DESIGN §18); `--loss-para '{"lovasz_weight": 1.0, "lovasz_bins": 1024}'` sets its weight and its error bins.
 `--prune-type taylor | taylor_w` scores by first-order Taylor instead of `dcfp`, `--slim-lambda` adds the Network
@@ -63,9 +65,10 @@ def get_parser():
     p.add_argument("--warmup", type=int, default=-1)
     p.add_argument("--deepsup", type=str2bool, default="True")
     p.add_argument("--loss-type", type=str, default="ce",
-                   help="ce, ohem, gsrl, kd or lovasz, or several joined by commas and summed: ce,kd / gsrl,lovasz")
+                   help="ce, ohem, gsrl, kd, kdpa or lovasz, or several joined by commas and summed: ce,kd / gsrl,kd,kdpa / "
+                        "gsrl,lovasz")
     p.add_argument("--loss-para", type=str, default="{}",
-                   help="JSON of the criteria's keyword arguments: ds_weight, kd_weight, kd_T, kd_mode, lovasz_weight, "
+                   help="JSON of the criteria's keyword arguments: ds_weight, kd_weight, kd_T, kd_mode, pa_weight, pa_pool, lovasz_weight, "
                         "lovasz_bins (a power of two in 64 .. 4096), ...")
     p.add_argument("--prune-type", type=str, default=None,
                    help="score while training and write score.pth: dcfp (the EIC score), taylor (first-order Taylor on "
@@ -75,7 +78,7 @@ def get_parser():
                         "step (0 = off), in any --prune-type")
     p.add_argument("--channel-cfg", type=str, default=None)
     p.add_argument("--teacher-from", type=str, default=None,
-                   help="checkpoint of the frozen teacher of --loss-type ...,kd: same --model, --backbone and classes as "
+                   help="checkpoint of the frozen teacher of --loss-type ...,kd / ...,kdpa: same --model, --backbone and classes as "
                         "the student, built without --channel-cfg (the dense model the student was pruned from)")
     p.add_argument("--teacher-engine", type=str2bool, default="True",
                    help="freeze the teacher into the fp16 deployment engine (default) or keep the fp32 model")
@@ -113,13 +116,15 @@ class SyntheticDataset:
         return images.to(device, non_blocking=True), labels.to(device, non_blocking=True)
 
 
+TEACHER_TERMS = ("kd", "kdpa")      # loss types that read the frozen teacher: its logits / its backbone feature
 TAYLOR_TYPES = {"taylor": "gate", "taylor_w": "weight"}      # --prune-type -> pruners.taylor_pruning(mode=...)
 
 
 def check_args(args):
     """Argument combinations that cannot run, refused before anything is built."""
-    if "kd" in args.loss_type.split(",") and not args.teacher_from:
-        raise ValueError("--loss-type %s: the kd term needs a teacher, give --teacher-from CKPT" % args.loss_type)
+    for term in TEACHER_TERMS:
+        if term in args.loss_type.split(",") and not args.teacher_from:
+            raise ValueError("--loss-type %s: the %s term needs a teacher, give --teacher-from CKPT" % (args.loss_type, term))
     if args.prune_type is not None and args.prune_type.startswith("taylor") and args.prune_type not in TAYLOR_TYPES:
         raise ValueError("--prune-type %s: the Taylor scorers are %s" % (args.prune_type, ", ".join(sorted(TAYLOR_TYPES))))
     if not args.slim_lambda >= 0.0:
@@ -179,8 +184,10 @@ def main(argv=None):
         optimizer = build_optimizer(args, seg_model)
         optimizer.zero_grad()
         # (built after the optimizer and never handed to it: the teacher's parameters stay out of the arenas)
-        wants_kd = "kd" in args.loss_type.split(",")
-        teacher = build_teacher(args, dataset.num_classes, device) if wants_kd else None
+        wants_kd, wants_pa = ("kd" in args.loss_type.split(",")), ("kdpa" in args.loss_type.split(","))
+        teacher = build_teacher(args, dataset.num_classes, device) if (wants_kd or wants_pa) else None
+        if hasattr(criterion, "attach"):
+            criterion.attach(seg_model)            # (the bare model: the tap sits under any data-parallel wrapper)
         train_pruning = pruners.dcfp_pruning(seg_model, 0.999) if args.prune_type == "dcfp" else None
         if args.prune_type in TAYLOR_TYPES:
             train_pruning = pruners.taylor_pruning(seg_model, TAYLOR_TYPES[args.prune_type])
@@ -216,7 +223,12 @@ def main(argv=None):
                 labels = {"ori": labels, "weight": 1.0 + (labels % 3 == 0).float()}
             if teacher is not None:
                 labels = dict(labels) if isinstance(labels, dict) else {"ori": labels}
-                labels["teacher"] = teacher(images)
+                if wants_pa:                         # one run of the teacher serves both terms
+                    logits, labels["teacher_feat"] = teacher(images, feature=True)
+                    if wants_kd:
+                        labels["teacher"] = logits
+                else:
+                    labels["teacher"] = teacher(images)
             optimizer.zero_grad()
             lr = adjust_learning_rate(optimizer, args.learning_rate, it, args.num_steps, args.power, args.warmup)
             loss = model(images, labels, deepsup=args.deepsup)
