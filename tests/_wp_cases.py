@@ -38,6 +38,11 @@ CASES = [
     ((2, 16, 129, 191, 160, 1, 1, 0, 1), "igemm2_kernel<1,4,4,2,2,0>", None),
     ((2, 16, 129, 191, 160, 3, 1, 1, 1), "igemm2_kernel<9,4,4,2,2,0>", None),
 ]
+# ... and the 1-, 2- and 5-channel layers a pruned model is left with (tests/_narrow_cases.py: one row per kernel they
+# reach): M = 1 in a 32- or 256-row copy, Ck = 1 in a 16-channel one.  Their row-pitched rows stay behind - the
+# descriptors here are dense - and are refreshed and replayed in tests/test_narrow_widths_gpu.py.
+from _narrow_cases import NARROW, NARROW_PITCH  # noqa: E402
+CASES += [(case, fwd, dgrad) for case, fwd, dgrad, _ in NARROW if case not in NARROW_PITCH]
 
 # kernels that leave the kept buffer alone (its layout is still registered and refreshed: nothing may depend on it)
 UNUSED_COPY = ("stem_fwd_kernel", "gemv_1x1_map_kernel")

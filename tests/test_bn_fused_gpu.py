@@ -49,7 +49,10 @@ def _same(a, b, what):
 
 
 # (N, C, H, W): one chunk; a ragged last chunk; HW not a multiple of 1024; several chunks; 256 | HW for the bit mask
-SHAPES = [(2, 8, 16, 16), (3, 5, 36, 52), (2, 6, 100, 100), (4, 16, 64, 128), (1, 3, 4, 4), (5, 33, 48, 64)]
+SHAPES = [(2, 8, 16, 16), (3, 5, 36, 52), (2, 6, 100, 100), (4, 16, 64, 128), (1, 3, 4, 4), (5, 33, 48, 64),
+          # one and two channels, what the pruner leaves of layer1.0.bn2 / layer2.0.bn1: one chunk with the bit mask, a ragged
+          # chunk, several chunks with the bit mask
+          (2, 1, 16, 16), (3, 2, 36, 52), (2, 1, 64, 128)]
 
 
 @pytest.mark.parametrize("shape", SHAPES)

@@ -136,7 +136,7 @@ def _run(case, kind, device, master, x, dy, train, need_dx=True, cached=None, ex
     from dcfp_amd import ops
     fwd, composite = KINDS[kind]
     hip = [copy.deepcopy(b).to(device).train(train) for b in master]
-    before = {n: b.clone() for h in hip for n, b in h.named_buffers()} if not train else None
+    before = {(k, n): b.clone() for k, h in enumerate(hip) for n, b in h.named_buffers()} if not train else None
     xh = x.to(device, copy=True).requires_grad_(need_dx)
     outs, masks, stages = fwd(hip, xh)
     grads = [(len(outs) - 1, dy)] + ([extra] if extra is not None else [])
@@ -160,9 +160,9 @@ def _run(case, kind, device, master, x, dy, train, need_dx=True, cached=None, ex
     used = ops.FANIN_RED_USED[0]
     _compare(case, hip, outs, xh.grad if need_dx else None, ref, r64, r32)
     if not train:                    # eval: running statistics and counters are constants
-        for h in hip:
+        for k, h in enumerate(hip):
             for n, b in h.named_buffers():
-                assert torch.equal(b, before[n]), n
+                assert torch.equal(b, before[(k, n)]), (k, n)
     return SimpleNamespace(ref=ref, r64=r64, r32=r32, masks=masks, used=used, hip=hip)
 
 
