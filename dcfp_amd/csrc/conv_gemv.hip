@@ -2,6 +2,7 @@
 // then a 2048 -> 256 1x1 conv on N x 2048 x 1 x 1).  A matrix-vector product per image; the 256 x 256 MFMA tiles of the
 // general kernels spent 159 us per launch on it (0.03 TF: VERDICT r02 weak 9).  Plain VALU kernels, fixed summation order.
 #include "common.h"
+#include "conv_dispatch.h"
 
 namespace {
 

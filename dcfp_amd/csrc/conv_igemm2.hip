@@ -13,6 +13,7 @@
 //    issued before the 16 MFMAs of step kk), and the next tile's global loads / LDS stores are
 //    spread over the eight 16-MFMA slots of a K-step instead of forming one serial block.
 #include "igemm2_common.h"
+#include "conv_dispatch.h"
 #include <queue>
 #include <vector>
 #include <stdio.h>
@@ -959,32 +960,26 @@ inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 }  // namespace
 
-// implemented in conv_igemm2n.hip: 8 x 2 wave tiles with dead row blocks skipped (ragged M)
-int dcfp_igemm2n_launch(const Igemm2Params& p, int T, hipStream_t stream);
-
-// implemented in conv_igemm2p.hip: the persistent 1x1 LDS-DMA kernel
-int dcfp_igemm2p_launch(const Igemm2Params& p, hipStream_t stream);
-bool dcfp_igemm2_persist();
-
-// ---- entry points used by conv_igemm.hip's C-ABI functions
-size_t dcfp_igemm2_workspace_bytes(int T, int M, int Ck, long long px, int sd) {
+// ---- entry points used by conv_igemm.hip's C-ABI functions (conv_dispatch.h)
+size_t dcfp_igemm2_workspace_bytes(const GemmProblem& g) {
     // rows rounded to 256: covers every tile height and the permuted 256-row layout of conv_igemm2n.hip
-    return (size_t)T * round_up(Ck, ck_pad()) * round_up(M, 256) * sizeof(float);
+    return (size_t)g.T * igemm2_route(g, GemmExtras(), true).CkP * round_up(g.M, 256) * sizeof(float);
 }
 
-int dcfp_igemm2_cfg_id(int M, long long px, int sd) { return pick_cfg(M, px, sd).id; }
+int dcfp_igemm2_cfg_id(const GemmProblem& g) { return pick_cfg(g.M, g.px(), g.sd).id; }
 
 // Number of (mean, M2) partial rows per channel the forward kernel can emit for this shape (each
 // over 128 pixels), or 0 when some tile is not interior / the tile shape has no fused statistics.
-long long dcfp_igemm2_stat_slots(int M, int P, int N, long long out_nstride, const float* out) {
-    const TileCfg c = pick_cfg(M, (long long)N * P, 1);
+long long dcfp_igemm2_stat_slots(const GemmProblem& g, const float* out) {
+    const TileCfg c = pick_cfg(g.M, g.px(), g.sd);
+    const int P = g.P();
     if (c.id != 0 && c.id != 1 && c.id != 2 && c.id != 4) return 0;          // TN == 4 tiles only
-    if (M % c.bm != 0 || P % c.bn != 0 || P % 4 != 0 || out_nstride % 4 != 0 || !dcfp_aligned16(out)) return 0;
-    return (long long)N * (P / c.bn) * (c.bn / 128);
+    if (g.M % c.bm != 0 || P % c.bn != 0 || P % 4 != 0 || g.out_nstride % 4 != 0 || !dcfp_aligned16(out)) return 0;
+    return (long long)g.N * (P / c.bn) * (c.bn / 128);
 }
 
-const char* dcfp_igemm2_cfg_args(int M, long long px, int sd) {
-    switch (pick_cfg(M, px, sd).id) {
+const char* dcfp_igemm2_cfg_args(const GemmProblem& g) {
+    switch (dcfp_igemm2_cfg_id(g)) {
         case 0: return "1,4,1,4,0";
         case 1: return "2,4,1,4,0";
         case 2: return "2,4,2,2,0";
@@ -998,25 +993,86 @@ const char* dcfp_igemm2_cfg_args(int M, long long px, int sd) {
 // LDS-DMA kernels (shifted quads must not need border handling: column shifts multiples of 4, or a row-pitched
 // source), enough pixel tiles to fill the chip, and >= 20 % less MFMA work than the tile the shape gets otherwise.
 // DCFP_IGEMM_DMA8=0: off.
-bool dcfp_igemm2_use_dma8(int T, int M, int P, long long px, int sn, int sd, int off0, int offstep, int HiWi,
-                          int Wo, bool pitched) {
+bool dcfp_igemm2_use_dma8(const GemmProblem& g) {
     static const int mode = [] { const char* e = getenv("DCFP_IGEMM_DMA8"); return e ? atoi(e) : 1; }();   // 0 off, 2 = wherever eligible (A/B)
-    static const bool dma = [] { const char* e = getenv("DCFP_IGEMM_DMA"); return !e || atoi(e) != 0; }();
-    const bool on = mode != 0;
-    if (!on || !dma || deep_k() || sn != 1 || sd != 1 || HiWi != P || Wo % 4 != 0) return false;
-    if (T == 1 ? off0 != 0 : ((((off0 | offstep) & 3) != 0 && !pitched) || off0 + 2 * offstep != -off0)) return false;
-    const long long tiles = ((long long)P + 255) / 256 * (px / P) * ((M + 255) / 256);
+    const int M = g.M, P = g.P(), off0 = g.off0, offstep = g.offstep;
+    if (mode == 0 || !igemm_dma_on() || deep_k() || g.sn != 1 || g.sd != 1 || g.HiWi() != P || g.Wo % 4 != 0) return false;
+    if (g.T == 1 ? off0 != 0 : ((((off0 | offstep) & 3) != 0 && !g.pitched()) || off0 + 2 * offstep != -off0)) return false;
+    const long long tiles = ((long long)P + 255) / 256 * g.N * ((M + 255) / 256);
     if (tiles < 192) return false;
     if (mode == 2) return true;
     // Measured (tools/conv_bench.py, profiles/r02_dma8_ab.txt): at 8 live row blocks this kernel is 10..17 % slower
     // than the 4 x 4-tile kernels (8-byte stores, 2-way LDS conflicts on the A fragments, no fused BatchNorm
     // statistics), at 7 of 8 it is 10 % faster, and on ragged M <= 64 it beats the register-staged 64 x 512
     // tile by 32..35 % at the same MFMA count.
-    const TileCfg c = pick_cfg(M, px, sd);
+    const TileCfg c = pick_cfg(M, g.px(), g.sd);
     if (M % c.bm == 0) return false;           // exact fit: the tile kernels (and their statistics epilogue) stay
     if (c.bm <= 64) return true;
     const long long old_rows = (long long)((M + c.bm - 1) / c.bm) * c.bm, new_rows = (long long)((M + 31) / 32) * 32;
     return 10 * new_rows <= 9 * old_rows;
+}
+
+// DCFP_IGEMM_PERSIST=0: 1x1 convs on the one-tile-per-workgroup kernel instead of conv_igemm2p.hip
+bool dcfp_igemm2_persist() {
+    static const bool persist = [] { const char* e = getenv("DCFP_IGEMM_PERSIST"); return !e || atoi(e) != 0; }();
+    return persist;
+}
+
+// shapes the 256 x 256 LDS-DMA kernels take
+bool dcfp_igemm2_dma_shape(const GemmProblem& g) {
+    static const bool dma9 = [] { const char* e = getenv("DCFP_IGEMM_DMA9"); return !e || atoi(e) != 0; }();
+    if (!igemm_dma_on() || dcfp_igemm2_cfg_id(g) != 4 || g.sn != 1 || g.sd != 1 || g.HiWi() != g.P() || g.Wo % 4 != 0)
+        return false;
+    return g.T == 1 ? g.off0 == 0 : dma9;
+}
+
+// THE route: which kernel dcfp_igemm2_run launches and how it tiles the problem.  Every query below reads it (with no
+// options and vec_store = true: the plain call with dense, 16-byte-aligned outputs); nothing else repeats its conditions.
+Igemm2Route igemm2_route(const GemmProblem& g, const GemmExtras& x, bool vec_store) {
+    const TileCfg c = pick_cfg(g.M, g.px(), g.sd);
+    const bool plain = !x.scale && !x.relu && !x.stat_part;     // (bias is handled by the ragged-M kernel's epilogue)
+    const bool d8 = plain && !x.wp_nstride && !x.fan_src && dcfp_igemm2_use_dma8(g);
+    const bool off_grid = ((g.off0 | g.offstep) & 3) != 0;      // tap shifts that are no multiples of 4 columns
+    Igemm2Route r = {};
+    r.cfg = c.id; r.bm = d8 ? 256 : c.bm; r.bn = d8 ? 256 : c.bn;
+    r.CkP = round_up(g.Ck, ck_pad()); r.Mpad = round_up(g.M, r.bm);
+    r.dma_shape = dcfp_igemm2_dma_shape(g);
+    {
+        const int t2d = igemm_2d_mode();
+        const bool fits = (t2d == 4 || t2d == 5) && g.Hi % (256 >> t2d) == 0 && g.Wi % (1 << t2d) == 0;
+        r.tile2d = (fits && !g.pitched() && g.T == 9 && off_grid && g.Ho == g.Hi && g.Wo == g.Wi) ? t2d : 0;
+    }
+    r.tiles_per_img = (g.P() + r.bn - 1) / r.bn;
+    if (g.sd > 1) {     // strided dgrad: sd*sd phases, each tiled over its own coarse grid
+        r.Hc = (g.Ho + g.sd - 1) / g.sd; r.Wc = (g.Wo + g.sd - 1) / g.sd;
+        r.tiles_per_phase = (r.Hc * r.Wc + r.bn - 1) / r.bn;
+        r.tiles_per_img = g.sd * g.sd * r.tiles_per_phase;
+        if (g.T == 1) {   // a 1x1 conv reaches ONE phase: only that phase gets tiles (they also write the zeros)
+            const int ph = ((-g.off0) % g.sd + g.sd) % g.sd;
+            r.zfold = ph * g.sd + ph + 1;
+            r.tiles_per_img = r.tiles_per_phase;
+        }
+    }
+    r.tiles_n_total = r.tiles_per_img * g.N;
+    r.tiles_m = r.Mpad / r.bm;
+    if (d8)
+        r.family = IGEMM2_DMA8;
+    else if (r.dma_shape && vec_store && !x.bias && !x.scale && !x.relu && !(x.stat_part && x.accumulate)) {
+        r.family = (g.T == 1 && dcfp_igemm2_persist()) ? IGEMM2_DMA1P : IGEMM2_DMA;
+        r.mixed = g.T == 9 && off_grid && !g.pitched();      // pitched rows: shifted quads need no border handling
+    } else
+        r.family = IGEMM2_TILE;
+    return r;
+}
+
+// the problem's and the route's geometry as the kernels (and the host's tile accounting below) read it
+static void set_tiling(Igemm2Params& p, const GemmProblem& g, const Igemm2Route& r) {
+    p.N = g.N; p.M = g.M; p.Ck = g.Ck; p.CkP = r.CkP; p.Mpad = r.Mpad;
+    p.Hi = g.Hi; p.Wi = g.Wi; p.Ho = g.Ho; p.Wo = g.Wo; p.P = g.P();
+    p.sn = g.sn; p.sd = g.sd; p.off0 = g.off0; p.offstep = g.offstep;
+    p.tile2d = r.tile2d;
+    p.tiles_per_img = r.tiles_per_img; p.tiles_n_total = r.tiles_n_total; p.tiles_m = r.tiles_m;
+    p.Hc = r.Hc; p.Wc = r.Wc; p.tiles_per_phase = r.tiles_per_phase; p.zfold = r.zfold;
 }
 
 // Dead kernel rows (9-tap LDS-DMA kernels): 0 = no skipping, 1 = skip in tile order, 2 = skip with the tiles dispatched
@@ -1027,7 +1083,6 @@ bool dcfp_igemm2_use_dma8(int T, int M, int P, long long px, int sn, int sd, int
 // the host (workgroups go to the first free CU in blockIdx order, one per CU) and skipping is used where it
 // predicts >= 3 % (measured: dilation 36 forward -17 %, layer4 dilation 16 -8 %, ASPP dgrad -4 / -10 / -17 %).
 // DCFP_IGEMM_TAPSKIP = 0 / 1 / 2 forces a mode (A/B).
-bool dcfp_igemm2_dma_shape(int T, int M, int Ck, int P, long long px, int sn, int sd, int off0, int HiWi, int Wo);
 
 // kernel rows (of 3) that tile `ti` of an image executes - the same arithmetic as the kernels' t_beg / t_end
 static int tile_live_rows(const Igemm2Params& p, int ti) {
@@ -1109,33 +1164,23 @@ static int pick_tapskip(const Igemm2Params& p, int bn) {
 
 // Fraction of the nominal K-steps (9 taps x channels, padded taps included - the usual FLOP convention) that the
 // kernel chosen for this problem executes: < 1 where dead kernel rows are skipped.  For honest accounting only.
-double dcfp_igemm2_exec_fraction(int T, int M, int Ck, int N, int Hi, int Wi, int Ho, int Wo, int sn, int sd,
-                                 int off0, int offstep, bool pitched) {
-    if (T != 9 || sn != 1 || sd != 1) return 1.0;
-    const long long px = (long long)N * Ho * Wo;
-    const bool d8 = dcfp_igemm2_use_dma8(T, M, Ho * Wo, px, sn, sd, off0, offstep, Hi * Wi, Wo, pitched);
-    if (!d8 && !dcfp_igemm2_dma_shape(T, M, Ck, Ho * Wo, px, sn, sd, off0, Hi * Wi, Wo)) return 1.0;
+double dcfp_igemm2_exec_fraction(const GemmProblem& g) {
+    if (g.T != 9 || g.sn != 1 || g.sd != 1) return 1.0;
+    const Igemm2Route r = igemm2_route(g, GemmExtras(), true);
+    if (r.family == IGEMM2_TILE) return 1.0;
     Igemm2Params p = {};
-    p.N = N; p.Hi = Hi; p.Wi = Wi; p.Ho = Ho; p.Wo = Wo; p.P = Ho * Wo; p.off0 = off0; p.offstep = offstep;
-    p.tiles_per_img = (p.P + 255) / 256; p.tiles_n_total = p.tiles_per_img * N; p.tiles_m = (M + 255) / 256;
-    {
-        static const int t2d = [] { const char* e = getenv("DCFP_IGEMM_2D"); return e ? atoi(e) : 5; }();
-        const bool fits = (t2d == 4 || t2d == 5) && Hi % (256 >> t2d) == 0 && Wi % (1 << t2d) == 0;
-        p.tile2d = (!d8 && fits && !pitched && ((off0 | offstep) & 3) != 0 && Ho == Hi && Wo == Wi) ? t2d : 0;
-    }
-    if (pick_tapskip(p, 256) == 0) return 1.0;
+    set_tiling(p, g, r);
+    if (pick_tapskip(p, r.bn) == 0) return 1.0;
     long long live = 0;
     for (int ti = 0; ti < p.tiles_per_img; ++ti) live += tile_live_rows(p, ti);
     return (double)live / (3.0 * p.tiles_per_img);
 }
 
 // Layout of the Wp copy dcfp_igemm2_run would build for this problem (everything but the pointers)
-void dcfp_igemm2_wp_layout(int T, int M, int Ck, int P, long long px, int sn, int sd, int off0, int offstep, int HiWi,
-                           int Wo, bool pitched, int sAm, int sAc, DcfpWpEntry* e) {
-    const TileCfg c = pick_cfg(M, px, sd);
-    const bool d8 = dcfp_igemm2_use_dma8(T, M, P, px, sn, sd, off0, offstep, HiWi, Wo, pitched);
-    e->T = T; e->Ck = Ck; e->CkP = round_up(Ck, ck_pad()); e->M = M; e->Mpad = round_up(M, d8 ? 256 : c.bm);
-    e->sAm = sAm; e->sAc = sAc; e->perm8 = d8 ? 1 : 0;
+void dcfp_igemm2_wp_layout(const GemmProblem& g, DcfpWpEntry* e) {
+    const Igemm2Route r = igemm2_route(g, GemmExtras(), true);
+    e->T = g.T; e->Ck = g.Ck; e->CkP = r.CkP; e->M = g.M; e->Mpad = r.Mpad;
+    e->sAm = g.sAm; e->sAc = g.sAc; e->perm8 = r.family == IGEMM2_DMA8 ? 1 : 0;
 }
 
 int dcfp_igemm2_permute_multi(const DcfpWpEntry* table, int n, long long total_blocks, hipStream_t stream) {
@@ -1143,105 +1188,59 @@ int dcfp_igemm2_permute_multi(const DcfpWpEntry* table, int n, long long total_b
     DCFP_RETURN_LAUNCH();
 }
 
-// DCFP_IGEMM_PERSIST=0: 1x1 convs on the one-tile-per-workgroup kernel instead of conv_igemm2p.hip
-bool dcfp_igemm2_persist() {
-    static const bool persist = [] { const char* e = getenv("DCFP_IGEMM_PERSIST"); return !e || atoi(e) != 0; }();
-    return persist;
-}
-
-// shapes the LDS-DMA kernel takes (also used for dcfp_conv2d_kernel_name)
-bool dcfp_igemm2_dma_shape(int T, int M, int Ck, int P, long long px, int sn, int sd, int off0, int HiWi, int Wo) {
-    static const bool dma = [] { const char* e = getenv("DCFP_IGEMM_DMA"); return !e || atoi(e) != 0; }();   // =0: off
-    static const bool dma9 = [] { const char* e = getenv("DCFP_IGEMM_DMA9"); return !e || atoi(e) != 0; }();
-    if (!dma || pick_cfg(M, px, sd).id != 4 || sn != 1 || sd != 1 || HiWi != P || Wo % 4 != 0) return false;
-    return T == 1 ? off0 == 0 : dma9;
-}
-
-// in: B-source tensor; w: reference-layout weights; (sAm, sAc): A strides in w
-int dcfp_igemm2_run(const float* in, long long in_nstride, const float* w, int sAm, int sAc,
-                    const float* bias, float* out, long long out_nstride, int N, int M, int Ck, int T,
-                    int Hi, int Wi, int Ho, int Wo, int sn, int sd, int off0, int offstep,
-                    int accumulate, void* workspace, size_t workspace_bytes, hipStream_t stream,
-                    const float* scale, const float* shift, const float* residual, int relu,
-                    float* stat_part, int wp_valid, int in_pitch, long long wp_nstride, const float* fan_src,
-                    const unsigned long long* fan_mask, const Igemm2Red* red) {
-    const long long px = (long long)N * Ho * Wo;
-    const TileCfg c = pick_cfg(M, px, sd);
-    Igemm2Params p;
-    p.stat_part = stat_part;
-    p.wp_nstride = wp_nstride;
-    p.fan_src = fan_src; p.fan_mask = fan_mask;
-    p.red_x = red ? red->x : nullptr; p.red_mask = red ? red->mask : nullptr;
-    p.red_mean = red ? red->mean : nullptr; p.red_part = red ? red->part : nullptr;
-    if (red && !fan_src) return DCFP_E_BADDESC;
-    p.in = in; p.bias = bias; p.out = out;
-    p.scale = scale; p.shift = shift; p.residual = residual; p.relu = relu;
-    p.in_nstride = in_nstride; p.out_nstride = out_nstride;
-    p.N = N; p.M = M; p.Ck = Ck; p.CkP = round_up(Ck, ck_pad()); p.Mpad = round_up(M, c.bm);
-    const bool plain = !scale && !relu && !stat_part;     // (bias is handled by the ragged-M kernel's epilogue)
-    const bool d8 = plain && !wp_nstride && !fan_src && dcfp_igemm2_use_dma8(T, M, Ho * Wo, px, sn, sd, off0, offstep, Hi * Wi, Wo,
-                                                                 in_pitch > 0 && in_pitch != Wi);
-    if (d8) p.Mpad = round_up(M, 256);
-    p.Hi = Hi; p.Wi = Wi; p.Ho = Ho; p.Wo = Wo; p.P = Ho * Wo;
-    p.in_pitch = in_pitch > 0 ? in_pitch : Wi;
-    const bool pitched = p.in_pitch != Wi;
-    if (pitched) {   // only the 9-tap LDS-DMA kernels read pitched sources; every tap's column shift must fit the tail
-        const int reach = off0 < 0 ? -off0 : off0;      // |first tap shift|; the last is off0 + 2*offstep = -off0 (pad = dil)
-        if (T != 9 || p.in_pitch < Wi + reach || off0 + 2 * offstep != -off0 || (p.in_pitch & 3) ||
-            (!d8 && (bias || !dcfp_igemm2_dma_shape(T, M, Ck, Ho * Wo, px, sn, sd, off0, Hi * Wi, Wo))) || scale || relu)
+// in: B-source tensor; w: reference-layout weights
+int dcfp_igemm2_run(const GemmProblem& g, const float* in, const float* w, float* out, void* workspace, size_t workspace_bytes,
+                    const GemmExtras& x, hipStream_t stream) {
+    if (x.red && !x.fan_src) return DCFP_E_BADDESC;
+    const int T = g.T;
+    const bool vec_store = (g.P() % 4 == 0) && (g.out_nstride % 4 == 0) && dcfp_aligned16(out);
+    const Igemm2Route r = igemm2_route(g, x, vec_store);
+    const bool d8 = r.family == IGEMM2_DMA8;
+    Igemm2Params p = {};
+    set_tiling(p, g, r);
+    p.stat_part = x.stat_part;
+    p.wp_nstride = x.wp_nstride;
+    p.fan_src = x.fan_src; p.fan_mask = x.fan_mask;
+    if (x.red) { p.red_x = x.red->x; p.red_mask = x.red->mask; p.red_mean = x.red->mean; p.red_part = x.red->part; }
+    p.in = in; p.bias = x.bias; p.out = out;
+    p.scale = x.scale; p.shift = x.shift; p.residual = x.residual; p.relu = x.relu;
+    p.in_nstride = g.in_nstride; p.out_nstride = g.out_nstride;
+    p.in_pitch = g.in_pitch > 0 ? g.in_pitch : g.Wi;
+    if (g.pitched()) {   // only the 9-tap LDS-DMA kernels read pitched sources; every tap's column shift must fit the tail
+        const int reach = g.off0 < 0 ? -g.off0 : g.off0;      // |first tap shift|; the last is off0 + 2*offstep = -off0 (pad = dil)
+        if (T != 9 || p.in_pitch < g.Wi + reach || g.off0 + 2 * g.offstep != -g.off0 || (p.in_pitch & 3) ||
+            (!d8 && (x.bias || !r.dma_shape)) || x.scale || x.relu)
             return DCFP_E_UNSUPPORTED;
-        if (!d8 && stat_part && dcfp_igemm2_use_dma8(T, M, Ho * Wo, px, sn, sd, off0, offstep, Hi * Wi, Wo, true))
+        if (!d8 && x.stat_part && dcfp_igemm2_use_dma8(g))
             return DCFP_E_UNSUPPORTED;                  // (cannot happen: such shapes report no statistics slots)
     }
-    {
-        static const int t2d = [] { const char* e = getenv("DCFP_IGEMM_2D"); return e ? atoi(e) : 5; }();   // 0: off; 4 / 5: 16 / 32 columns
-        const bool fits = (t2d == 4 || t2d == 5) && Hi % (256 >> t2d) == 0 && Wi % (1 << t2d) == 0;
-        p.tile2d = (fits && !pitched && T == 9 && ((off0 | offstep) & 3) != 0 && Ho == Hi && Wo == Wi) ? t2d : 0;
-    }
-    p.tapskip = 0;      // decided below, once the tiling is known
     {
         static const int nt = [] { const char* e = getenv("DCFP_IGEMM_NT"); return e ? atoi(e) : 0; }();
         p.nt_store = nt;
     }
-    p.tiles_per_img = (p.P + (d8 ? 256 : c.bn) - 1) / (d8 ? 256 : c.bn);
-    p.Hc = p.Wc = p.tiles_per_phase = p.zfold = 0;
-    if (sd > 1) {     // strided dgrad: sd*sd phases, each tiled over its own coarse grid
-        p.Hc = (Ho + sd - 1) / sd; p.Wc = (Wo + sd - 1) / sd;
-        p.tiles_per_phase = (p.Hc * p.Wc + c.bn - 1) / c.bn;
-        p.tiles_per_img = sd * sd * p.tiles_per_phase;
-        if (T == 1) {   // a 1x1 conv reaches ONE phase: only that phase gets tiles (they also write the zeros)
-            const int ph = ((-off0) % sd + sd) % sd;
-            p.zfold = ph * sd + ph + 1;
-            p.tiles_per_img = p.tiles_per_phase;
-        }
-    }
-    p.tiles_n_total = p.tiles_per_img * N;
-    p.tiles_m = p.Mpad / (d8 ? 256 : c.bm);
-    p.sn = sn; p.sd = sd; p.off0 = off0; p.offstep = offstep;
-    p.accumulate = accumulate;
-    p.vec_store = (p.P % 4 == 0) && (out_nstride % 4 == 0) && dcfp_aligned16(out);
-    if (T == 9 && sd == 1 && sn == 1) p.tapskip = pick_tapskip(p, d8 ? 256 : c.bn);
+    p.accumulate = x.accumulate;
+    p.vec_store = vec_store;
+    if (T == 9 && g.sd == 1 && g.sn == 1) p.tapskip = pick_tapskip(p, r.bn);
     const size_t need = (size_t)T * p.CkP * p.Mpad * sizeof(float);
     if (!workspace || workspace_bytes < need || !dcfp_aligned16(workspace)) return DCFP_E_WORKSPACE;
     float* wp = static_cast<float*>(workspace);
     p.wp = wp;
-    if (!wp_valid) {   // (the caller's buffer already holds Wp of these weights for this pass and shape otherwise)
+    if (!x.wp_valid) {   // (the caller's buffer already holds Wp of these weights for this pass and shape otherwise)
         const long long total = (long long)T * p.CkP * p.Mpad;
         long long b = (total + 255) / 256;
         if (b > 2048) b = 2048;
         hipLaunchKernelGGL(permute_weights_kernel, dim3((unsigned)b), dim3(256), 0, stream, w, wp, T,
-                           Ck, p.CkP, M, p.Mpad, sAm, sAc, d8 ? 1 : 0);
+                           g.Ck, p.CkP, g.M, p.Mpad, g.sAm, g.sAc, d8 ? 1 : 0);
     }
     if (d8) {
-        if (!p.vec_store || wp_nstride || fan_src) return DCFP_E_UNSUPPORTED;
+        if (!p.vec_store || x.wp_nstride || x.fan_src) return DCFP_E_UNSUPPORTED;
         return dcfp_igemm2n_launch(p, T, stream);
     }
-    if (dcfp_igemm2_dma_shape(T, M, Ck, p.P, px, sn, sd, off0, Hi * Wi, Wo) && p.vec_store && !bias && !scale &&
-        !relu && !(stat_part && accumulate)) {
+    if (r.family != IGEMM2_TILE) {
         const long long groups = ((long long)p.tiles_n_total + 7) / 8;
         const long long blocks = groups * 8 * p.tiles_m;
         // 64 KB of operand buffers; the statistics epilogue re-uses them as 4 x [64 rows][33] (sum, M2) pairs
-        const size_t lds = stat_part ? (size_t)4 * 64 * 33 * 8 : (size_t)2 * BK * 512 * sizeof(float);
+        const size_t lds = x.stat_part ? (size_t)4 * 64 * 33 * 8 : (size_t)2 * BK * 512 * sizeof(float);
         auto launch = [&](auto kern) -> int {
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1249,18 +1248,19 @@ int dcfp_igemm2_run(const float* in, long long in_nstride, const float* w, int s
             hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, stream, p);
             DCFP_RETURN_LAUNCH();
         };
+        const bool accumulate = x.accumulate != 0;
         if (T == 1) {
-            if (fan_src && (M % 256 != 0 || p.P % 256 != 0 || !dcfp_igemm2_persist())) return DCFP_E_UNSUPPORTED;
-            if (dcfp_igemm2_persist()) return dcfp_igemm2p_launch(p, stream);
-            if (wp_nstride) return DCFP_E_UNSUPPORTED;
+            if (x.fan_src && (g.M % 256 != 0 || p.P % 256 != 0 || r.family != IGEMM2_DMA1P)) return DCFP_E_UNSUPPORTED;
+            if (r.family == IGEMM2_DMA1P) return dcfp_igemm2p_launch(p, stream);
+            if (x.wp_nstride) return DCFP_E_UNSUPPORTED;
             return accumulate ? launch(igemm2_dma_kernel<1, false, true>) : launch(igemm2_dma_kernel<1, false, false>);
         }
-        if (((off0 | offstep) & 3) == 0 || pitched)    // pitched rows: shifted quads need no border handling
+        if (!r.mixed)
             return accumulate ? launch(igemm2_dma_kernel<9, false, true>) : launch(igemm2_dma_kernel<9, false, false>);
         return accumulate ? launch(igemm2_dma_kernel<9, true, true>) : launch(igemm2_dma_kernel<9, true, false>);
     }
-    if (wp_nstride || fan_src) return DCFP_E_UNSUPPORTED;     // per-image weights / masked fan-in: the persistent 1x1 kernel only
-    return T == 1 ? launch_taps<1>(p, c.id, stream) : launch_taps<9>(p, c.id, stream);
+    if (x.wp_nstride || x.fan_src) return DCFP_E_UNSUPPORTED;     // per-image weights / masked fan-in: the persistent 1x1 kernel only
+    return T == 1 ? launch_taps<1>(p, r.cfg, stream) : launch_taps<9>(p, r.cfg, stream);
 }
 
 int dcfp_igemm2_ck_pad() { return ck_pad(); }

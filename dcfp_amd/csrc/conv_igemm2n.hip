@@ -18,6 +18,7 @@
 // A lane owns 2 consecutive pixels (8-byte stores); the dispatcher uses this kernel only where it saves >= 20 %
 // of the MFMA work against the tile the shape would otherwise get.
 #include "igemm2_common.h"
+#include "conv_dispatch.h"
 #include <stdlib.h>
 
 namespace {

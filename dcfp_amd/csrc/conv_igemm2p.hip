@@ -29,6 +29,7 @@
 // the compiler tracks, and its conservative vmcnt(N) waits in front of the next copies then also wait for
 // the (untracked, inline-asm) LDS-DMA copies in flight: the first version of this kernel lost 12 % to that.
 #include "igemm2_common.h"
+#include "conv_dispatch.h"
 #include <stdlib.h>
 
 namespace {

@@ -21,6 +21,7 @@
 // Diagnosis builds (same instruction stream minus one cost, used for the numbers in DESIGN.md §3b):
 // -DI3_DBG_NOLOADB (activation loads fetch nothing), -DI3_DBG_NOSTORE (no epilogue stores).
 #include "common.h"
+#include "conv_dispatch.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <type_traits>
@@ -506,36 +507,35 @@ size_t dcfp_igemm3_workspace_bytes(int T, int M, int Ck) {
     return (size_t)T * round_up(Ck, BK) * round_up(M, BM) * 3 * sizeof(__bf16);
 }
 
-// same argument meaning as dcfp_igemm2_run; stride-1 sampling only (sn == sd == 1)
-int dcfp_igemm3_run(const float* in, long long in_nstride, const float* w, int sAm, int sAc,
-                    const float* bias, float* out, long long out_nstride, int N, int M, int Ck, int T,
-                    int Hi, int Wi, int Ho, int Wo, int off0, int offstep, int accumulate,
-                    void* workspace, size_t workspace_bytes, hipStream_t stream, const float* scale,
-                    const float* shift, const float* residual, int relu, int wp_valid) {
+// same arguments as dcfp_igemm2_run; stride-1 sampling only (sn == sd == 1), of the options the inference epilogue,
+// accumulate and wp_valid
+int dcfp_igemm3_run(const GemmProblem& g, const float* in, const float* w, float* out, void* workspace, size_t workspace_bytes,
+                    const GemmExtras& x, hipStream_t stream) {
     Igemm3Params p;
-    if (bias) return DCFP_E_UNSUPPORTED;   // callers route bias convs to the fp32 kernel
+    if (x.bias) return DCFP_E_UNSUPPORTED;   // callers route bias convs to the fp32 kernel
+    const int T = g.T;
     p.in = in; p.out = out;
-    p.in_nstride = in_nstride; p.out_nstride = out_nstride;
-    p.N = N; p.M = M; p.Ck = Ck; p.CkP = round_up(Ck, BK); p.Mpad = round_up(M, BM);
-    p.Hi = Hi; p.Wi = Wi; p.Ho = Ho; p.Wo = Wo; p.P = Ho * Wo;
+    p.in_nstride = g.in_nstride; p.out_nstride = g.out_nstride;
+    p.N = g.N; p.M = g.M; p.Ck = g.Ck; p.CkP = round_up(g.Ck, BK); p.Mpad = round_up(g.M, BM);
+    p.Hi = g.Hi; p.Wi = g.Wi; p.Ho = g.Ho; p.Wo = g.Wo; p.P = g.P();
     p.tiles_per_img = (p.P + BN - 1) / BN;
-    p.tiles_n_total = p.tiles_per_img * N;
+    p.tiles_n_total = p.tiles_per_img * g.N;
     p.tiles_m = p.Mpad / BM;
-    p.off0 = off0; p.offstep = offstep;
-    p.accumulate = accumulate;
-    p.scale = scale; p.shift = shift; p.residual = residual; p.relu = relu;
-    if (scale && (accumulate || !shift)) return DCFP_E_BADDESC;
-    const size_t need = dcfp_igemm3_workspace_bytes(T, M, Ck);
+    p.off0 = g.off0; p.offstep = g.offstep;
+    p.accumulate = x.accumulate;
+    p.scale = x.scale; p.shift = x.shift; p.residual = x.residual; p.relu = x.relu;
+    if (x.scale && (x.accumulate || !x.shift)) return DCFP_E_BADDESC;
+    const size_t need = dcfp_igemm3_workspace_bytes(T, g.M, g.Ck);
     if (!workspace || workspace_bytes < need || !dcfp_aligned16(workspace)) return DCFP_E_WORKSPACE;
-    if ((long long)Ck * Hi * Wi * 4 > 0x7fffffffLL || need > 0x7fffffffULL) return DCFP_E_UNSUPPORTED;
+    if ((long long)g.Ck * g.Hi * g.Wi * 4 > 0x7fffffffLL || need > 0x7fffffffULL) return DCFP_E_UNSUPPORTED;
     __bf16* wp3 = static_cast<__bf16*>(workspace);
     p.wp3 = wp3;
-    if (!wp_valid) {
+    if (!x.wp_valid) {
         const long long total = (long long)T * p.CkP * p.Mpad;
         long long b = (total + 255) / 256;
         if (b > 4096) b = 4096;
         hipLaunchKernelGGL(permute_split_weights_kernel, dim3((unsigned)b), dim3(256), 0, stream, w, wp3,
-                           T, Ck, p.CkP, M, p.Mpad, sAm, sAc);
+                           T, g.Ck, p.CkP, g.M, p.Mpad, g.sAm, g.sAc);
     }
     const long long groups = ((long long)p.tiles_n_total + 7) / 8;
     const long long blocks = groups * 8 * p.tiles_m;
@@ -549,7 +549,7 @@ int dcfp_igemm3_run(const float* in, long long in_nstride, const float* w, int s
         return hipSuccess;
     };
     hipError_t e;
-    const int epi = scale ? 2 : accumulate ? 1 : 0;
+    const int epi = x.scale ? 2 : x.accumulate ? 1 : 0;
     if (T == 1) e = epi == 2 ? launch(igemm3_kernel<1, 2>) : epi == 1 ? launch(igemm3_kernel<1, 1>) : launch(igemm3_kernel<1, 0>);
     else        e = epi == 2 ? launch(igemm3_kernel<9, 2>) : epi == 1 ? launch(igemm3_kernel<9, 1>) : launch(igemm3_kernel<9, 0>);
     if (e != hipSuccess) return (int)e;

@@ -15,6 +15,7 @@
 //             the slabs in wave order (fixed order, no atomics).
 // fp32 multiplicands, fp32 accumulation on the fp32 MFMA, as everywhere.  Padding = out-of-range buffer offsets (read zeros).
 #include "igemm2_common.h"
+#include "conv_dispatch.h"
 #include <stdlib.h>
 
 namespace {
@@ -291,8 +292,10 @@ long long dcfp_stem_stat_slots(const DcfpConvDesc* d, const float* y, long long 
     return (long long)d->N * d->Hout * d->Wout / 128;
 }
 
-int dcfp_stem_fwd(const DcfpConvDesc* d, const float* x, const float* w, const float* bias, float* y, long long y_nstride,
-                  hipStream_t stream, float* stat_part) {
+int dcfp_stem_fwd(const DcfpConvDesc* d, const float* x, const float* w, float* y, long long y_nstride, const GemmExtras& ex,
+                  hipStream_t stream) {
+    const float* bias = ex.bias;
+    float* stat_part = ex.stat_part;
     StemParams p = {};
     p.x = x; p.w = w; p.y = y; p.bias = bias; p.stat = stat_part;
     p.y_nstride = y_nstride ? y_nstride : (long long)d->Cout * d->Hout * d->Wout;

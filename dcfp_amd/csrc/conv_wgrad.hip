@@ -13,17 +13,9 @@
 // Both operands are pixel-contiguous in NCHW, so LDS keeps them K-contiguous:
 // As[m][k], Bs[n][k] (row pitch 20 floats: conflict-free ds_read_b128), and one
 // 16-byte read per lane feeds FOUR consecutive k-steps of a 32x32x2 MFMA tile.
-#include "common.h"
+#include "conv_dispatch.h"
 #include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 #include <type_traits>
-
-// EXPERIMENTAL opt-in: DCFP_CONV_MATH=bf16x3 routes qualifying wgrad shapes to conv_wgrad3.hip
-int dcfp_wgrad3_launch(const float* dy, long long dy_nstride, const float* x, long long x_nstride,
-                       float* out, int N, int M, int Cin, int T, int H, int W, int Ho, int Wo, int pad,
-                       int dil, int Kpix, int kchunk, int splits, int tiles_m, int tiles_n,
-                       hipStream_t stream);
 
 namespace {
 
@@ -764,12 +756,9 @@ struct Plan {
     bool half;        // 128 x 256 tile on wgrad_dma_kernel<1, .., HALF>: two workgroups per CU (1x1 convs, Cout % 128 == 0)
 };
 
-static bool math_bf16x3();
-
 // shapes the LDS-DMA kernels take apart from the tile choice: stride 1, output = input size, rows multiple of 16 px
 bool dma_geometry(const DcfpConvDesc* d) {
-    static const bool on = [] { const char* e = getenv("DCFP_WGRAD_DMA"); return !e || atoi(e) != 0; }();   // =0: off
-    return on && d->stride == 1 && d->Hout == d->H && d->Wout == d->W && d->W % 16 == 0;
+    return wgrad_dma_on() && d->stride == 1 && d->Hout == d->H && d->Wout == d->W && d->W % 16 == 0;
 }
 
 Plan make_plan(const DcfpConvDesc* d) {
@@ -853,30 +842,7 @@ Plan make_plan(const DcfpConvDesc* d) {
     return pl;
 }
 
-int check_desc(const DcfpConvDesc* d) {
-    if (!d) return DCFP_E_BADDESC;
-    if (d->N <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->H <= 0 || d->W <= 0 || d->stride <= 0 ||
-        d->dil <= 0 || d->pad < 0)
-        return DCFP_E_BADDESC;
-    if (d->KH != d->KW || (d->KH != 1 && d->KH != 3)) return DCFP_E_UNSUPPORTED;
-    const int ho = (d->H + 2 * d->pad - d->dil * (d->KH - 1) - 1) / d->stride + 1;
-    const int wo = (d->W + 2 * d->pad - d->dil * (d->KW - 1) - 1) / d->stride + 1;
-    if (ho != d->Hout || wo != d->Wout || ho <= 0 || wo <= 0) return DCFP_E_BADDESC;
-    if ((d->x_pitch != 0 && (d->x_pitch < d->W || (d->x_pitch & 3))) ||
-        (d->dy_pitch != 0 && (d->dy_pitch < d->Wout || (d->dy_pitch & 3))))
-        return DCFP_E_BADDESC;
-    if ((long long)d->Cin * d->H * (d->x_pitch ? d->x_pitch : d->W) >= (1LL << 29) ||
-        (long long)d->Cout * d->Hout * (d->dy_pitch ? d->dy_pitch : d->Wout) >= (1LL << 29) ||
-        (long long)d->Cout * d->Cin * d->KH * d->KW >= (1LL << 29))
-        return DCFP_E_UNSUPPORTED;
-    return DCFP_OK;
-}
-
 // EXPERIMENTAL opt-in: DCFP_CONV_MATH=bf16x3 routes qualifying wgrad shapes to conv_wgrad3.hip
-static bool math_bf16x3() {
-    static const bool v = [] { const char* e = getenv("DCFP_CONV_MATH"); return e && !strcmp(e, "bf16x3"); }();
-    return v;
-}
 static bool wgrad3_ok(const DcfpConvDesc* d, int cfg) {
     return math_bf16x3() && cfg == 0 && d->stride == 1 && (d->Wout % 4 == 0);
 }
@@ -893,20 +859,17 @@ int launch_cfg(const WgradParams& p, long long blocks, hipStream_t stream) {
         if (e != hipSuccess) return (int)e;
     }
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(NT), lds, stream, p);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? DCFP_OK : (int)e;
+    DCFP_RETURN_LAUNCH();
 }
 
 // shapes the LDS-DMA kernel takes: 256 x 256 tile, stride 1, output = input size, rows of 16 k pixels
 static bool wgrad_dma_ok(const DcfpConvDesc* d, int cfg) {
-    static const bool on = [] { const char* e = getenv("DCFP_WGRAD_DMA"); return !e || atoi(e) != 0; }();   // =0: off
     static const bool mixed_too = [] { const char* e = getenv("DCFP_WGRAD_DMA_MIXED"); return !e || atoi(e) != 0; }();   // =0: off
     const bool mixed = d->KH == 3 && ((d->pad | d->dil) & 3) != 0;
     // same-box A/B against the register-staged kernel: +17 % where every tap keeps quads aligned (1x1,
     // dilation 4/8/12/...); +7 % for dilation 1/2 (16-byte copies from the 4/8-byte aligned shifted source,
     // dword copies only on the K-steps whose quads straddle the image border; -1 % with dword copies throughout)
-    return on && cfg == 0 && d->stride == 1 && d->Hout == d->H && d->Wout == d->W && d->W % 16 == 0 &&
-           (!mixed || mixed_too);
+    return cfg == 0 && dma_geometry(d) && (!mixed || mixed_too);
 }
 static bool wgrad_dma_mixed(const DcfpConvDesc* d) { return d->KH == 3 && ((d->pad | d->dil) & 3) != 0; }
 
@@ -914,8 +877,7 @@ template <int TAPS, bool MIXED, bool WIDE = false, bool BATCH = false, bool HALF
 int launch_dma(const WgradParams& p, long long blocks, hipStream_t stream) {
     const size_t lds = (size_t)2 * (HALF ? 384 : 512) * BK * sizeof(float);
     hipLaunchKernelGGL((wgrad_dma_kernel<TAPS, MIXED, WIDE, BATCH, HALF>), dim3((unsigned)blocks), dim3(256), lds, stream, p);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? DCFP_OK : (int)e;
+    DCFP_RETURN_LAUNCH();
 }
 
 template <int TAPS>
@@ -934,12 +896,29 @@ int launch_taps(const WgradParams& p, const Plan& pl, hipStream_t stream) {
 
 }  // namespace
 
-bool dcfp_gemv_shape(const DcfpConvDesc* d);     // conv_gemv.hip
-bool dcfp_stem_shape(const DcfpConvDesc* d);     // conv_stem.hip
-size_t dcfp_stem_wgrad_workspace_bytes(const DcfpConvDesc* d);
-int dcfp_stem_wgrad(const DcfpConvDesc* d, const float* dy, long long dy_nstride, const float* x, float* dw, void* workspace,
-                    size_t workspace_bytes, hipStream_t stream);
-int dcfp_gemv_wgrad(const DcfpConvDesc* d, const float* dy, long long dy_nstride, const float* x, float* dw, hipStream_t stream);
+// The split-K slabs [splits][wn] summed into `out` in a fixed order
+static void launch_splitk_reduce(const float* slabs, float* out, long long wn, int splits, hipStream_t stream) {
+    if (wn % 4 == 0 && dcfp_aligned16(slabs) && dcfp_aligned16(out)) {
+        const long long n4 = wn / 4;
+        hipLaunchKernelGGL(splitk_reduce_vec4_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, slabs, out, n4, wn,
+                           splits);
+    } else {
+        long long b = (wn + 255) / 256;
+        if (b > 4096) b = 4096;
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)b), dim3(256), 0, stream, slabs, out, wn, splits);
+    }
+}
+
+// Row pitches and image strides of the two operands as a call reads them (dy_nstride: the caller's, 0 = dense)
+struct WgradOperands { int xp, dyp; long long xn, dyn; };
+static WgradOperands wgrad_operands(const DcfpConvDesc* d, long long dy_nstride) {
+    WgradOperands o;
+    o.xp = d->x_pitch ? d->x_pitch : d->W;
+    o.dyp = d->dy_pitch ? d->dy_pitch : d->Wout;
+    o.xn = (long long)d->Cin * d->H * o.xp;
+    o.dyn = dy_nstride ? dy_nstride : (long long)d->Cout * d->Hout * o.dyp;
+    return o;
+}
 
 // pitched operands: the LDS-DMA kernels and the register-staged wgrad2_kernel (not the bf16x3 split kernel), 3x3 with
 // pad = dil and a tail that covers the column shifts
@@ -947,7 +926,7 @@ bool dcfp_wgrad_pitch_ok(const DcfpConvDesc* d) {
     if (check_desc(d) != DCFP_OK) return false;
     const Plan pl = make_plan(d);
     if (wgrad3_ok(d, pl.cfg)) return false;
-    const int xp = d->x_pitch ? d->x_pitch : d->W;
+    const int xp = wgrad_operands(d, 0).xp;
     if (xp != d->W && (d->KH != 3 || d->pad != d->dil || xp < d->W + d->pad)) return false;
     // 31-bit byte offsets relative to the first image of a split: checked in the launcher with the pitched strides
     return true;
@@ -1005,19 +984,7 @@ int dcfp_wgrad_batched_run(const float* a, const float* bmat, float* out, int ba
     int rc = (M % 256 != 0 && 10 * live <= 9 * mp) ? launch_dma<1, false, true, true>(p, blocks, stream)
                                                    : launch_dma<1, false, false, true>(p, blocks, stream);
     if (rc) return rc;
-    if (splits > 1) {
-        const long long wn = (long long)batch * M * C;
-        if (wn % 4 == 0 && dcfp_aligned16(out)) {
-            const long long n4 = wn / 4;
-            hipLaunchKernelGGL(splitk_reduce_vec4_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream,
-                               static_cast<const float*>(workspace), out, n4, wn, splits);
-        } else {
-            long long b = (wn + 255) / 256;
-            if (b > 4096) b = 4096;
-            hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)b), dim3(256), 0, stream,
-                               static_cast<const float*>(workspace), out, wn, splits);
-        }
-    }
+    if (splits > 1) launch_splitk_reduce(static_cast<const float*>(workspace), out, (long long)batch * M * C, splits, stream);
     DCFP_RETURN_LAUNCH();
 }
 
@@ -1040,33 +1007,13 @@ int dcfp_wgrad_kernel_name(const DcfpConvDesc* d, char* buf, int buf_len) {
     return snprintf(buf, buf_len, "wgrad2_kernel<%d,%s>", d->KH * d->KW, args);
 }
 
-// conv_winograd.hip
-bool dcfp_wino_wgrad_ok(int N, int H, int W, int d, int M, int C);
-size_t dcfp_wino_wgrad_workspace_bytes(int N, int H, int W, int d, int M, int C);
-double dcfp_wino_exec_fraction(int N, int H, int W, int d, int M, int Ck);
-int dcfp_wino_wgrad_run(const float* dy, long long dy_nstride, int dy_pitch, const float* x, long long x_nstride,
-                        int x_pitch, float* dw, int N, int M, int C, int H, int W, int d, void* workspace,
-                        size_t workspace_bytes, hipStream_t stream, const float* xform_in = nullptr);
-extern "C" size_t dcfp_conv2d_xform_bytes(const DcfpConvDesc* d);
-
 // executed-MFMA rate the cost model prices the fused Winograd weight gradient at (DCFP_WINO_WGRAD_RATE, TF: A/B), and
 // DCFP_WINO_WGRAD_FUSED=2: take it wherever it applies and beats the direct kernel, whatever the batched path's model says
 static double wino_wgrad_fused_rate() {
     static const double v = [] { const char* e = getenv("DCFP_WINO_WGRAD_RATE"); return (e ? atof(e) : 118.0) * 1e12; }();
     return v;
 }
-static bool wino_wgrad_fused_forced() {
-    static const bool v = [] { const char* e = getenv("DCFP_WINO_WGRAD_FUSED"); return e && atoi(e) == 2; }();
-    return v;
-}
-
-// conv_winograd3.hip: the fused weight-gradient kernel (both operands transformed inside the GEMM, no kept V)
-bool dcfp_wino_wgrad_fused_ok(int N, int H, int W, int d, int M, int C, long long x_nstride, int x_pitch,
-                              long long dy_nstride, int dy_pitch);
-size_t dcfp_wino_wgrad_fused_workspace_bytes(int N, int H, int W, int d, int M, int C);
-int dcfp_wino_wgrad_fused_run(const float* dy, long long dy_nstride, int dy_pitch, const float* x, long long x_nstride,
-                              int x_pitch, float* dw, int N, int M, int C, int H, int W, int d, void* workspace,
-                              size_t workspace_bytes, hipStream_t stream);
+static bool wino_wgrad_fused_forced() { return wino_wgrad_fused_mode() == 2; }
 
 // Winograd F(2x2, 3x3) weight gradient where the cost model (same-box measurements, profiles/r02_winograd_ab.txt,
 // profiles/r04_wino_wgrad_fused_ab.txt) says it beats the direct LDS-DMA kernel: direct = nominal FLOPs at 130 TF (123 on
@@ -1074,17 +1021,17 @@ int dcfp_wino_wgrad_fused_run(const float* dy, long long dy_nstride, int dy_pitc
 // passes at 4.2 / 5 TB/s; fused Winograd (kind 2, conv_winograd3.hip) = the same products on 64 x 64-channel blocks at the
 // rate of its K loop, no passes - the only Winograd weight gradient below 128 channels (stem, layer1, layer2, pruned widths).
 // Returns 0 (direct kernels), 1 or 2.  DCFP_CONV_WINOGRAD: 0 off, 1 model (default), 2 wherever eligible.
+static double wino_fraction(const DcfpConvDesc* d) {      // (the forward's tiling: M = Cout, Ck = Cin)
+    return dcfp_wino_exec_fraction(wino_problem(gemm_problem(d, DCFP_CONV_FWD, 0)));
+}
 static int wino_wgrad_kind(const DcfpConvDesc* d) {
-    static const int mode = [] { const char* e = getenv("DCFP_CONV_WINOGRAD"); return e ? atoi(e) : 1; }();
-    if (mode == 0) return 0;
-    if (d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad != d->dil || d->Hout != d->H || d->Wout != d->W) return 0;
-    if (math_bf16x3()) return 0;
-    const int xp = d->x_pitch ? d->x_pitch : d->W, dyp = d->dy_pitch ? d->dy_pitch : d->Wout;
+    const int mode = conv_winograd_mode();
+    if (mode == 0 || !same_size_3x3(d) || math_bf16x3()) return 0;
+    const WgradOperands o = wgrad_operands(d, 0);
     const bool batched = dcfp_wino_wgrad_ok(d->N, d->H, d->W, d->dil, d->Cout, d->Cin);
     // (a dy that is a channel slice of a wider tensor - the ASPP branches - has its own image stride: the entry point
     //  checks the real one again)
-    const bool fused = dcfp_wino_wgrad_fused_ok(d->N, d->H, d->W, d->dil, d->Cout, d->Cin, (long long)d->Cin * d->H * xp, xp,
-                                                (long long)d->Cout * d->Hout * dyp, dyp);
+    const bool fused = dcfp_wino_wgrad_fused_ok(d->N, d->H, d->W, d->dil, d->Cout, d->Cin, o.xn, o.xp, o.dyn, o.dyp);
     if (!batched && !fused) return 0;
     if (mode == 2) return fused ? 2 : 1;
     const double pix = (double)d->N * d->H * d->W;
@@ -1095,7 +1042,7 @@ static int wino_wgrad_kind(const DcfpConvDesc* d) {
                                : 1.0;     // (x 1.15: the 8 x 2 wave layout of the ragged-M kernel)
     // (below 128 output channels the direct path is the register-staged wgrad2_kernel: 82...110 TF measured)
     const double t_direct = nominal * dpad / (d->Cout < 128 ? 100e12 : dense_d1 ? 123e12 : 130e12);
-    const double f = dcfp_wino_exec_fraction(d->N, d->H, d->W, d->dil, d->Cout, d->Cin);
+    const double f = wino_fraction(d);
     double t_b = 1e30, t_f = 1e30;
     if (batched) {
         const double tiles = f * 9.0 / 16.0 * pix;
@@ -1118,10 +1065,8 @@ bool dcfp_wgrad_wants_xform(const DcfpConvDesc* d) { return wino_wgrad_kind(d) =
 
 // share of the nominal multiply-adds issued (the direct kernels execute every K-step: a tile of dW mixes all nine taps)
 double dcfp_wgrad_exec_fraction(const DcfpConvDesc* d) {
-    return wino_wgrad_pass(d) ? dcfp_wino_exec_fraction(d->N, d->H, d->W, d->dil, d->Cout, d->Cin) : 1.0;
+    return wino_wgrad_pass(d) ? wino_fraction(d) : 1.0;
 }
-
-size_t dcfp_conv2d_fwd_dgrad_workspace_bytes_(const DcfpConvDesc* d, int pass);
 
 extern "C" size_t dcfp_conv2d_workspace_bytes(const DcfpConvDesc* d, int pass) {
     if (pass == DCFP_CONV_FWD || pass == DCFP_CONV_DGRAD) return dcfp_conv2d_fwd_dgrad_workspace_bytes_(d, pass);
@@ -1158,26 +1103,22 @@ extern "C" int dcfp_conv2d_wgrad_f32_nchw(const DcfpConvDesc* d, const float* dy
     if (dcfp_stem_shape(d) && !db)      // Cin = 3, stride 2 (backbone.conv1.0): conv_stem.hip
         return dcfp_stem_wgrad(d, dy, dy_nstride, x, dw, workspace, workspace_bytes, dcfp_s(stream));
     int wk = wino_wgrad_kind(d);
-    if (wk == 2) {      // the descriptor-level decision assumed a dense batch stride for dy: check the real one
-        const int dyp = d->dy_pitch ? d->dy_pitch : d->Wout, xp = d->x_pitch ? d->x_pitch : d->W;
-        const long long dyn = dy_nstride ? dy_nstride : (long long)d->Cout * d->Hout * dyp;
-        if (!dcfp_wino_wgrad_fused_ok(d->N, d->H, d->W, d->dil, d->Cout, d->Cin, (long long)d->Cin * d->H * xp, xp, dyn, dyp))
-            wk = dcfp_wino_wgrad_ok(d->N, d->H, d->W, d->dil, d->Cout, d->Cin) ? 1 : 0;     // batched Winograd, or the direct kernels below
-    }
+    const WgradOperands o = wgrad_operands(d, dy_nstride);
+    // (the descriptor-level decision assumed a dense batch stride for dy: check the real one)
+    if (wk == 2 && !dcfp_wino_wgrad_fused_ok(d->N, d->H, d->W, d->dil, d->Cout, d->Cin, o.xn, o.xp, o.dyn, o.dyp))
+        wk = dcfp_wino_wgrad_ok(d->N, d->H, d->W, d->dil, d->Cout, d->Cin) ? 1 : 0;     // batched Winograd, or the direct kernels below
     if (wk) {
-        const int dyp = d->dy_pitch ? d->dy_pitch : d->Wout, xp = d->x_pitch ? d->x_pitch : d->W;
-        const long long dyn = dy_nstride ? dy_nstride : (long long)d->Cout * d->Hout * dyp;
-        if (db && dyp != d->Wout) return DCFP_E_UNSUPPORTED;      // (the bias-gradient kernel reads dense rows; nothing launched yet)
-        if (wk == 2) {
-            rc = dcfp_wino_wgrad_fused_run(dy, dyn, dyp, x, (long long)d->Cin * d->H * xp, xp, dw, d->N, d->Cout, d->Cin, d->H,
-                                           d->W, d->dil, workspace, workspace_bytes, dcfp_s(stream));
-        } else
-            rc = dcfp_wino_wgrad_run(dy, dyn, dyp, x, (long long)d->Cin * d->H * xp, xp, dw, d->N, d->Cout, d->Cin, d->H, d->W,
-                                     d->dil, workspace, workspace_bytes, dcfp_s(stream));
+        if (db && o.dyp != d->Wout) return DCFP_E_UNSUPPORTED;      // (the bias-gradient kernel reads dense rows; nothing launched yet)
+        if (wk == 2)
+            rc = dcfp_wino_wgrad_fused_run(dy, o.dyn, o.dyp, x, o.xn, o.xp, dw, d->N, d->Cout, d->Cin, d->H, d->W, d->dil,
+                                           workspace, workspace_bytes, dcfp_s(stream));
+        else
+            rc = dcfp_wino_wgrad_run(dy, o.dyn, o.dyp, x, o.xn, o.xp, dw, d->N, d->Cout, d->Cin, d->H, d->W, d->dil, workspace,
+                                     workspace_bytes, dcfp_s(stream), /*xform_in=*/nullptr);
         if (rc) return rc;
         if (db)
-            hipLaunchKernelGGL(bias_grad_kernel, dim3((unsigned)d->Cout), dim3(1024), 0, dcfp_s(stream), dy, dyn, db, d->N,
-                               d->Hout * d->Wout, (int)((d->Hout * d->Wout) % 4 == 0 && dyn % 4 == 0 && dcfp_aligned16(dy)));
+            hipLaunchKernelGGL(bias_grad_kernel, dim3((unsigned)d->Cout), dim3(1024), 0, dcfp_s(stream), dy, o.dyn, db, d->N,
+                               d->Hout * d->Wout, (int)((d->Hout * d->Wout) % 4 == 0 && o.dyn % 4 == 0 && dcfp_aligned16(dy)));
         DCFP_RETURN_LAUNCH();
     }
     const Plan pl = make_plan(d);
@@ -1188,13 +1129,11 @@ extern "C" int dcfp_conv2d_wgrad_f32_nchw(const DcfpConvDesc* d, const float* dy
     WgradParams p;
     p.dy = dy; p.x = x;
     p.out = pl.splits > 1 ? static_cast<float*>(workspace) : dw;
-    p.x_pitch = d->x_pitch ? d->x_pitch : d->W;
-    p.dy_pitch = d->dy_pitch ? d->dy_pitch : d->Wout;
+    p.x_pitch = o.xp; p.dy_pitch = o.dyp;
     const bool pitched = p.x_pitch != d->W || p.dy_pitch != d->Wout;
     if (pitched && !dcfp_wgrad_pitch_ok(d)) return DCFP_E_UNSUPPORTED;
     if (db && p.dy_pitch != d->Wout) return DCFP_E_UNSUPPORTED;   // (the bias-gradient kernel reads dense rows) - before anything is launched
-    p.dy_nstride = dy_nstride ? dy_nstride : (long long)d->Cout * d->Hout * p.dy_pitch;
-    p.x_nstride = (long long)d->Cin * d->H * p.x_pitch;
+    p.dy_nstride = o.dyn; p.x_nstride = o.xn;
     p.N = d->N; p.M = d->Cout; p.Cin = d->Cin; p.Nn = d->Cin * T;
     p.H = d->H; p.W = d->W; p.Ho = d->Hout; p.Wo = d->Wout; p.P = d->Hout * d->Wout;
     p.stride = d->stride; p.pad = d->pad; p.dil = d->dil;
@@ -1226,18 +1165,7 @@ extern "C" int dcfp_conv2d_wgrad_f32_nchw(const DcfpConvDesc* d, const float* dy
     } else
         rc = T == 1 ? launch_taps<1>(p, pl, dcfp_s(stream)) : launch_taps<9>(p, pl, dcfp_s(stream));
     if (rc) return rc;
-    if (pl.splits > 1) {
-        if (wn % 4 == 0 && dcfp_aligned16(workspace) && dcfp_aligned16(dw)) {
-            const long long n4 = wn / 4;
-            hipLaunchKernelGGL(splitk_reduce_vec4_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0,
-                               dcfp_s(stream), static_cast<const float*>(workspace), dw, n4, wn, pl.splits);
-        } else {
-            long long b = (wn + 255) / 256;
-            if (b > 4096) b = 4096;
-            hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)b), dim3(256), 0, dcfp_s(stream),
-                               static_cast<const float*>(workspace), dw, wn, pl.splits);
-        }
-    }
+    if (pl.splits > 1) launch_splitk_reduce(static_cast<const float*>(workspace), dw, wn, pl.splits, dcfp_s(stream));
     if (db) {
         hipLaunchKernelGGL(bias_grad_kernel, dim3((unsigned)d->Cout), dim3(1024), 0, dcfp_s(stream),
                            dy, p.dy_nstride, db, d->N, p.P,
@@ -1257,8 +1185,7 @@ extern "C" int dcfp_conv2d_wgrad_kept_f32_nchw(const DcfpConvDesc* d, const floa
     const size_t need = dcfp_conv2d_xform_bytes(d);
     if (need == 0) return DCFP_E_UNSUPPORTED;
     if (xform_bytes < need || !dcfp_aligned16(xform)) return DCFP_E_WORKSPACE;
-    const int dyp = d->dy_pitch ? d->dy_pitch : d->Wout;
-    const long long dyn = dy_nstride ? dy_nstride : (long long)d->Cout * d->Hout * dyp;
-    return dcfp_wino_wgrad_run(dy, dyn, dyp, nullptr, 0, 0, dw, d->N, d->Cout, d->Cin, d->H, d->W, d->dil, workspace,
+    const WgradOperands o = wgrad_operands(d, dy_nstride);
+    return dcfp_wino_wgrad_run(dy, o.dyn, o.dyp, /*x=*/nullptr, 0, 0, dw, d->N, d->Cout, d->Cin, d->H, d->W, d->dil, workspace,
                                workspace_bytes, dcfp_s(stream), xform);
 }

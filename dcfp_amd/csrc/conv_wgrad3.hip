@@ -15,6 +15,7 @@
 // Diagnosis builds: -DW3_DBG_NOLOAD (global loads fetch nothing), -DW3_DBG_NOSTAGE (no split /
 // LDS store / reload at all) - the same instruction stream minus one cost.
 #include "common.h"
+#include "conv_dispatch.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <type_traits>

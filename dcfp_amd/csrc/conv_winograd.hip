@@ -17,26 +17,7 @@
 // with dilation d restricted to the residue class (a, b) mod d is an undilated conv.  Tile column index
 // tcol = j * d + b, so that consecutive tiles read / write consecutive pixels (runs of d).
 #include "igemm2_common.h"
-
-int dcfp_igemm2_run(const float* in, long long in_nstride, const float* w, int sAm, int sAc,
-                    const float* bias, float* out, long long out_nstride, int N, int M, int Ck, int T,
-                    int Hi, int Wi, int Ho, int Wo, int sn, int sd, int off0, int offstep,
-                    int accumulate, void* workspace, size_t workspace_bytes, hipStream_t stream,
-                    const float* scale, const float* shift, const float* residual, int relu, float* stat_part,
-                    int wp_valid, int in_pitch, long long wp_nstride, const float* fan_src = nullptr,
-                    const unsigned long long* fan_mask = nullptr, const Igemm2Red* red = nullptr);
-bool dcfp_igemm2_dma_shape(int T, int M, int Ck, int P, long long px, int sn, int sd, int off0, int HiWi, int Wo);
-bool dcfp_igemm2_use_dma8(int T, int M, int P, long long px, int sn, int sd, int off0, int offstep, int HiWi,
-                          int Wo, bool pitched);
-bool dcfp_igemm2_persist();
-int dcfp_igemm2_ck_pad();
-// conv_winograd2.hip: the fused kernel (transforms inside the GEMM)
-bool dcfp_wino_fused_ok(int N, int H, int W, int d, int M, int Ck, long long in_nstride, int pitch);
-size_t dcfp_wino_fused_workspace_bytes(int N, int H, int W, int d, int M, int Ck);
-int dcfp_wino_fused_run(const float* in, long long in_nstride, int in_pitch, const float* w, int sAm, int sAc, int flip,
-                        float* out, long long out_nstride, int N, int M, int Ck, int H, int W, int d, int accumulate,
-                        void* workspace, size_t workspace_bytes, hipStream_t stream, float* xform_out, float* stat_part,
-                        const float* scale, const float* shift, const float* residual, int relu, int wp_valid);
+#include "conv_dispatch.h"
 
 namespace {
 
@@ -435,48 +416,66 @@ static int wino_vec(int d, int W, int pitch, const float* base, long long nstrid
     return 1;
 }
 
-// 3x3, stride 1, pad == dil, same-size output; M = output channels of the pass, Ck = reduced channels
-bool dcfp_wino_ok(int N, int H, int W, int d, int M, int Ck) {
-    if (!dcfp_igemm2_persist()) return false;
-    if (M < 129 || Ck < 128) return false;     // the transforms cost ~ 1/M + 1/Ck of the GEMM (the cost model decides)
-    const WinoPlan pl = wino_plan(N, H, W, d, M, Ck);
-    if (4 * pl.T > (long long)N * H * W * 27 / 20) return false;  // > 35 % padding of the 2d x 2d super-blocks
-    if (pl.T16 >= (1LL << 26) || 16LL * pl.T16 >= (1LL << 30)) return false;
-    if ((long long)Ck * pl.T16 >= (1LL << 29) || (long long)M * pl.T16 >= (1LL << 29)) return false;
-    const int P = (int)pl.T16;
-    // (ragged M - pruned models - runs on the persistent kernel's edge tiles: the batched GEMM never takes the
-    //  ragged-M kernel, whose permuted weight layout has no per-image copies)
-    return dcfp_igemm2_dma_shape(1, M, Ck, P, 16LL * P, 1, 1, 0, P, P);
+static WinoPlan wino_plan(const WinoProblem& q) { return wino_plan(q.N, q.H, q.W, q.d, q.M, q.Ck); }
+
+// The batched GEMM of the three-pass path, M[xi] = U[xi] * V[xi]: 16 "images" of one row of T16 pixels, each with its
+// own weights (GemmExtras::wp_nstride) - the one problem view that is written out by hand
+static GemmProblem batched_gemm(const WinoPlan& pl, int M, int Ck) {
+    GemmProblem g = {};
+    g.T = 1; g.M = M; g.Ck = Ck; g.N = 16;
+    g.Hi = g.Ho = 1; g.Wi = g.Wo = (int)pl.T16;
+    g.sn = g.sd = 1; g.off0 = 0; g.offstep = 1;
+    g.in_nstride = (long long)Ck * pl.T16; g.out_nstride = (long long)M * pl.T16;
+    return g;
 }
 
-size_t dcfp_wino_workspace_bytes(int N, int H, int W, int d, int M, int Ck) {
-    const WinoPlan pl = wino_plan(N, H, W, d, M, Ck);
+// 3x3, stride 1, pad == dil, same-size output; M = output channels of the pass, Ck = reduced channels
+bool dcfp_wino_ok(const WinoProblem& q) {
+    if (!dcfp_igemm2_persist()) return false;
+    if (q.M < 129 || q.Ck < 128) return false;     // the transforms cost ~ 1/M + 1/Ck of the GEMM (the cost model decides)
+    const WinoPlan pl = wino_plan(q);
+    if (4 * pl.T > (long long)q.N * q.H * q.W * 27 / 20) return false;  // > 35 % padding of the 2d x 2d super-blocks
+    if (pl.T16 >= (1LL << 26) || 16LL * pl.T16 >= (1LL << 30)) return false;
+    if ((long long)q.Ck * pl.T16 >= (1LL << 29) || (long long)q.M * pl.T16 >= (1LL << 29)) return false;
+    // (ragged M - pruned models - runs on the persistent kernel's edge tiles: the batched GEMM never takes the
+    //  ragged-M kernel, whose permuted weight layout has no per-image copies)
+    return dcfp_igemm2_dma_shape(batched_gemm(pl, q.M, q.Ck));
+}
+
+size_t dcfp_wino_workspace_bytes(const WinoProblem& q) {
+    const WinoPlan pl = wino_plan(q);
     return (size_t)(pl.u_floats + pl.v_floats + pl.m_floats) * sizeof(float);
 }
 
 // share of the nominal multiply-adds (2*N*M*H*W*Ck*9) that the batched GEMM issues
-double dcfp_wino_exec_fraction(int N, int H, int W, int d, int M, int Ck) {
-    const WinoPlan pl = wino_plan(N, H, W, d, M, Ck);
-    return 16.0 * (double)pl.T / (9.0 * (double)N * H * W);
+double dcfp_wino_exec_fraction(const WinoProblem& q) {
+    const WinoPlan pl = wino_plan(q);
+    return 16.0 * (double)pl.T / (9.0 * (double)q.N * q.H * q.W);
 }
 
-// in: x (forward) or dy (dgrad), rows at `in_pitch` floats; w with strides (sAm, sAc) as dcfp_igemm2_run takes them
 // Partials (of 128 outputs each) per channel that the output transform can emit for the BatchNorm behind the conv; 0 where
 // some tile is not wholly inside the image
-long long dcfp_wino_stat_slots(int N, int H, int W, int d) {
+long long dcfp_wino_stat_slots(const WinoProblem& q) {
+    const int H = q.H, W = q.W, d = q.d;
     if (H % (2 * d) != 0 || W % (2 * d) != 0 || (W / 2) % 4 != 0) return 0;
     const long long tpi = (long long)(H / 2) * (W / 2);
     if (tpi % 32 != 0) return 0;
-    return (long long)N * tpi / 32;
+    return (long long)q.N * tpi / 32;
 }
 
-// xform_out (nullable): 16 * Ck * T16 floats of the caller's that receive the transformed input V instead of the scratch
+// g: a same-size 3x3 problem (gemm_problem of a forward or dgrad pass); in: x or dy, w: the conv's weights.
+// x.xform_out (nullable): 16 * Ck * T16 floats of the caller's that receive the transformed input V instead of the scratch
 // (the weight gradient of the same conv can take it over: dcfp_wino_wgrad_run's xform_in)
-int dcfp_wino_run(const float* in, long long in_nstride, int in_pitch, const float* w, int sAm, int sAc, int flip,
-                  float* out, long long out_nstride, int N, int M, int Ck, int H, int W, int d, int accumulate,
-                  void* workspace, size_t workspace_bytes, hipStream_t stream, float* xform_out, float* stat_part,
-                  const float* scale, const float* shift, const float* residual, int relu, int wp_valid) {
-    const WinoPlan pl = wino_plan(N, H, W, d, M, Ck);
+int dcfp_wino_run(const GemmProblem& g, const float* in, const float* w, float* out, void* workspace, size_t workspace_bytes,
+                  const GemmExtras& x, hipStream_t stream) {
+    const WinoProblem q = wino_problem(g);
+    const int N = q.N, M = q.M, Ck = q.Ck, H = q.H, W = q.W, d = q.d, in_pitch = q.in_pitch;
+    const int flip = g.offstep < 0;          // dgrad: the taps rotated by 180 degrees
+    const long long in_nstride = g.in_nstride, out_nstride = g.out_nstride;
+    float* const xform_out = x.xform_out;
+    float* const stat_part = x.stat_part;
+    const int accumulate = x.accumulate;
+    const WinoPlan pl = wino_plan(q);
     if (!workspace || !dcfp_aligned16(workspace)) return DCFP_E_WORKSPACE;
     // The fused kernel (conv_winograd2.hip) where it measures faster than the three passes (same-box A/B,
     // profiles/r03_wino_fused_ab.txt, profiles/r04_wino_fused_burst_ab.txt): everywhere except a forward that must leave V
@@ -486,18 +485,14 @@ int dcfp_wino_run(const float* in, long long in_nstride, int in_pitch, const flo
     // K loop got faster in round 4.)  Where the three passes do not apply at all (fewer than 129 / 128 channels: the narrow
     // layers of the stem, layer1, layer2 and of pruned models) the fused kernel is the Winograd path.
     // DCFP_WINO_FUSED=2 takes it wherever it applies (tests).
-    static const int fused_mode = [] { const char* e = getenv("DCFP_WINO_FUSED"); return e ? atoi(e) : 1; }();
-    const bool three_ok = dcfp_wino_ok(N, H, W, d, M, Ck);
-    const bool fused_wins = fused_mode == 2 || !three_ok || !(xform_out && Ck > 256);
-    if (fused_wins && dcfp_wino_fused_ok(N, H, W, d, M, Ck, in_nstride, in_pitch) &&
-        workspace_bytes >= dcfp_wino_fused_workspace_bytes(N, H, W, d, M, Ck)) {
-        if (stat_part && (!dcfp_wino_stat_slots(N, H, W, d) || accumulate)) return DCFP_E_UNSUPPORTED;
-        return dcfp_wino_fused_run(in, in_nstride, in_pitch, w, sAm, sAc, flip, out, out_nstride, N, M, Ck, H, W, d,
-                                   accumulate, workspace, workspace_bytes, stream, xform_out, stat_part, scale, shift,
-                                   residual, relu, wp_valid);
+    const bool three_ok = dcfp_wino_ok(q);
+    const bool fused_wins = wino_fused_mode() == 2 || !three_ok || !(xform_out && Ck > 256);
+    if (fused_wins && dcfp_wino_fused_ok(q) && workspace_bytes >= dcfp_wino_fused_workspace_bytes(q)) {
+        if (stat_part && (!dcfp_wino_stat_slots(q) || accumulate)) return DCFP_E_UNSUPPORTED;
+        return dcfp_wino_fused_run(g, in, w, out, workspace, workspace_bytes, x, stream);
     }
     if (!three_ok) return DCFP_E_UNSUPPORTED;
-    if (workspace_bytes < dcfp_wino_workspace_bytes(N, H, W, d, M, Ck)) return DCFP_E_WORKSPACE;
+    if (workspace_bytes < dcfp_wino_workspace_bytes(q)) return DCFP_E_WORKSPACE;
     float* U = static_cast<float*>(workspace);
     float* V = xform_out ? xform_out : U + pl.u_floats;
     float* Mb = U + pl.u_floats + pl.v_floats;
@@ -505,7 +500,7 @@ int dcfp_wino_run(const float* in, long long in_nstride, int in_pitch, const flo
     {
         long long b = ((long long)pl.CkP * pl.Mpad + 255) / 256;
         if (b > 4096) b = 4096;
-        hipLaunchKernelGGL(wino_filter_kernel, dim3((unsigned)b), dim3(256), 0, stream, w, sAm, sAc, flip, M, Ck,
+        hipLaunchKernelGGL(wino_filter_kernel, dim3((unsigned)b), dim3(256), 0, stream, w, g.sAm, g.sAc, flip, M, Ck,
                            pl.CkP, pl.Mpad, U);
     }
     const int tpi = pl.TH * pl.TW;
@@ -516,17 +511,17 @@ int dcfp_wino_run(const float* in, long long in_nstride, int in_pitch, const flo
                                               in_nstride, in_pitch > 0 ? in_pitch : W, N, Ck, H, W, d, pl.TH, pl.TW, V, pl.T16)
     if (vec == 4) DCFP_WINO_IN(4); else if (vec == 2) DCFP_WINO_IN(2); else DCFP_WINO_IN(1);
 #undef DCFP_WINO_IN
-    const int rc = dcfp_igemm2_run(V, (long long)Ck * pl.T16, nullptr, 0, 0, nullptr, Mb, (long long)M * pl.T16, 16, M, Ck, 1,
-                                   1, (int)pl.T16, 1, (int)pl.T16, 1, 1, 0, 1, 0, U,
-                                   (size_t)pl.u_floats * sizeof(float), stream, nullptr, nullptr, nullptr, 0, nullptr,
-                                   /*wp_valid=*/1, 0, (long long)pl.CkP * pl.Mpad);
+    GemmExtras gx;
+    gx.wp_valid = 1;                                  // U is the weight operand as the kernel reads it
+    gx.wp_nstride = (long long)pl.CkP * pl.Mpad;
+    const int rc = dcfp_igemm2_run(batched_gemm(pl, M, Ck), V, /*w=*/nullptr, Mb, U, (size_t)pl.u_floats * sizeof(float), gx, stream);
     if (rc) return rc;
     const int ovec = wino_vec(d, W, W, out, out_nstride, pl.TW);
     const unsigned gout = (unsigned)((tpi / ovec + 255) / 256);
 #define DCFP_WINO_OUT(VEC_, ST_) hipLaunchKernelGGL((wino_output_kernel<VEC_, ST_>), dim3(gout, (unsigned)N, (unsigned)M), dim3(256), 0, \
-                                               stream, Mb, pl.T16, M, out, out_nstride, H, W, d, pl.TH, pl.TW, accumulate, stat_part, scale, shift, residual, relu)
+                                               stream, Mb, pl.T16, M, out, out_nstride, H, W, d, pl.TH, pl.TW, accumulate, stat_part, x.scale, x.shift, x.residual, x.relu)
     if (stat_part) {
-        if (!dcfp_wino_stat_slots(N, H, W, d) || accumulate) return DCFP_E_UNSUPPORTED;
+        if (!dcfp_wino_stat_slots(q) || accumulate) return DCFP_E_UNSUPPORTED;
         if (ovec == 4) DCFP_WINO_OUT(4, true); else if (ovec == 2) DCFP_WINO_OUT(2, true); else DCFP_WINO_OUT(1, true);
     } else if (ovec == 4) DCFP_WINO_OUT(4, false); else if (ovec == 2) DCFP_WINO_OUT(2, false); else DCFP_WINO_OUT(1, false);
 #undef DCFP_WINO_OUT
@@ -538,9 +533,6 @@ int dcfp_wino_run(const float* in, long long in_nstride, int in_pitch, const flo
 // 16 products over the tiles instead of 36 over the pixels: the x transform of the forward pass, a 2x2 -> 4x4 transform
 // of dy, ONE launch of the LDS-DMA 1x1 weight-gradient kernel over 16 independent problems (conv_wgrad.hip), and a
 // 16 -> 9 transform of the result.
-size_t dcfp_wgrad_batched_workspace_bytes(int batch, int M, int C, long long K, int* splits_out);
-int dcfp_wgrad_batched_run(const float* a, const float* bmat, float* out, int batch, int M, int C, long long K,
-                           void* workspace, size_t workspace_bytes, hipStream_t stream);
 
 namespace {
 struct WinoWgradPlan { WinoPlan pl; long long T16, v, y, du, slabs; };
@@ -601,7 +593,6 @@ int dcfp_wino_wgrad_run(const float* dy, long long dy_nstride, int dy_pitch, con
 }
 
 // bytes of the transformed input V (16 x C x T16 floats) that a forward call can leave behind for the weight gradient
-size_t dcfp_wino_xform_bytes(int N, int H, int W, int d, int C) {
-    const WinoPlan pl = wino_plan(N, H, W, d, 256, C);
-    return (size_t)16 * C * pl.T16 * sizeof(float);
+size_t dcfp_wino_xform_bytes(const WinoProblem& q) {
+    return (size_t)16 * q.Ck * wino_plan(q).T16 * sizeof(float);
 }

@@ -24,6 +24,7 @@
 // Tile numbering, super-blocks for dilation d, and the transforms' arithmetic (operation order included) are those of
 // conv_winograd.hip: V written on the side is bit-identical to wino_input_kernel's.
 #include "wino_patch.h"
+#include "conv_dispatch.h"
 #include <stdlib.h>
 
 namespace {
@@ -515,16 +516,10 @@ FusedPlan fused_plan(int N, int H, int W, int d, int M, int Ck) {
 
 }  // namespace
 
-// DCFP_WINO_FUSED: 0 off (the three-pass path of conv_winograd.hip), 1 on (default)
-bool dcfp_wino_fused_enabled() {
-    static const int v = [] { const char* e = getenv("DCFP_WINO_FUSED"); return e ? atoi(e) : 1; }();
-    return v != 0;
-}
-
 // patch-load mode for this input, or -1 where the kernel does not apply
-static int fused_mode(int N, int H, int W, int d, int Ck, long long in_nstride, int pitch) {
-    if (pitch <= 0) pitch = W;
-    const long long span = (long long)(N - 1) * in_nstride + (long long)((Ck + 15) / 16 * 16) * H * pitch + 64;
+static int fused_mode(const WinoProblem& q) {
+    const int pitch = q.in_pitch > 0 ? q.in_pitch : q.W, d = q.d, W = q.W;
+    const long long span = (long long)(q.N - 1) * q.in_nstride + (long long)((q.Ck + 15) / 16 * 16) * q.H * pitch + 64;
     if (span * 4 >= 0x7fffff00LL) return -1;                 // 32-bit byte offsets with bit 31 as the out-of-range mark
     if (d == 1 && pitch >= W + 4) return 1;
     if (d == 2 && pitch >= W + 4) return 2;
@@ -532,40 +527,45 @@ static int fused_mode(int N, int H, int W, int d, int Ck, long long in_nstride, 
     return -1;
 }
 
-bool dcfp_wino_fused_ok(int N, int H, int W, int d, int M, int Ck, long long in_nstride, int pitch) {
-    if (!dcfp_wino_fused_enabled()) return false;
-    if (M < 48 || Ck < 48) return false;       // (the cost model of conv_igemm.hip decides above that)
-    const FusedPlan pl = fused_plan(N, H, W, d, M, Ck);
+bool dcfp_wino_fused_ok(const WinoProblem& q) {
+    if (wino_fused_mode() == 0) return false;
+    if (q.M < 48 || q.Ck < 48) return false;       // (the cost model of conv_igemm.hip decides above that)
+    const FusedPlan pl = fused_plan(q.N, q.H, q.W, q.d, q.M, q.Ck);
     if (pl.T16 >= (1LL << 30) || (long long)pl.tblocks * pl.mblocks + 8 * pl.mblocks >= (1LL << 31)) return false;
     if ((long long)pl.CkP * pl.Mpad * 16 * 4 >= 0x7fffff00LL) return false;
-    return fused_mode(N, H, W, d, Ck, in_nstride, pitch) >= 0;
+    return fused_mode(q) >= 0;
 }
 
 // padded channel counts of the transformed-filter image (for dcfp_conv2d_wp_layout)
-void dcfp_wino_fused_pads(int N, int H, int W, int d, int M, int Ck, int* CkP, int* Mpad) {
-    const FusedPlan pl = fused_plan(N, H, W, d, M, Ck);
+void dcfp_wino_fused_pads(const WinoProblem& q, int* CkP, int* Mpad) {
+    const FusedPlan pl = fused_plan(q.N, q.H, q.W, q.d, q.M, q.Ck);
     *CkP = pl.CkP; *Mpad = pl.Mpad;
 }
 
-size_t dcfp_wino_fused_workspace_bytes(int N, int H, int W, int d, int M, int Ck) {
-    return (size_t)fused_plan(N, H, W, d, M, Ck).ug_floats * sizeof(float);
+size_t dcfp_wino_fused_workspace_bytes(const WinoProblem& q) {
+    return (size_t)fused_plan(q.N, q.H, q.W, q.d, q.M, q.Ck).ug_floats * sizeof(float);
 }
 
-int dcfp_wino_fused_run(const float* in, long long in_nstride, int in_pitch, const float* w, int sAm, int sAc, int flip,
-                        float* out, long long out_nstride, int N, int M, int Ck, int H, int W, int d, int accumulate,
-                        void* workspace, size_t workspace_bytes, hipStream_t stream, float* xform_out, float* stat_part,
-                        const float* scale, const float* shift, const float* residual, int relu, int wp_valid) {
+// g: a same-size 3x3 problem (gemm_problem of a forward or dgrad pass); reads x.wp_valid, xform_out, stat_part, the
+// inference epilogue and accumulate
+int dcfp_wino_fused_run(const GemmProblem& g, const float* in, const float* w, float* out, void* workspace,
+                        size_t workspace_bytes, const GemmExtras& x, hipStream_t stream) {
+    const WinoProblem q = wino_problem(g);
+    const int N = q.N, M = q.M, Ck = q.Ck, H = q.H, W = q.W, d = q.d;
+    const int flip = g.offstep < 0;          // dgrad: the taps rotated by 180 degrees
+    const long long in_nstride = g.in_nstride, out_nstride = g.out_nstride;
+    float* const xform_out = x.xform_out;
     const FusedPlan pl = fused_plan(N, H, W, d, M, Ck);
     if (!workspace || !dcfp_aligned16(workspace) || workspace_bytes < (size_t)pl.ug_floats * sizeof(float))
         return DCFP_E_WORKSPACE;
-    const int pitch = in_pitch > 0 ? in_pitch : W;
-    const int mode = fused_mode(N, H, W, d, Ck, in_nstride, pitch);
+    const int pitch = q.in_pitch > 0 ? q.in_pitch : W;
+    const int mode = fused_mode(q);
     if (mode < 0) return DCFP_E_UNSUPPORTED;
     float* Ug = static_cast<float*>(workspace);
-    if (!wp_valid) {      // (valid: the caller kept U from an earlier call / the multi-tensor refresh and the weights are unchanged)
+    if (!x.wp_valid) {      // (valid: the caller kept U from an earlier call / the multi-tensor refresh and the weights are unchanged)
         long long b = ((long long)pl.CkP * pl.Mpad + 255) / 256;
         if (b > 4096) b = 4096;
-        hipLaunchKernelGGL(wino_filter2_kernel, dim3((unsigned)b), dim3(256), 0, stream, w, sAm, sAc, flip, M, Ck, pl.CkP,
+        hipLaunchKernelGGL(wino_filter2_kernel, dim3((unsigned)b), dim3(256), 0, stream, w, g.sAm, g.sAc, flip, M, Ck, pl.CkP,
                            pl.Mpad, Ug);
     }
     WinoFusedParams p;
@@ -579,12 +579,12 @@ int dcfp_wino_fused_run(const float* in, long long in_nstride, int in_pitch, con
     p.out = out;
     p.out_nstride = out_nstride;
     p.xform_out = xform_out;
-    p.stat_part = stat_part;
-    p.scale = scale; p.shift = shift; p.residual = residual; p.relu = relu;
+    p.stat_part = x.stat_part;
+    p.scale = x.scale; p.shift = x.shift; p.residual = x.residual; p.relu = x.relu;
     p.N = N; p.M = M; p.Ck = Ck; p.H = H; p.W = W; p.d = d; p.TH = pl.TH; p.TW = pl.TW;
     p.T = pl.T; p.T16 = pl.T16;
     p.mblocks = pl.mblocks; p.tblocks = pl.tblocks; p.nk = pl.nk;
-    p.accumulate = accumulate;
+    p.accumulate = x.accumulate;
     p.ragged_c = (Ck % 16) != 0;
     {
         const long long ospan = ((long long)(N - 1) * out_nstride + (long long)M * H * W) * 4;

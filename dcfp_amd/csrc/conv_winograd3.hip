@@ -23,6 +23,7 @@
 // No instruction in the loop is inline-asm memory traffic, so the compiler's own vmcnt bookkeeping is exact: a step ends
 // in `s_waitcnt lgkmcnt(0)` + barrier and the patch loads issued three K-steps ahead are waited for where they are used.
 #include "wino_patch.h"
+#include "conv_dispatch.h"
 #include <stdlib.h>
 
 namespace {
@@ -470,15 +471,9 @@ WgPlan wg_plan(int N, int H, int W, int d, int M, int C) {
 
 }  // namespace
 
-// DCFP_WINO_WGRAD_FUSED: 0 off (the batched path of conv_winograd.hip with the kept transform), 1 on (default)
-bool dcfp_wino_wgrad_fused_enabled() {
-    static const int v = [] { const char* e = getenv("DCFP_WINO_WGRAD_FUSED"); return e ? atoi(e) : 1; }();
-    return v != 0;
-}
-
 bool dcfp_wino_wgrad_fused_ok(int N, int H, int W, int d, int M, int C, long long x_nstride, int x_pitch,
                               long long dy_nstride, int dy_pitch) {
-    if (!dcfp_wino_wgrad_fused_enabled()) return false;
+    if (wino_wgrad_fused_mode() == 0) return false;
     if (M < 48 || C < 48) return false;        // (the cost model of conv_wgrad.hip decides above that)
     if (x_pitch <= 0) x_pitch = W;
     if (dy_pitch <= 0) dy_pitch = W;
