@@ -118,6 +118,12 @@ class SlidePass(C.Structure):
                [("weight", C.c_float)]
 
 
+class EngineInfo(C.Structure):
+    """dcfp_engine_info_t: what a flat engine file says about itself."""
+    _fields_ = [(n, C.c_int32) for n in ("format", "num_classes", "in_channels", "align_corner", "model", "n_records",
+                                         "n_buffers", "n_slots", "has_input_table")]
+
+
 SLIDE_MAX_PASSES, SLIDE_MAX_TILES_PER_AXIS = 16, 32    # DCFP_SLIDE_MAX_* of include/dcfp_hip.h
 AUG_SATURATION, AUG_HUE = 1, 2
 SGD_CHUNK = 16384
@@ -256,6 +262,18 @@ SIGNATURES = {
     "dcfp_filter_reduce_f32": (_I, [_P, _I, _L, _I, _P]),
     "dcfp_fpgm_workspace_bytes": (_Z, [_I]),
     "dcfp_fpgm_f32": (_I, [_P, _I, _L, _P, _Z, _P]),
+    "dcfp_engine_open": (_I, [C.c_char_p, C.POINTER(_P), C.c_char_p, _Z]),
+    "dcfp_engine_open_memory": (_I, [_P, _Z, C.POINTER(_P), C.c_char_p, _Z]),
+    "dcfp_engine_close": (None, [_P]),
+    "dcfp_engine_info": (_I, [_P, C.POINTER(EngineInfo)]),
+    "dcfp_engine_weight_bytes": (_Z, [_P]),
+    "dcfp_engine_upload": (_I, [_P, _P, _P]),
+    "dcfp_engine_output_shape": (_I, [_P, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
+    "dcfp_engine_buffer_shapes": (_I, [_P, _I, _I, C.POINTER(_I), _I]),
+    "dcfp_engine_workspace_bytes": (_Z, [_P, _I, _I, _I]),
+    "dcfp_engine_run_f32": (_I, [_P, _P, _P, _I, _I, _I, _P, _Z, _P, _P]),
+    "dcfp_engine_run_u8": (_I, [_P, _P, _P, _Z, _I, _I, _I, _P, _Z, _P, _P]),
+    "dcfp_image_u8_hwc_to_nhwc_f16": (_I, [_P, _Z, _I, _I, _I, _P, C.POINTER(_I), _P, _I, _P]),
 }
 
 

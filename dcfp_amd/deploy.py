@@ -28,8 +28,14 @@ record wrote - the calibration and the per-record tests are built on it.
 
 An Engine offers what evaluate.predict_whole / predict_sliding / predict_multiscale / predict_labels ask of a net:
 engine(image) -> [logits], engine.lowres_logits(image) -> [lowres], engine.align_corner.
+
+`save_flat(engine, path, mean, std)` writes an engine of either format as a flat engine file: what the
+library's C runtime (dcfp_engine_* of include/dcfp_hip.h, tools/engine_run.cpp) loads and runs without Python.
+`CEngine(path, device)` is that runtime behind the interface of an Engine - same kernels, same arguments, same bits -
+and `CEngine.run_u8` takes uint8 HWC frames, normalised on the device through `input_table(mean, std)`.
 """
 import ctypes as C
+import os
 
 import torch
 import torch.nn as nn
@@ -814,3 +820,242 @@ class Engine:
 
     def conv_records(self):
         return [r for r in self.plan if r["op"] == "conv"]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The flat engine file and the C runtime: an engine as a file a C program loads and runs
+# (include/dcfp_hip.h, dcfp_engine_*; csrc/engine_file.cpp parses it, csrc/engine_rt.hip runs it).
+
+FLAT_VERSION = 1
+FLAT_MAGIC = b"DCFPENG\0"
+FLAT_SECTIONS = ("meta", "records", "buffers", "tensors", "strings", "weights", "input")
+FLAT_HEADER_BYTES = 32 + 16 * len(FLAT_SECTIONS)
+FLAT_RECORD_INTS, FLAT_RECORD_BYTES = 32, 136       # 32 int32 fields, then the floats res_mul and scale
+FLAT_WEIGHT_ALIGN = 256
+_FLAT_OPS = {"conv": 1, "maxpool": 2, "avgpool": 3, "broadcast": 4, "cast": 5, "resize": 6, "pyramid": 7}
+_FLAT_FMT = {"f16": 0, "f8": 1}
+_FLAT_DTYPE = {torch.float16: 0, torch.float32: 1, F8: 2}
+_FLAT_MODELS = ("simple", "deeplabv3", "deeplabv3p", "psp")
+
+
+def input_table(mean, std):
+    """fp16 [3, 256]: table[c][v] = (v / 255 - mean[c]) / std[c], formed in fp64 and rounded once - what the uint8
+    input kernel looks a byte up in (dcfp_image_u8_hwc_to_nhwc_f16)."""
+    mean, std = torch.tensor(list(mean), dtype=torch.float64), torch.tensor(list(std), dtype=torch.float64)
+    if mean.numel() != 3 or std.numel() != 3:
+        raise ValueError("input_table: mean and std hold one value per colour channel")
+    v = torch.arange(256, dtype=torch.float64).view(1, 256)
+    return ((v / 255.0 - mean.view(3, 1)) / std.view(3, 1)).to(torch.float16)
+
+
+def _f32_bits(v):
+    """The 4 bytes of the float a ctypes call makes of a Python number."""
+    return bytes(C.c_float(float(v)))
+
+
+def _pad_to(b, align):
+    return b + b"\0" * (-len(b) % align)
+
+
+def flat_bytes(engine, mean=None, std=None, bgr=True):
+    """The flat engine file (version FLAT_VERSION, layout in DESIGN.md §11b) of `engine`, as bytes: only what
+    engine.state_dict() holds, plus - when mean / std are given - the uint8 input table and the channel order."""
+    import struct
+    state = engine.state_dict()
+    meta, plan, fmt8 = state["meta"], state["plan"], state["format"] == FORMAT_F8
+    if (mean is None) != (std is None):
+        raise ValueError("save_flat: give both mean and std, or neither")
+    names, name_off = b"", []
+    for r in plan:
+        name_off.append(len(names))
+        names += r["name"].encode() + b"\0"
+    records = b""
+    for r, noff in zip(plan, name_off):
+        f8 = r.get("fmt") == "f8"
+        sizes, dsts = list(r.get("sizes", ())), list(r.get("dsts", ()))
+        conv = r["op"] == "conv"
+        ints = [_FLAT_OPS[r["op"]], noff, _FLAT_FMT[r.get("fmt", "f16")], r["src"], r["dst"], r.get("res", -1),
+                r.get("k", 0), r.get("stride", 0), r.get("pad", 0), r.get("dil", 0), r.get("cin8", 0), r.get("cout", 0),
+                r.get("y_off", 0), r.get("x_off", 0), r.get("c", 0), r.get("c8", 0), int(r.get("relu", False)),
+                int(r.get("f32", False)), int(r.get("align", False)), len(sizes)]
+        ints += (sizes + [0] * 4)[:4] + (dsts + [-1] * 4)[:4]
+        ints += [r["w"], r["mul"] if f8 else r["shift"], r["add"] if f8 else -1] if conv else [-1, -1, -1]
+        ints += [0]
+        assert len(ints) == FLAT_RECORD_INTS and len(sizes) <= 4
+        records += struct.pack(f"<{FLAT_RECORD_INTS}i", *ints) + _f32_bits(r.get("res_mul", 0.0)) + \
+            _f32_bits(r.get("scale", 0.0))
+    fmts = state["buffer_fmt"] if fmt8 else ["f16"] * len(state["buffers"])
+    scales = state["scales"] if fmt8 else [1.0] * len(state["buffers"])
+    buffers = b"".join(struct.pack("<ii", p, _FLAT_FMT[f]) + _f32_bits(s) + struct.pack("<i", 0)
+                       for p, f, s in zip(state["buffers"], fmts, scales))
+    tensors, blob = b"", bytearray()
+    for t in state["tensors"]:
+        raw = t.contiguous().view(torch.uint8).numpy().tobytes()
+        blob += b"\0" * (-len(blob) % FLAT_WEIGHT_ALIGN)       # every tensor starts on a 256-byte boundary
+        tensors += struct.pack("<iiQQ", _FLAT_DTYPE[t.dtype], 0, len(raw), len(blob))
+        blob += raw
+    meta_b = struct.pack("<8i", state["format"], int(meta["align_corner"]), meta["num_classes"], meta["in_channels"],
+                         _FLAT_MODELS.index(meta["model"]), len(plan), len(state["buffers"]), len(state["tensors"]))
+    parts = {"meta": meta_b, "records": records, "buffers": buffers, "tensors": tensors, "strings": names,
+             "weights": bytes(blob), "input": b""}
+    if mean is not None:
+        order = [2, 1, 0] if bgr else [0, 1, 2]
+        parts["input"] = input_table(mean, std).numpy().tobytes() + struct.pack("<4i", *order, 0)
+    out, table = bytearray(b"\0" * FLAT_HEADER_BYTES), []
+    for name in FLAT_SECTIONS:                       # the weight blob and the table behind it start on 256 bytes
+        out += b"\0" * (-len(out) % (FLAT_WEIGHT_ALIGN if name in ("weights", "input") else 16))
+        table.append((len(out), len(parts[name])))
+        out += parts[name]
+    head = FLAT_MAGIC + struct.pack("<IIQII", FLAT_VERSION, FLAT_HEADER_BYTES, len(out), len(FLAT_SECTIONS), 0)
+    head += b"".join(struct.pack("<QQ", o, n) for o, n in table)
+    out[:FLAT_HEADER_BYTES] = head
+    return bytes(out)
+
+
+def save_flat(engine, path, mean=None, std=None, bgr=True):
+    """Write `engine` as a flat engine file: what dcfp_engine_open, deploy.CEngine and tools/engine_run.cpp load.
+    mean / std (per RGB channel, of the 0 .. 1 image): the file also carries the uint8 input table, without which it
+    cannot take uint8 input; bgr: the uint8 frames are B, G, R (the loaders' order), else R, G, B."""
+    data = flat_bytes(engine, mean, std, bgr)
+    with open(path, "wb") as f:
+        f.write(data)
+    return len(data)
+
+
+def flat_sections(data):
+    """{section name: (offset, size)} of a flat engine file's bytes, as its header states them."""
+    import struct
+    return {name: struct.unpack_from("<QQ", data, 32 + 16 * i) for i, name in enumerate(FLAT_SECTIONS)}
+
+
+def is_flat_file(path):
+    with open(path, "rb") as f:
+        return f.read(len(FLAT_MAGIC)) == FLAT_MAGIC
+
+
+class CEngine:
+    """A flat engine file run by the library's C runtime (dcfp_engine_*): the plan is parsed, sized and launched in C;
+    this wrapper owns the torch-allocated weight and workspace tensors and offers what an Engine offers the
+    evaluation drivers: engine(image) -> [logits], engine.lowres_logits(image) -> [lowres], engine.align_corner, plus
+    run_u8(uint8 [N,H,W,3] image) -> [lowres] for a file that carries the input table.  Same kernels, same arguments,
+    same bits as the Engine the file was written from.  Not thread-safe (one handle, one cache of launch lists)."""
+
+    def __init__(self, path_or_bytes, device="cuda"):
+        L = _lib.lib()
+        self._lib = L
+        self.handle = C.c_void_p()
+        err = C.create_string_buffer(256)
+        if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+            data = bytes(path_or_bytes)
+            st = L.dcfp_engine_open_memory(data, len(data), C.byref(self.handle), err, len(err))
+        else:
+            st = L.dcfp_engine_open(os.fsencode(path_or_bytes), C.byref(self.handle), err, len(err))
+        if st != 0:
+            self.handle = C.c_void_p()
+            raise ValueError(f"deploy.CEngine: {err.value.decode(errors='replace')} (status {st})")
+        info = _lib.EngineInfo()
+        check(L.dcfp_engine_info(self.handle, C.byref(info)), "deploy.CEngine: info")
+        self.format, self.num_classes, self.align_corner = info.format, info.num_classes, bool(info.align_corner)
+        self.has_input_table = bool(info.has_input_table)
+        self.meta = {"align_corner": self.align_corner, "num_classes": info.num_classes, "in_channels": info.in_channels,
+                     "dtype": "float16" if info.format == FORMAT else "float8_e4m3fn", "model": _FLAT_MODELS[info.model]}
+        self.n_records, self.n_buffers, self.n_slots = info.n_records, info.n_buffers, info.n_slots
+        self.training = False
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("deploy.CEngine runs on the MI355X HIP kernels only (no CPU fallback exists)")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        self.device = device
+        self.weights = torch.empty(int(L.dcfp_engine_weight_bytes(self.handle)), dtype=torch.uint8, device=device)
+        with torch.cuda.device(device):
+            check(L.dcfp_engine_upload(self.handle, C.c_void_p(self.weights.data_ptr()), ops._stream()),
+                  "deploy.CEngine: upload")
+            torch.cuda.current_stream().synchronize()
+        self._workspace = None
+
+    def __del__(self):
+        if getattr(self, "handle", None) is not None and self.handle.value:
+            self._lib.dcfp_engine_close(self.handle)
+            self.handle = C.c_void_p()
+
+    def eval(self):
+        return self
+
+    def output_shape(self, N, H, W):
+        c, h, w = C.c_int(), C.c_int(), C.c_int()
+        st = self._lib.dcfp_engine_output_shape(self.handle, N, H, W, C.byref(c), C.byref(h), C.byref(w))
+        if st != 0:
+            raise RuntimeError(f"deploy.CEngine: a {N}x{H}x{W} input is too small for a layer or not supported "
+                               f"(status {st})")
+        return (N, c.value, h.value, w.value)
+
+    def buffer_shapes(self, H, W):
+        """{buffer id: (h, w)}, what Engine.buffer_shapes returns (-1: the low-resolution logits)."""
+        pairs = (C.c_int * (2 * self.n_buffers))()
+        st = self._lib.dcfp_engine_buffer_shapes(self.handle, H, W, pairs, self.n_buffers)
+        if st != 0:
+            raise RuntimeError(f"deploy.CEngine: a {H}x{W} input is too small for a layer or not supported (status {st})")
+        hw = {b: (pairs[2 * b], pairs[2 * b + 1]) for b in range(self.n_buffers) if pairs[2 * b] > 0}
+        hw[-1] = self.output_shape(1, H, W)[2:]
+        return hw
+
+    def workspace_bytes(self, N, H, W):
+        return int(self._lib.dcfp_engine_workspace_bytes(self.handle, N, H, W))
+
+    def workspace(self, N, H, W):
+        """The workspace tensor a call of this shape runs in (grown to the largest shape seen; its bytes need no
+        initialising)."""
+        need = self.workspace_bytes(N, H, W)
+        if need == 0:
+            raise RuntimeError(f"deploy.CEngine: a {N}x{H}x{W} input is too small for a layer or not supported")
+        if self._workspace is None or self._workspace.numel() < need:
+            self._workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._workspace
+
+    def _check_image(self, image, dtype, what):
+        if not isinstance(image, torch.Tensor) or not image.is_cuda or image.device != self.device:
+            raise RuntimeError(f"deploy.CEngine: the engine is on {self.device}; the image must be a tensor there")
+        if image.dtype != dtype or image.dim() != 4:
+            raise RuntimeError(f"deploy.CEngine: image must be {what}")
+
+    def _launch(self, run, image, extra, N, H, W):
+        with torch.cuda.device(self.device):
+            out = torch.empty(self.output_shape(N, H, W), dtype=torch.float32, device=self.device)
+            ws = self.workspace(N, H, W)
+            check(run(self.handle, C.c_void_p(self.weights.data_ptr()), C.c_void_p(image.data_ptr()), *extra, N, H, W,
+                      C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(out.data_ptr()), ops._stream()),
+                  "deploy.CEngine: run")
+        return [out]
+
+    @torch.no_grad()
+    def lowres_logits(self, image, deepsup=False):
+        """[fp32 N x classes x h x w logits at 1/os resolution] of a float32 [N,3,H,W] image."""
+        self._check_image(image, torch.float32, f"float32 [N,{self.meta['in_channels']},H,W]")
+        if image.shape[1] != self.meta["in_channels"]:
+            raise RuntimeError(f"deploy.CEngine: image must be float32 [N,{self.meta['in_channels']},H,W]")
+        image = image.contiguous()
+        N, _, H, W = image.shape
+        return self._launch(self._lib.dcfp_engine_run_f32, image, (), N, H, W)
+
+    @torch.no_grad()
+    def run_u8(self, image_u8):
+        """[fp32 low-resolution logits] of a uint8 [N,H,W,3] image (the channel order the file was saved for),
+        normalised on the device by the file's table.  Rows may be pitched: image_u8[:, :, :W] of a wider tensor."""
+        self._check_image(image_u8, torch.uint8, "uint8 [N,H,W,3]")
+        N, H, W, Cc = image_u8.shape
+        if Cc != 3:
+            raise RuntimeError("deploy.CEngine: image must be uint8 [N,H,W,3]")
+        if not self.has_input_table:
+            raise RuntimeError("deploy.CEngine: this engine file carries no input table (save_flat(mean=, std=))")
+        sn, sh, sw, sc = image_u8.stride()
+        if sc != 1 or sw != 3 or sh < 3 * W or (N > 1 and sn != H * sh):
+            image_u8 = image_u8.contiguous()
+            sh = 3 * W
+        return self._launch(self._lib.dcfp_engine_run_u8, image_u8, (sh,), N, H, W)
+
+    @torch.no_grad()
+    def __call__(self, image, labels=None, deepsup=False):
+        """[fp32 N x classes x H x W logits]: the low-resolution logits through the bilinear upsample kernel."""
+        lowres = self.lowres_logits(image)
+        return [ops.upsample_bilinear(z, image.shape[2:], self.align_corner) for z in lowres]

@@ -28,6 +28,9 @@
  *     kernel / algorithm selection A/B knobs, results are identical up to the documented
  *     fp32 tolerances; changing them after the first call has no effect.  (A thread_local 16-entry cache
  *     of dispatch decisions for dilated convs is the only other state.)
+ *     The second object that keeps state is an engine handle (dcfp_engine_t, the last section): it owns HOST memory
+ *     only - the parsed engine file and the cached per-shape launch lists - from dcfp_engine_open to dcfp_engine_close;
+ *     the device weights, workspace, input and output stay the caller's.
  *   - tensors are fp32, NCHW, dense unless a *_nstride (batch stride, in elements)
  *     argument says otherwise.
  *   - return value: 0 ok; <0 bad descriptor / unsupported shape (DCFP_E_*);
@@ -1003,6 +1006,63 @@ int dcfp_lovasz_bwd_f32(const float* logits, const int64_t* labels, int ignore_i
                         const float* grad_scale /* device scalar */, float* asum, float* dlogits, dcfp_stream_t stream);
 int dcfp_lovasz_errors_u32(const float* logits, const int64_t* labels, int ignore_index, int N, int C, int h, int w,
                            int H, int W, int align_corners, uint32_t* errors, dcfp_stream_t stream);
+
+/* ------------------------------------------------- the C engine runtime (engine_rt.hip, image_u8.hip)
+ * A deployment engine as a file a C program loads and runs: deploy.save_flat writes the plan, the tables and one weight
+ * blob in a flat little-endian layout; the calls below parse it (trusting nothing in it), size the workspace for an
+ * input shape and run the plan through the entry points of the two sections above, in plan order, on `stream` - the
+ * same kernels with the same arguments as dcfp_amd.deploy.Engine, hence the same bits.
+ *
+ * The caller owns every device buffer: the weights (dcfp_engine_weight_bytes, filled by dcfp_engine_upload), the
+ * workspace (dcfp_engine_workspace_bytes for the shape; activation slots - buffers with disjoint lifetimes share one,
+ * each rounded up to 256 bytes - followed by the pools' partial sums; no byte of it needs initialising), the image
+ * and the logits, all 16-byte aligned.  The handle owns host memory only.  A handle is NOT thread-safe: calls on one
+ * handle (they update its cache of launch lists) must not overlap; different handles are independent.
+ *
+ * Errors: a file the parser rejects is DCFP_E_BADDESC with a one-line message in err (errlen bytes, may be null);
+ * an input too small for a layer DCFP_E_BADDESC, a size no kernel takes DCFP_E_UNSUPPORTED, a workspace too small
+ * DCFP_E_WORKSPACE - each before anything is launched; dcfp_engine_run_u8 on a file without an input table
+ * DCFP_E_UNSUPPORTED.  A failing launch returns that kernel's status and nothing further is launched.
+ * The full-resolution steps stay separate calls: dcfp_upsample_bilinear_fwd_f32 / dcfp_upsample_argmax_f32 on the
+ * logits with dcfp_engine_info_t.align_corner. */
+typedef struct dcfp_engine* dcfp_engine_t;
+typedef struct dcfp_engine_info_t {
+    int32_t format;          /* 1: fp16 engine, 2: fp8 engine                                   */
+    int32_t num_classes, in_channels, align_corner;
+    int32_t model;           /* 0 simple, 1 deeplabv3, 2 deeplabv3p, 3 psp                      */
+    int32_t n_records, n_buffers, n_slots;
+    int32_t has_input_table; /* the file carries the uint8 lookup table: dcfp_engine_run_u8 works */
+} dcfp_engine_info_t;
+/* Host only, no GPU call. */
+int dcfp_engine_open(const char* path, dcfp_engine_t* out, char* err, size_t errlen);
+int dcfp_engine_open_memory(const void* bytes, size_t n, dcfp_engine_t* out, char* err, size_t errlen);
+void dcfp_engine_close(dcfp_engine_t e);
+int dcfp_engine_info(dcfp_engine_t e, dcfp_engine_info_t* out);
+size_t dcfp_engine_weight_bytes(dcfp_engine_t e);
+/* One host-to-device copy of the weight blob (and the input table behind it) on `stream`. */
+int dcfp_engine_upload(dcfp_engine_t e, void* dev_weights, dcfp_stream_t stream);
+/* The logits of an N x in_channels x H x W input: fp32 NCHW dense [N, *C, *h, *w]. */
+int dcfp_engine_output_shape(dcfp_engine_t e, int N, int H, int W, int* C, int* h, int* w);
+/* hw_pairs[2b], hw_pairs[2b+1] = height and width of activation buffer b for an H x W input (0, 0: no record writes
+ * it); n_pairs >= n_buffers. */
+int dcfp_engine_buffer_shapes(dcfp_engine_t e, int H, int W, int* hw_pairs, int n_pairs);
+/* 0: the shape is not supported (too small for a layer, or beyond a kernel's limits). */
+size_t dcfp_engine_workspace_bytes(dcfp_engine_t e, int N, int H, int W);
+/* image_nchw: fp32 [N, in_channels, H, W] dense on the device. */
+int dcfp_engine_run_f32(dcfp_engine_t e, const void* dev_weights, const float* image_nchw, int N, int H, int W,
+                        void* workspace, size_t workspace_bytes, float* logits_nchw, dcfp_stream_t stream);
+/* image_hwc: uint8 [N][H][W][3] on the device, rows row_pitch_bytes >= 3 W apart (images H * row_pitch_bytes apart),
+ * normalised by the file's table. */
+int dcfp_engine_run_u8(dcfp_engine_t e, const void* dev_weights, const uint8_t* image_hwc, size_t row_pitch_bytes,
+                       int N, int H, int W, void* workspace, size_t workspace_bytes, float* logits_nchw,
+                       dcfp_stream_t stream);
+/* The uint8 input converter: dst[n][y][x][c] = table[c * 256 + src[n][y][x][order[c]]] for c < 3 and exact zeros for
+ * c = 3 .. C8-1; src uint8 [N][H][W][3], rows row_pitch_bytes >= 3 W apart, any alignment; table 3 x 256 fp16 on the
+ * device (deploy.input_table: fp16((v / 255 - mean[c]) / std[c]), rounded once from fp64), order a HOST array of 3
+ * source byte indices (BGR -> RGB is {2, 1, 0}); dst fp16 NHWC [N,H,W,C8], C8 a multiple of 8.  A pure lookup: the
+ * result is exact.  3 bytes read and 2 C8 written per pixel. */
+int dcfp_image_u8_hwc_to_nhwc_f16(const uint8_t* src, size_t row_pitch_bytes, int N, int H, int W, const void* table,
+                                  const int* order, void* dst, int C8, dcfp_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -3,7 +3,14 @@
 (optionally slimmed) model, freeze it into an fp16 engine (dcfp_amd/deploy.py) - or, with --precision fp8, calibrate that engine on
 --calib-batches batches and build the e4m3 engine - save the engine, reload it, and time
 it as totrt.benchmark does: 10 warm-up calls, 50 timed calls, each timed call synchronised; prints the average batch
-time.  Without --restore-from the model keeps its initial weights (synthetic, as tools/train.py starts from)."""
+time.  Without --restore-from the model keeps its initial weights (synthetic, as tools/train.py starts from).
+
+--save-flat PATH also writes the engine as a flat engine file, what dcfp_engine_open and
+tools/engine_run.cpp load.  --runtime c times deploy.CEngine - the same plan launched by the library's C runtime - in the
+same run with the same protocol and prints three lines: the Python engine, the C runtime on the same fp32 batch, and the C
+runtime on a uint8 frame with the host -> device copy of the frame included; then the uint8 input kernel's own time
+(device events around a chain of launches) next to its byte bound, 3 B read + 2 * 8 B written per pixel at the measured
+float4-copy rate of an MI355X."""
 import argparse
 import json
 import os
@@ -45,8 +52,67 @@ def get_parser():
                    help="fp8: batches the activation maxima are taken over (synthetic images without --data-para)")
     p.add_argument("--data-para", type=str, default=None,
                    help='fp8: JSON {"root": ..., "list_path": ...}: calibrate on the first batches of --dataset')
+    p.add_argument("--save-flat", type=str, default=None,
+                   help="also write the flat engine file (with the uint8 input table) that the C runtime loads")
+    p.add_argument("--runtime", type=str, default="python", choices=("python", "c"),
+                   help="c: also time deploy.CEngine (fp32 and uint8 input) in the same run")
     p.add_argument("--seed", type=int, default=12345)
     return p
+
+
+MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)      # the datasets' normalisation (datasets/base.py)
+HBM_MEASURED = 6.29e12                                        # float4-copy rate measured on an MI355X (8.0e12 on the sheet)
+
+
+def time_u8_kernel(ce, frame, launches=200):
+    """Seconds per launch of dcfp_image_u8_hwc_to_nhwc_f16 on `frame` (uint8 [N,H,W,3] on the device): device events
+    around `launches` back-to-back launches, after a warm-up."""
+    import ctypes as C
+    from dcfp_amd import _lib, ops
+    L = _lib.lib()
+    N, H, W, _ = frame.shape
+    table = deploy.input_table(MEAN, STD).to(frame.device)
+    dst = torch.empty((N, H, W, 8), dtype=torch.float16, device=frame.device)
+    order = (C.c_int * 3)(2, 1, 0)
+
+    def launch():
+        _lib.check(L.dcfp_image_u8_hwc_to_nhwc_f16(C.c_void_p(frame.data_ptr()), 3 * W, N, H, W,
+                                                   C.c_void_p(table.data_ptr()), order, C.c_void_p(dst.data_ptr()), 8,
+                                                   ops._stream()), "uint8 input kernel")
+    for _ in range(10):
+        launch()
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for _ in range(launches):
+        launch()
+    t1.record()
+    torch.cuda.synchronize()
+    return t0.elapsed_time(t1) * 1e-3 / launches
+
+
+def benchmark_c_runtime(args, flat_path, x, dev, h, w):
+    """The C runtime's two lines and the uint8 kernel's own line."""
+    from dcfp_amd import ops
+    ce = deploy.CEngine(flat_path, dev)
+    what = f"{args.model}-{args.backbone} {h}x{w} batch {args.batch_size} {args.precision} engine"
+    avg_c = benchmark(ce, x)
+    print(f"Average batch time: {avg_c * 1e3:.2f} ms ({args.batch_size / avg_c:.2f} images/s) {what}, C runtime, "
+          f"fp32 input")
+    gen = torch.Generator().manual_seed(args.seed)
+    host = torch.randint(0, 256, (args.batch_size, h, w, 3), generator=gen, dtype=torch.uint8).pin_memory()
+    frame = torch.empty_like(host, device=dev)
+
+    def from_frame(_):                               # the frame crosses to the device inside the timed call
+        frame.copy_(host, non_blocking=True)
+        return [ops.upsample_bilinear(z, (h, w), ce.align_corner) for z in ce.run_u8(frame)]
+    avg_u8 = benchmark(from_frame, None)
+    print(f"Average batch time: {avg_u8 * 1e3:.2f} ms ({args.batch_size / avg_u8:.2f} images/s) {what}, C runtime, "
+          f"uint8 input (host -> device copy of the frame included)")
+    t = time_u8_kernel(ce, frame)
+    nbytes = args.batch_size * h * w * (3 + 2 * 8)
+    print(f"uint8 input kernel: {t * 1e6:.1f} us for {nbytes / 1e6:.1f} MB ({nbytes / t / 1e12:.2f} TB/s); byte bound "
+          f"{nbytes / HBM_MEASURED * 1e6:.1f} us at {HBM_MEASURED / 1e12:.2f} TB/s")
+    return avg_c, avg_u8, t
 
 
 def get_num_classes(dataset):
@@ -111,6 +177,12 @@ def main(argv=None):
     avg = benchmark(engine, x)
     print(f"Average batch time: {avg * 1e3:.2f} ms ({args.batch_size / avg:.2f} images/s) "
           f"{args.model}-{args.backbone} {h}x{w} batch {args.batch_size} {args.precision} engine")
+    if args.save_flat or args.runtime == "c":
+        flat_path = args.save_flat or os.path.join(args.save_dir, f"engine_{args.precision}.bin")
+        size = deploy.save_flat(engine, flat_path, MEAN, STD)
+        print(f"saved {flat_path}: flat engine file version {deploy.FLAT_VERSION}, {size / 2 ** 20:.1f} MiB")
+        if args.runtime == "c":
+            benchmark_c_runtime(args, flat_path, x, dev, h, w)
     return avg
 
 

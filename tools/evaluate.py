@@ -127,10 +127,15 @@ def build_model(args):
 
 def load_engine_file(args, device):
     """The saved engine of --engine-file on `device`; its class count and align_corner replace the command line's."""
-    engine = deploy.load_engine(args.engine_file, device)
+    if deploy.is_flat_file(args.engine_file):       # a flat engine file (its magic says so): the C runtime runs it
+        engine = deploy.CEngine(args.engine_file, device)
+        records = engine.n_records
+    else:
+        engine = deploy.load_engine(args.engine_file, device)
+        records = len(engine.plan)
     args.num_classes, args.align_corner = engine.num_classes, engine.align_corner
     print(f"engine {args.engine_file}: format {engine.format}, {engine.meta['dtype']}, {engine.meta['model']}, "
-          f"{len(engine.plan)} layer records", flush=True)
+          f"{records} layer records" + (", C runtime" if isinstance(engine, deploy.CEngine) else ""), flush=True)
     return engine
 
 
