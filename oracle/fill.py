@@ -47,9 +47,11 @@ def closed_form_state(state_dict, gamma_amp=0.2, gamma_mid=1.0):
     return out
 
 
-def closed_form_input(N, H, W, dtype=torch.float32):
+def closed_form_input(N, H, W, dtype=torch.float32, phase=0.0):
+    """phase: added to the offset of both terms - another draw of the same distribution (0: the input of every fixture
+    made before the second-draw one)."""
     n = N * 3 * H * W
-    x = 0.7 * _wave(n, 0.0137, 0.3) + 0.9 * _noise(n, 4.1414, 0.77)
+    x = 0.7 * _wave(n, 0.0137, 0.3 + phase) + 0.9 * _noise(n, 4.1414, 0.77 + phase)
     return x.reshape(N, 3, H, W).to(dtype)
 
 

@@ -3,7 +3,8 @@
 Dev-container only (the reference never travels to the GPU box).  Run:
     PYTHONDONTWRITEBYTECODE=1 python oracle/make_golden.py [--out DIR] [KEY ...]
 KEYs: see the bottom of this file (`v3p` / `psp`: the whole-model, prune and flops fixtures of that head; `v3p:model`
-etc. for one of them).  --out: write there instead of tests/golden/ (to compare a recipe change with the fixtures).
+etc. for one of them; `ade` / `coco` / `ctx`: the whole-model fixture of that training recipe, `ade:p1`: ADE20K's on a
+second draw of the input).  --out: write there instead of tests/golden/ (to compare a recipe change with the fixtures).
 Accommodations — none of them touches a reference file:
   * `ordered_set` (third-party, un-vendored) -> an insertion-ordered list stand-in;
   * torch 2.x names conv's autograd node 'ConvolutionBackward0' -> registered at run time;
@@ -71,10 +72,12 @@ class _DS:
     class_weights = None
 
 
-def build_ref(model, backbone, align, dtype):
-    crit = build_criterions("ce", _DS(), {"ds_weight": 0.4})
+def build_ref(model, backbone, align, dtype, num_classes=19, backbone_para=None):
+    ds = _DS()
+    ds.num_classes = num_classes
+    crit = build_criterions("ce", ds, {"ds_weight": 0.4})
     cls = getattr(networks, model).Seg_Model
-    m = cls(backbone=backbone, backbone_para=dict(BB_PARA), model_para={}, num_classes=19,
+    m = cls(backbone=backbone, backbone_para=dict(backbone_para or BB_PARA), model_para={}, num_classes=num_classes,
             align_corner=align, criterion=crit, deepsup=True)
     m.load_state_dict(fill.closed_form_state(m.state_dict()))
     m.conv_deepsup[3].p = 0.0
@@ -93,19 +96,27 @@ def _grad_summaries(m, res, sfx):
 
 def whole_model(tag, model, backbone, N, H, W, align, cls="last_conv.6",
                 convs=("backbone.conv1.0", "backbone.layer1.0.conv1", "backbone.layer2.0.conv2"),
-                running=("backbone.bn1",), logit_step=2, compact=False):
+                running=("backbone.bn1",), logit_step=2, compact=False, num_classes=19, backbone_para=None, phase=0.0,
+                eval_logits=False, summaries_only=False):
     """cls: the classifier conv (weight and bias gradient stored); convs: further convs whose weight gradient is stored
     whole; running: BatchNorms whose running statistics are stored; logits are stored at every logit_step-th pixel
     (fixture size; recorded as `logit_step` unless 2).  compact: the fp64 gradient arrays are kept as float32
     differences to the fp32 run (key suffix d64m32 instead of 64: a test rebuilds fp64 as fp32 + difference), which
-    keeps the files of the heads added later under 1 MiB."""
+    keeps the files of the heads added later under 1 MiB.
+    num_classes / backbone_para (None: 19 / BB_PARA, the Cityscapes recipe): the recipe, recorded in the file when given;
+    phase: the draw of the input (fill.closed_form_input); eval_logits: also the eval-mode logits of both heads;
+    summaries_only: the loss, the per-tensor gradient summaries and the BatchNorm gradients, nothing else (what a second
+    draw of the input is compared by)."""
+    recipe = dict(num_classes=num_classes, backbone_para=backbone_para)
+
+    def inputs(dtype):
+        return fill.closed_form_input(N, H, W, dtype, phase), fill.closed_form_labels(N, H, W, num_classes=num_classes)
     res = {}
     for dtype, sfx in ((torch.float32, "32"), (torch.float64, "64")):
         torch.manual_seed(0)
-        m = build_ref(model, backbone, align, dtype)
+        m = build_ref(model, backbone, align, dtype, **recipe)
         m.train()
-        x = fill.closed_form_input(N, H, W, dtype)
-        lab = fill.closed_form_labels(N, H, W)
+        x, lab = inputs(dtype)
         loss = m(x, lab, deepsup=True)["loss"]
         loss.backward()
         grads = {k: p.grad.detach() for k, p in m.named_parameters()}
@@ -113,9 +124,10 @@ def whole_model(tag, model, backbone, N, H, W, align, cls="last_conv.6",
         res["loss" + sfx] = np.array(loss.item(), dtype=np.float64)
         flat = {"bn_wgrad": torch.cat([grads[n + ".weight"].reshape(-1) for n in bn_names]),
                 "bn_bgrad": torch.cat([grads[n + ".bias"].reshape(-1) for n in bn_names])}
-        for cname in tuple(convs) + (cls,):
-            flat["wgrad:" + cname + ":"] = grads[cname + ".weight"]
-        flat["bgrad:" + cls + ":"] = grads[cls + ".bias"]
+        if not summaries_only:
+            for cname in tuple(convs) + (cls,):
+                flat["wgrad:" + cname + ":"] = grads[cname + ".weight"]
+            flat["bgrad:" + cls + ":"] = grads[cls + ".bias"]
         for k, v in flat.items():
             if compact and sfx == "64":
                 res[k + "d64m32"] = (v - torch.from_numpy(res[k + "32"]).double()).float().numpy()
@@ -124,6 +136,9 @@ def whole_model(tag, model, backbone, N, H, W, align, cls="last_conv.6",
         pnames = _grad_summaries(m, res, sfx)
         if sfx == "32":
             res["param_names"] = np.array(pnames)
+        if summaries_only:
+            res["bn_names"] = np.array(bn_names)
+            continue
         # running stats after the training-mode forward
         sd = m.state_dict()
         for bn in running:
@@ -131,23 +146,30 @@ def whole_model(tag, model, backbone, N, H, W, align, cls="last_conv.6",
             res[f"rv:{bn}:" + sfx] = sd[bn + ".running_var"].numpy()
         # logits of both heads: second (eval-free) pass in train mode would re-update stats, so
         # take them from a fresh identical model
-        m2 = build_ref(model, backbone, align, dtype)
+        m2 = build_ref(model, backbone, align, dtype, **recipe)
         m2.train()
         with torch.no_grad():
             outs = m2(x, None, deepsup=True)
+        heads = [("logits", outs[0]), ("logits_ds", outs[1])]
+        if eval_logits:    # BatchNorm folded from the closed-form running statistics: a third identical model
+            m3 = build_ref(model, backbone, align, dtype, **recipe)
+            m3.eval()
+            with torch.no_grad():
+                outs_e = m3(x, None, deepsup=True)
+            heads += [("logits_eval", outs_e[0]), ("logits_eval_ds", outs_e[1])]
         # stored sub-sampled; fp64 kept as the difference to fp32
         s = logit_step
         if sfx == "32":
-            l32 = [o[:, :, ::s, ::s].clone() for o in outs]
-            res["logits32"] = l32[0].numpy()
-            res["logits_ds32"] = l32[1].numpy()
+            l32 = {k: o[:, :, ::s, ::s].clone() for k, o in heads}
+            for k, o in l32.items():
+                res[k + "32"] = o.numpy()
             res["bn_names"] = np.array(bn_names)
             res["state_keys"] = np.array(list(sd.keys()))
             res["state_shapes"] = np.array([str(tuple(v.shape)) for v in sd.values()])
             res["ignore_prune_layer"] = np.array(m.ignore_prune_layer)
         else:
-            res["logits_d64m32"] = (outs[0][:, :, ::s, ::s] - l32[0].double()).float().numpy()
-            res["logits_ds_d64m32"] = (outs[1][:, :, ::s, ::s] - l32[1].double()).float().numpy()
+            for k, o in heads:
+                res[k + "_d64m32"] = (o[:, :, ::s, ::s] - l32[k].double()).float().numpy()
     # Round 4: the SAME fp32 reference code in four more summation orders (1 / 2 / 4 threads, oneDNN off) - only the two
     # per-tensor gradient summaries.  One fp32 run is one draw of a tensor's fp32-vs-fp64 error (which near-zero
     # pre-activations get the other ReLU mask); the per-tensor bound of tests/_parity.py takes the tensor's error as the
@@ -157,10 +179,9 @@ def whole_model(tag, model, backbone, N, H, W, align, cls="last_conv.6",
         torch.set_num_threads(threads)
         torch.backends.mkldnn.enabled = dnn
         torch.manual_seed(0)
-        m = build_ref(model, backbone, align, torch.float32)
+        m = build_ref(model, backbone, align, torch.float32, **recipe)
         m.train()
-        x = fill.closed_form_input(N, H, W, torch.float32)
-        lab = fill.closed_form_labels(N, H, W)
+        x, lab = inputs(torch.float32)
         m(x, lab, deepsup=True)["loss"].backward()
         _grad_summaries(m, res, sfx)
     torch.set_num_threads(8)
@@ -169,6 +190,11 @@ def whole_model(tag, model, backbone, N, H, W, align, cls="last_conv.6",
     res["meta"] = np.array([N, H, W, int(align)])
     if logit_step != 2:
         res["logit_step"] = np.array(logit_step)
+    if backbone_para is not None:
+        import json
+        res["num_classes"] = np.array(num_classes)
+        res["backbone_para"] = np.array(json.dumps(backbone_para))
+        res["phase"] = np.array(phase)
     np.savez_compressed(os.path.join(OUT, f"model_{tag}.npz"), **res)
     print("wrote", tag, "loss32", res["loss32"], "loss64", res["loss64"])
 
@@ -209,6 +235,27 @@ def eic_trajectory():
 
 PRUNE_CASES = [("v3r50", "deeplabv3", "resnet50", True, 0.5), ("v3r50", "deeplabv3", "resnet50", True, 0.7),
                ("v3r101", "deeplabv3", "resnet101", True, 0.5), ("simple_r50", "simple", "resnet50", False, 0.5)]
+
+
+# the other three recipes (scripts/{ade,coco,ctx}/pretrain.sh): DeepLabv3-R50, align_corner False, three layer4 blocks at
+# one dilation, many classes; at 2 x 96 x 128 - even, not square, every strided stage sees an even map, and the 12 x 16
+# feature map gives the ASPP's dilation-12 branch live off-centre taps in one direction only.
+# command-line key -> (classes, logit_step, convs stored whole beside the classifier).  A file must stay under 1 MiB and
+# the BatchNorm gradients of a ResNet-50 are 0.44 MB of it whatever the recipe, so the classifier's C x 256 weight
+# gradient decides what else fits: the deep-supervision classifier's C x 512 only at 59 classes, and the logits at the
+# largest density that still fits.  The steps are odd: every 8th pixel of an 8x upsample has one interpolation phase.
+RECIPE_PARA = {"os": 8, "mg_unit": [1, 1, 1], "inplanes": 128, "pretrained": False}
+_STEM = ("backbone.conv1.0", "backbone.layer1.0.conv1")
+RECIPES = {"ade": (150, 29, _STEM), "coco": (171, 33, _STEM), "ctx": (59, 21, _STEM + ("conv_deepsup.4",))}
+
+
+def recipe_model(key, phase=0.0, summaries_only=False):
+    """model_v3_r50_<key>_2x96x128.npz, or - summaries_only - its second input draw ..._<key>_p1_..."""
+    classes, step, convs = RECIPES[key]
+    tag = f"v3_r50_{key}_" + ("p1_" if summaries_only else "") + "2x96x128"
+    whole_model(tag, "deeplabv3", "resnet50", 2, 96, 128, False, convs=convs, logit_step=step, compact=True,
+                num_classes=classes, backbone_para=RECIPE_PARA, phase=phase, eval_logits=not summaries_only,
+                summaries_only=summaries_only)
 
 
 # the heads added after DeepLabv3: command-line key -> what their whole-model, prune and flops fixtures are made from
@@ -497,3 +544,8 @@ if __name__ == "__main__":
             masks_and_surgery(cases=[(h["prune_tag"], h["model"], "resnet50", True, 0.5)])
         if key in which or key + ":flops" in which:
             flops_golden(h["model"], key, ("resnet50",), h["flops_file"])
+    for key in RECIPES:              # `ade`, `coco`, `ctx`; `ade:p1`: ADE20K's recipe on a second draw of the input
+        if key in which:
+            recipe_model(key)
+        if key + ":p1" in which:
+            recipe_model(key, phase=1.0, summaries_only=True)

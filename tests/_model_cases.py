@@ -1,4 +1,5 @@
-"""What the whole-model tests of every head share (tests/test_model_gpu.py, test_deeplabv3p_*.py, test_psp_*.py):
+"""What the whole-model tests of every head share (tests/test_model_gpu.py, test_recipes_gpu.py, test_deeplabv3p_*.py,
+test_psp_*.py):
 one record per whole-model fixture (CASES), the fixture reader that hides its two fp64 encodings (load_golden), the
 comparison against it (compare_to_golden: numpy only, tests/test_model_cases_cpu.py runs it without a GPU) and the
 bodies of the tests every head has - slim model, data-parallel child, train -> prune tools, and the host-side trio
@@ -29,8 +30,18 @@ BB = {"os": 8, "mg_unit": [1, 2, 4], "inplanes": 128, "pretrained": False}
 # running statistics it stores; running_rel: False - max|mine - fp64| < 1e-5; True - <= max(1e-5, 3 max|fp32 - fp64|)
 # (PSPNet: the first pyramid stage's BatchNorm sees N values per channel, the bottleneck's a 4096-channel 3x3 sum - the
 # reference's own fp32 run is up to 3.7e-5 from fp64 there)
-Case = collections.namedtuple("Case", "tag model backbone classifier convs running running_rel")
+# classes / backbone_para: the recipe (default: Cityscapes'); eval_logits: the fixture also holds both heads' eval-mode logits
+Case = collections.namedtuple("Case", "tag model backbone classifier convs running running_rel classes backbone_para "
+                                      "eval_logits", defaults=(19, BB, False))
 _V3_CONVS = ("backbone.conv1.0", "backbone.layer1.0.conv1", "backbone.layer2.0.conv2", "last_conv.6")
+# the ADE20K / COCO-Stuff / Pascal-Context recipes: three layer4 blocks at one dilation, align_corner False (in the
+# fixture's meta), many classes - at 2 x 96 x 128, an even size whose 12 x 16 feature map is not square
+RECIPE_BB = {"os": 8, "mg_unit": [1, 1, 1], "inplanes": 128, "pretrained": False}
+_STEM = ("backbone.conv1.0", "backbone.layer1.0.conv1")
+# key -> (classes, convs).  (The deep-supervision classifier's whole weight gradient fits a file of 1 MiB only at 59
+# classes; at 150 / 171 it is held through its norm and projection like every other tensor.)
+RECIPES = {"ade": (150, _STEM + ("last_conv.6",)), "coco": (171, _STEM + ("last_conv.6",)),
+           "ctx": (59, _STEM + ("conv_deepsup.4", "last_conv.6"))}
 CASES = {c.tag: c for c in (
     Case("simple_r50_4x64x64", "simple", "resnet50", "last_conv.6", _V3_CONVS, ("backbone.bn1",), False),
     Case("v3_r50_2x65x65", "deeplabv3", "resnet50", "last_conv.6", _V3_CONVS, ("backbone.bn1",), False),
@@ -41,26 +52,34 @@ CASES = {c.tag: c for c in (
     Case("psp_r50_2x65x65", "psp", "resnet50", "last_conv",
          ("backbone.conv1.0", "backbone.layer1.0.conv1", "last_conv"),
          ("backbone.bn1", "ppm.stages.0.2", "ppm.bottleneck.1"), True),
-)}
+) + tuple(Case(f"v3_r50_{key}_2x96x128", "deeplabv3", "resnet50", "last_conv.6", convs, ("backbone.bn1",), False,
+               classes, RECIPE_BB, True) for key, (classes, convs) in RECIPES.items())}
+# summaries-only fixtures (compare_summaries_to_golden): a second draw of the input -> the case whose model it is
+SECOND_DRAWS = {"v3_r50_ade_p1_2x96x128": "v3_r50_ade_2x96x128"}
 
 
-class _DS:
-    ignore_label = 255
-    num_classes = 19
-    class_weights = None
+def _DS(classes=19):
+    """What build_criterions reads of a dataset."""
+    return collections.namedtuple("_DS", "ignore_label num_classes class_weights")(255, classes, None)
 
 
-def build_model(name, backbone, align, device, criterion=True, deepsup=True):
+def build_model(name, backbone, align, device, criterion=True, deepsup=True, classes=19, backbone_para=BB):
     """The product Seg_Model `name` with the closed-form weights, in training mode on `device`."""
     from dcfp_amd import networks
     from dcfp_amd.loss.criterion import build_criterions
-    crit = build_criterions("ce", _DS(), {"ds_weight": 0.4}) if criterion else None
-    m = getattr(networks, name).Seg_Model(backbone=backbone, backbone_para=dict(BB), num_classes=19, align_corner=align,
-                                          criterion=crit, deepsup=deepsup)
+    crit = build_criterions("ce", _DS(classes), {"ds_weight": 0.4}) if criterion else None
+    m = getattr(networks, name).Seg_Model(backbone=backbone, backbone_para=dict(backbone_para), num_classes=classes,
+                                          align_corner=align, criterion=crit, deepsup=deepsup)
     m.load_state_dict(fill.closed_form_state(m.state_dict()))
     if deepsup:
         m.conv_deepsup[3].p = 0.0
     return m.to(device).train()
+
+
+def build_case_model(case, align, device, **kw):
+    """build_model with the class count and the backbone parameters of `case`."""
+    return build_model(case.model, case.backbone, align, device, classes=case.classes, backbone_para=case.backbone_para,
+                       **kw)
 
 
 class Golden:
@@ -74,6 +93,7 @@ class Golden:
         self.N, self.H, self.W, self.align = [int(v) for v in self.g["meta"]]
         self.logit_step = int(self.g["logit_step"]) if "logit_step" in self.g.files else 2
         self.variants = [str(v) for v in self.g["fp32_variants"]]
+        self.phase = float(self.g["phase"]) if "phase" in self.g.files else 0.0     # (fill.closed_form_input)
 
     def __getitem__(self, k):
         return self.g[k]
@@ -91,32 +111,24 @@ def load_golden(tag):
     return Golden(tag)
 
 
-def compare_to_golden(rec, gold, case, capsys=None):
-    """The acceptance of a whole-model run against its fixture.  rec: "loss"; "out_shapes" (both heads' full logits
-    shapes); "logits" / "logits_ds" at every gold.logit_step-th pixel; "bn_wgrad" / "bn_bgrad" (the BatchNorm gamma /
-    beta gradients concatenated in gold["bn_names"] order); "grad_l2" / "grad_proj" (per parameter of
-    gold["param_names"]: the gradient's L2 norm and its projection on cos(0.37 i)); "wgrad" {conv: weight gradient} for
-    case.convs; "rm" / "rv" {BatchNorm: running mean / var} for case.running.  All numpy / float."""
+def _rel_l2(g, what, mine):
+    # bounded by the reference's own fp32-vs-fp64 noise only (no fixed 5e-2 floor)
+    r32, r64 = g.f32(what), g.f64(what)
+    rel = np.linalg.norm(np.asarray(mine, dtype=np.float64) - r64) / np.linalg.norm(r64)
+    ref_rel = np.linalg.norm(r32 - r64) / np.linalg.norm(r64)
+    assert rel <= max(1e-3, 3 * ref_rel), (what, rel, ref_rel)
+
+
+def compare_summaries_to_golden(rec, gold, capsys=None):
+    """What a summaries-only fixture (a second draw of the input) holds, by the rules of compare_to_golden, which
+    starts with this: "loss", "bn_wgrad" / "bn_bgrad", "grad_l2" / "grad_proj"."""
     g = gold
     ref64, ref32 = float(g["loss64"]), float(g["loss32"])
     assert abs(rec["loss"] - ref64) <= max(1e-5 * abs(ref64), 3 * abs(ref32 - ref64)), (rec["loss"], ref32, ref64)
 
-    assert [tuple(s) for s in rec["out_shapes"]] == [(g.N, 19, g.H, g.W)] * 2, rec["out_shapes"]
-    for key in ("logits", "logits_ds"):
-        l64 = g.f32(key) + g[key + "_d64m32"]
-        err = np.abs(np.asarray(rec[key], dtype=np.float64) - l64).max()
-        ref_err = np.abs(g[key + "_d64m32"]).max()
-        assert err <= max(1e-3, 3 * ref_err), (key, err, ref_err)
-
-    def rel_l2(what, mine):
-        # bounded by the reference's own fp32-vs-fp64 noise only (no fixed 5e-2 floor)
-        r32, r64 = g.f32(what), g.f64(what)
-        rel = np.linalg.norm(np.asarray(mine, dtype=np.float64) - r64) / np.linalg.norm(r64)
-        ref_rel = np.linalg.norm(r32 - r64) / np.linalg.norm(r64)
-        assert rel <= max(1e-3, 3 * ref_rel), (what, rel, ref_rel)
     # BN gamma / beta gradients: the statistic that feeds the EIC score
     for what in ("bn_wgrad", "bn_bgrad"):
-        rel_l2(what, rec[what])
+        _rel_l2(g, what, rec[what])
 
     # every parameter gradient through its L2 norm (the fixture holds norms for all ~160-310 tensors).  The reference's
     # own fp32-vs-fp64 error of a tensor: the largest over its five fp32 summation orders (8 / 4 / 2 / 1 threads, oneDNN
@@ -134,8 +146,27 @@ def compare_to_golden(rec, gold, case, capsys=None):
     perr = np.abs(rec["grad_proj"] - p64) / (np.abs(l64) + 1e-12)
     pref = np.max([np.abs(g["grad_proj:" + v] - p64) for v in g.variants], axis=0) / (np.abs(l64) + 1e-12)
     check_rankwise(perr, pref, pn, f"{g.tag} gradient projections", capsys)     # (why rank-wise: tests/_parity.py)
+
+
+def compare_to_golden(rec, gold, case, capsys=None):
+    """The acceptance of a whole-model run against its fixture.  rec: "loss"; "out_shapes" (both heads' full logits
+    shapes); "logits" / "logits_ds" at every gold.logit_step-th pixel (case.eval_logits: and "logits_eval" /
+    "logits_eval_ds", the same of a model in eval mode); "bn_wgrad" / "bn_bgrad" (the BatchNorm gamma /
+    beta gradients concatenated in gold["bn_names"] order); "grad_l2" / "grad_proj" (per parameter of
+    gold["param_names"]: the gradient's L2 norm and its projection on cos(0.37 i)); "wgrad" {conv: weight gradient} for
+    case.convs; "bgrad" (the classifier's bias gradient); "rm" / "rv" {BatchNorm: running mean / var} for case.running.
+    All numpy / float."""
+    g = gold
+    compare_summaries_to_golden(rec, g, capsys)
+    assert [tuple(s) for s in rec["out_shapes"]] == [(g.N, case.classes, g.H, g.W)] * 2, rec["out_shapes"]
+    for key in ("logits", "logits_ds") + (("logits_eval", "logits_eval_ds") if case.eval_logits else ()):
+        l64 = g.f32(key) + g[key + "_d64m32"]
+        err = np.abs(np.asarray(rec[key], dtype=np.float64) - l64).max()
+        ref_err = np.abs(g[key + "_d64m32"]).max()
+        assert err <= max(1e-3, 3 * ref_err), (key, err, ref_err)
     for key in case.convs:
-        rel_l2(f"wgrad:{key}:", rec["wgrad"][key])
+        _rel_l2(g, f"wgrad:{key}:", rec["wgrad"][key])
+    _rel_l2(g, f"bgrad:{case.classifier}:", rec["bgrad"])
     for bn in case.running:
         for what in ("rm", "rv"):
             mine, r64 = np.asarray(rec[what][bn], dtype=np.float64), g[f"{what}:{bn}:64"]
@@ -146,18 +177,16 @@ def compare_to_golden(rec, gold, case, capsys=None):
                 assert err < 1e-5, (bn, what, err)
 
 
-def collect_record(model, fresh_model, x, lab, gold, case):
-    """The GPU half: one training-mode forward + backward of `model`, and the logits of `fresh_model` (an identical
-    model, so that the BatchNorm running statistics match the fixture's) -> the record compare_to_golden takes."""
+def _sub(t, s):
+    return t[:, :, ::s, ::s].double().cpu().numpy()
+
+
+def collect_summaries(model, x, lab, gold):
+    """One training-mode forward + backward of `model` -> the record compare_summaries_to_golden takes."""
     loss = model(x, lab, deepsup=True)["loss"]
     loss.backward()
     torch.cuda.synchronize()
-    with torch.no_grad():
-        outs = fresh_model(x, None, deepsup=True)
-    s = gold.logit_step
-    rec = {"loss": loss.item(), "out_shapes": [tuple(o.shape) for o in outs[:2]],
-           "logits": outs[0][:, :, ::s, ::s].double().cpu().numpy(),
-           "logits_ds": outs[1][:, :, ::s, ::s].double().cpu().numpy()}
+    rec = {"loss": loss.item()}
     mods = dict(model.named_modules())
     for what, attr in (("bn_wgrad", "weight"), ("bn_bgrad", "bias")):
         rec[what] = torch.cat([getattr(mods[n], attr).grad.reshape(-1)
@@ -167,20 +196,64 @@ def collect_record(model, fresh_model, x, lab, gold, case):
     rec["grad_l2"] = np.array([float(params[k].grad.double().norm()) for k in pn])
     rec["grad_proj"] = np.array([float((params[k].grad.double().reshape(-1) * torch.cos(
         0.37 * torch.arange(params[k].numel(), dtype=torch.float64, device=x.device))).sum()) for k in pn])
+    return rec
+
+
+def collect_record(model, fresh_model, x, lab, gold, case, eval_model=None):
+    """The GPU half: one training-mode forward + backward of `model`, the logits of `fresh_model` (an identical
+    model, so that the BatchNorm running statistics match the fixture's) and, for a case with eval_logits, those of
+    `eval_model` (a third one, in eval mode: the inference epilogues) -> the record compare_to_golden takes."""
+    rec = collect_summaries(model, x, lab, gold)
+    with torch.no_grad():
+        outs = fresh_model(x, None, deepsup=True)
+    s = gold.logit_step
+    rec.update(out_shapes=[tuple(o.shape) for o in outs[:2]], logits=_sub(outs[0], s), logits_ds=_sub(outs[1], s))
+    if case.eval_logits:
+        assert not eval_model.training
+        with torch.no_grad():
+            outs = eval_model(x, None, deepsup=True)
+        rec.update(logits_eval=_sub(outs[0], s), logits_eval_ds=_sub(outs[1], s))
+    params = dict(model.named_parameters())
     rec["wgrad"] = {k: params[k + ".weight"].grad.double().cpu().numpy() for k in case.convs}
+    rec["bgrad"] = params[case.classifier + ".bias"].grad.double().cpu().numpy()
     sd = model.state_dict()
     rec["rm"] = {bn: sd[bn + ".running_mean"].double().cpu().numpy() for bn in case.running}
     rec["rv"] = {bn: sd[bn + ".running_var"].double().cpu().numpy() for bn in case.running}
     return rec
 
 
-def forward_backward_vs_golden(tag, device, capsys):
-    """test_forward_backward_vs_reference_golden of every head."""
+def golden_inputs(gold, classes, device):
+    x = fill.closed_form_input(gold.N, gold.H, gold.W, phase=gold.phase).to(device)
+    return x, fill.closed_form_labels(gold.N, gold.H, gold.W, num_classes=classes).to(device)
+
+
+def golden_record(tag, device, align=None, backbone_para=None, before=None):
+    """The product model of the case `tag` run on its fixture's inputs -> (record, fixture, case).  align /
+    backbone_para: build the model with these instead of the fixture's align_corner / the case's backbone parameters
+    (another recipe, which the fixture must reject); before(model): the test's own assertions on the model about to run."""
     case, gold = CASES[tag], load_golden(tag)
-    x = fill.closed_form_input(gold.N, gold.H, gold.W).to(device)
-    lab = fill.closed_form_labels(gold.N, gold.H, gold.W).to(device)
-    m, m2 = (build_model(case.model, case.backbone, bool(gold.align), device) for _ in range(2))
-    compare_to_golden(collect_record(m, m2, x, lab, gold, case), gold, case, capsys)
+    x, lab = golden_inputs(gold, case.classes, device)
+    built = case if backbone_para is None else case._replace(backbone_para=backbone_para)
+    align = bool(gold.align) if align is None else align
+    m, m2 = (build_case_model(built, align, device) for _ in range(2))
+    m3 = build_case_model(built, align, device).eval() if case.eval_logits else None
+    if before is not None:
+        before(m)
+    return collect_record(m, m2, x, lab, gold, case, m3), gold, case
+
+
+def forward_backward_vs_golden(tag, device, capsys, before=None):
+    """test_forward_backward_vs_reference_golden of every head."""
+    rec, gold, case = golden_record(tag, device, before=before)
+    compare_to_golden(rec, gold, case, capsys)
+
+
+def second_draw_vs_golden(tag, device, capsys):
+    """test_second_input_draw: the model of the case SECOND_DRAWS[tag] on the fixture's other draw of the input."""
+    case, gold = CASES[SECOND_DRAWS[tag]], load_golden(tag)
+    x, lab = golden_inputs(gold, case.classes, device)
+    m = build_case_model(case, bool(gold.align), device)
+    compare_summaries_to_golden(collect_summaries(m, x, lab, gold), gold, capsys)
 
 
 def _prune_gp50(m, score_path):
@@ -316,7 +389,7 @@ def module_tree_check(tag):
     """Module tree, state_dict, ignore_prune_layer, parameter and BatchNorm names against the whole-model fixture.
     Returns (model, fixture) for the head's own assertions."""
     g = np.load(os.path.join(G, f"model_{tag}.npz"))
-    m = host_model(CASES[tag].model)
+    m = build_case_model(CASES[tag], True, torch.device("cpu"), criterion=False)
     sd = m.state_dict()
     assert list(sd.keys()) == g["state_keys"].tolist()
     assert [str(tuple(v.shape)) for v in sd.values()] == g["state_shapes"].tolist()

@@ -1,6 +1,7 @@
 """CPU: the oracle (oracle/, a restatement of the reference's algorithm) against golden vectors
 produced by importing the real reference (oracle/make_golden.py).  This is what pins the
 oracle; the GPU tests then compare the HIP path with the oracle."""
+import json
 import os
 
 import numpy as np
@@ -46,22 +47,30 @@ def test_ohem_threshold():
 
 
 MODELS = [("simple_r50_4x64x64", "simple", "resnet50"), ("v3_r50_2x65x65", "deeplabv3", "resnet50"),
-          ("v3_r101_2x65x65", "deeplabv3", "resnet101")]
+          ("v3_r101_2x65x65", "deeplabv3", "resnet101")] + \
+    [(f"v3_r50_{key}_2x96x128", "deeplabv3", "resnet50") for key in ("ade", "coco", "ctx")]     # the other recipes
+BB = {"os": 8, "mg_unit": [1, 2, 4], "inplanes": 128, "pretrained": False}
 
 
-def product_state(model_name, backbone, align):
+def recipe(g):
+    """(classes, backbone parameters) a whole-model fixture was made with: Cityscapes' where it does not say"""
+    if "num_classes" not in g.files:
+        return 19, BB
+    return int(g["num_classes"]), json.loads(str(g["backbone_para"]))
+
+
+def product_state(model_name, backbone, align, classes=19, backbone_para=BB):
     """state_dict (names/shapes) of the product module tree, closed-form filled."""
     from dcfp_amd import networks
     m = getattr(networks, model_name).Seg_Model(
-        backbone=backbone, backbone_para={"os": 8, "mg_unit": [1, 2, 4], "inplanes": 128, "pretrained": False},
-        num_classes=19, align_corner=align, deepsup=True)
+        backbone=backbone, backbone_para=dict(backbone_para), num_classes=classes, align_corner=align, deepsup=True)
     return m, fill.closed_form_state(m.state_dict())
 
 
 @pytest.mark.parametrize("tag,model_name,backbone", MODELS)
 def test_state_dict_contract(tag, model_name, backbone):
     g = _load(f"model_{tag}.npz")
-    m, sd = product_state(model_name, backbone, bool(g["meta"][3]))
+    m, sd = product_state(model_name, backbone, bool(g["meta"][3]), *recipe(g))
     assert list(sd.keys()) == list(g["state_keys"])
     assert [str(tuple(v.shape)) for v in sd.values()] == list(g["state_shapes"])
     assert m.ignore_prune_layer == list(g["ignore_prune_layer"])
@@ -69,30 +78,61 @@ def test_state_dict_contract(tag, model_name, backbone):
 
 @pytest.mark.parametrize("tag,model_name,backbone", MODELS)
 def test_oracle_model_matches_reference(tag, model_name, backbone):
+    """The three oldest fixtures: the oracle in fp32 against the reference's fp32 run - the same ATen CPU ops, which
+    agree far below the fp32-vs-fp64 noise floor where the CPU libraries block their sums alike.  They do not on every
+    host (another cache hierarchy, another vendor path of the BLAS: 1.6e-4 ... 3.7e-4 on these logits, 0.3 ... 0.5 of
+    the noise), and one fp32 fixture cannot be right for two hosts.  So the recipe fixtures are compared in fp64, the
+    oracle's against the reference's: the same bounds, which one algorithm then meets on any host by orders of
+    magnitude and another one does not; the oracle's fp32 run is held to that fp64 by the rule of the HIP build
+    (tests/_model_cases.py: max(1e-3, 3 x the reference's own fp32-vs-fp64 distance))."""
     g = _load(f"model_{tag}.npz")
     N, H, W, align = [int(v) for v in g["meta"]]
-    _, sd0 = product_state(model_name, backbone, bool(align))
-    cfg = omodel.Cfg(model=model_name, backbone=backbone, align_corner=bool(align))
-    sd = omodel.clone_state(sd0)
-    x, lab = fill.closed_form_input(N, H, W), fill.closed_form_labels(N, H, W)
+    classes, bb = recipe(g)
+    step = int(g["logit_step"]) if "logit_step" in g.files else 2
+    in64 = "num_classes" in g.files
+    dtype, sfx = (torch.float64, "64") if in64 else (torch.float32, "32")
+
+    def ref(k, sep=""):
+        """the reference's array k in the precision compared (the later fixtures hold fp64 as a float32 difference)"""
+        if not in64 or k + "64" in g.files:
+            return g[k + sfx]
+        return g[k + "32"].astype(np.float64) + g[k + sep + "d64m32"]
+    _, sd0 = product_state(model_name, backbone, bool(align), classes, bb)
+    cfg = omodel.Cfg(model=model_name, backbone=backbone, os=bb["os"], mg_unit=bb["mg_unit"], align_corner=bool(align))
+    sd = omodel.clone_state(sd0, dtype=dtype)
+    x, lab = fill.closed_form_input(N, H, W, dtype), fill.closed_form_labels(N, H, W, num_classes=classes)
     outs, loss, _ = omodel.seg_forward(sd, x, cfg, lab, training=True)
     loss.backward()
-    # same ATen CPU ops as the reference: agreement far below the fp32-vs-fp64 noise floor
     noise = np.abs(g["logits_d64m32"]).max()
-    d = np.abs(outs[0][:, :, ::2, ::2].detach().numpy() - g["logits32"]).max()
-    dds = np.abs(outs[1][:, :, ::2, ::2].detach().numpy() - g["logits_ds32"]).max()
+    assert outs[0].shape == outs[1].shape == (N, classes, H, W)
+    d = np.abs(outs[0][:, :, ::step, ::step].detach().numpy() - ref("logits", "_")).max()
+    dds = np.abs(outs[1][:, :, ::step, ::step].detach().numpy() - ref("logits_ds", "_")).max()
     assert d <= max(1e-5, 0.1 * noise) and dds <= max(1e-5, 0.1 * noise), (d, dds, noise)
-    assert abs(float(loss) - float(g["loss32"])) < 2e-6
+    assert abs(float(loss) - float(g["loss" + sfx])) < 2e-6
     bn_w = torch.cat([sd[n + ".weight"].grad.reshape(-1) for n in g["bn_names"]]).numpy()
-    ref = g["bn_wgrad32"]
-    rel = np.linalg.norm(bn_w - ref) / np.linalg.norm(ref)
-    noise_rel = np.linalg.norm(g["bn_wgrad64"] - ref) / np.linalg.norm(g["bn_wgrad64"])
+    r32, r64 = g["bn_wgrad32"].astype(np.float64), (ref("bn_wgrad") if in64 else g["bn_wgrad64"])
+    rel = np.linalg.norm(bn_w - ref("bn_wgrad")) / np.linalg.norm(ref("bn_wgrad"))
+    noise_rel = np.linalg.norm(r64 - r32) / np.linalg.norm(r64)
     assert rel <= max(1e-4, 0.5 * noise_rel), (rel, noise_rel)
-    for key in ("backbone.conv1.0", "backbone.layer2.0.conv2", "last_conv.6"):
-        a = sd[key + ".weight"].grad.numpy(); b = g[f"wgrad:{key}:32"]
+    stored = [k for k in ("backbone.conv1.0", "backbone.layer2.0.conv2", "conv_deepsup.4", "last_conv.6")
+              if f"wgrad:{k}:32" in g.files]
+    assert len(stored) >= 2 and stored[-1] == "last_conv.6"
+    for key in stored:
+        a = sd[key + ".weight"].grad.numpy(); b = ref(f"wgrad:{key}:")
         assert np.linalg.norm(a - b) / np.linalg.norm(b) < 1e-3, key
-    assert np.abs(sd["backbone.bn1.running_mean"].numpy() - g["rm:backbone.bn1:32"]).max() < 1e-6
-    assert np.abs(sd["backbone.bn1.running_var"].numpy() - g["rv:backbone.bn1:32"]).max() < 1e-6
+    assert np.abs(sd["backbone.bn1.running_mean"].numpy() - ref("rm:backbone.bn1:")).max() < 1e-6
+    assert np.abs(sd["backbone.bn1.running_var"].numpy() - ref("rv:backbone.bn1:")).max() < 1e-6
+    if in64:
+        with torch.no_grad():
+            outs32, loss32, _ = omodel.seg_forward(omodel.clone_state(sd0, requires_grad=False),
+                                                   fill.closed_form_input(N, H, W), cfg, lab, training=True)
+        l64, l32 = float(g["loss64"]), float(g["loss32"])
+        assert abs(float(loss32) - l64) <= max(1e-5 * abs(l64), 3 * abs(l32 - l64)), (float(loss32), l32, l64)
+        for o, k in zip(outs32, ("logits", "logits_ds")):
+            err = np.abs(o[:, :, ::step, ::step].double().numpy() - ref(k, "_")).max()
+            assert err <= max(1e-3, 3 * np.abs(g[k + "_d64m32"]).max()), (k, err)
+        print(f"[{tag}] oracle fp64 vs reference fp64: logits {d:.1e} / {dds:.1e} (bound {max(1e-5, 0.1 * noise):.1e}), "
+              f"loss {abs(float(loss) - l64):.1e}, bn gamma gradients rel {rel:.1e}")
 
 
 @pytest.mark.parametrize("tag,model_name,backbone,align,gp",
