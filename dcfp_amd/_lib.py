@@ -147,6 +147,7 @@ SIGNATURES = {
     "dcfp_conv2d_pitch_supported": (_I, [_D]),
     "dcfp_conv2d_kernel_name": (_I, [_D, _I, C.c_char_p, _I]),
     "dcfp_conv2d_executed_fraction": (C.c_double, [_D, _I]),
+    "dcfp_wino_tile_plan": (_I, [_I, _I, _I, _I, _I, _I, C.POINTER(C.c_int64)]),
     "dcfp_conv2d_workspace_is_scratch": (_I, [_D, _I]),
     "dcfp_conv2d_dgrad_fanin_supported": (_I, [_D]),
     "dcfp_conv2d_dgrad_fanin_f32_nchw": (_I, [_D, _P, _L, _P, _P, _P, _P, _P, _Z, _I, _P]),

@@ -179,6 +179,7 @@ int dcfp_igemm3_run(const GemmProblem& g, const float* in, const float* w, float
 bool dcfp_wino_ok(const WinoProblem& q);
 size_t dcfp_wino_workspace_bytes(const WinoProblem& q);
 double dcfp_wino_exec_fraction(const WinoProblem& q);
+double dcfp_wino_grid_fraction(const WinoProblem& q);
 long long dcfp_wino_stat_slots(const WinoProblem& q);
 size_t dcfp_wino_xform_bytes(const WinoProblem& q);
 int dcfp_wino_run(const GemmProblem& g, const float* in, const float* w, float* out, void* workspace, size_t workspace_bytes,

@@ -14,6 +14,7 @@
 // gemm_problem (conv_dispatch.h) is the one place that writes this table out; every entry point and query below works on
 // the GemmProblem it returns.
 #include "conv_dispatch.h"
+#include "wino_plan.h"
 #include <stdio.h>
 
 extern "C" int dcfp_abi_version(void) { return 2; }
@@ -45,7 +46,7 @@ static int wino_kind(const DcfpConvDesc* d, int pass) {
     // (channel counts off the 256 grid - pruned models, the narrow layers - run the ragged-M / register-staged direct
     //  kernels: 100...127 TF measured)
     const double t_direct = nominal * f_direct / (M % 256 != 0 ? 115e12 : 143e12);
-    const double f_wino = dcfp_wino_exec_fraction(q);
+    const double f_wino = dcfp_wino_grid_fraction(q);
     double t_wino = 1e30;
     if (three) {
         const double tiles = f_wino * 9.0 / 16.0 * d->N * (double)d->H * d->W;          // T
@@ -138,9 +139,28 @@ extern "C" double dcfp_conv2d_executed_fraction(const DcfpConvDesc* d, int pass)
     if (check_desc(d) != DCFP_OK) return 1.0;
     if (pass == DCFP_CONV_WGRAD) return dcfp_wgrad_exec_fraction(d);
     const GemmProblem g = gemm_problem(d, pass, 0);
+    // (Winograd: the enumerated tiles at 16 components each.  The 12- and 9-component classes of the fused forward / dgrad
+    //  kernel are not subtracted - dcfp_wino_tile_plan reports the issued components exactly)
     if (wino_pass(d, pass)) return dcfp_wino_exec_fraction(wino_problem(g));
     if (igemm3_ok(g)) return 1.0;
     return dcfp_igemm2_exec_fraction(g);
+}
+
+// The tile plan of the Winograd paths (wino_plan.h) for an N x H x W map with dilation d.  ragged: 0 the full grid of
+// super-blocks, 1 the valid tiles only, -1 as DCFP_WINO_RAGGED selects; classes: cut the grid into component classes
+// (the fused forward / dgrad kernel).  out[0..5] = TH, TW, T, T16, regions, 64-tile blocks; then 8 values per region
+// (four slots): r0, nr, c0, nc, rows3, cols3, first block, blocks; out[38] = components issued over all tiles.
+extern "C" int dcfp_wino_tile_plan(int N, int H, int W, int d, int ragged, int classes, int64_t* out) {
+    if (N <= 0 || H <= 0 || W <= 0 || d <= 0 || !out) return DCFP_E_BADDESC;
+    const WinoTilePlan pl = wino_tile_plan(N, H, W, d, ragged < 0 ? wino_ragged_on() : ragged != 0, classes != 0);
+    out[0] = pl.TH; out[1] = pl.TW; out[2] = pl.T; out[3] = pl.T16; out[4] = pl.nreg; out[5] = pl.tblocks;
+    for (int i = 0; i < pl.nreg; ++i) {
+        const WinoRegion& r = pl.reg[i];
+        int64_t* o = out + 6 + 8 * i;
+        o[0] = r.r0; o[1] = r.nr; o[2] = r.c0; o[3] = r.nc; o[4] = r.rows3; o[5] = r.cols3; o[6] = r.tb0; o[7] = r.nblocks;
+    }
+    out[38] = pl.issued;
+    return DCFP_OK;
 }
 
 // Bytes of the transformed input (Winograd V, conv_winograd.hip) that the forward pass of this conv can write into a

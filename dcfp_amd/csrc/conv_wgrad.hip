@@ -1021,8 +1021,8 @@ static bool wino_wgrad_fused_forced() { return wino_wgrad_fused_mode() == 2; }
 // passes at 4.2 / 5 TB/s; fused Winograd (kind 2, conv_winograd3.hip) = the same products on 64 x 64-channel blocks at the
 // rate of its K loop, no passes - the only Winograd weight gradient below 128 channels (stem, layer1, layer2, pruned widths).
 // Returns 0 (direct kernels), 1 or 2.  DCFP_CONV_WINOGRAD: 0 off, 1 model (default), 2 wherever eligible.
-static double wino_fraction(const DcfpConvDesc* d) {      // (the forward's tiling: M = Cout, Ck = Cin)
-    return dcfp_wino_exec_fraction(wino_problem(gemm_problem(d, DCFP_CONV_FWD, 0)));
+static double wino_fraction(const DcfpConvDesc* d) {      // (the forward's tiling: M = Cout, Ck = Cin; the full grid)
+    return dcfp_wino_grid_fraction(wino_problem(gemm_problem(d, DCFP_CONV_FWD, 0)));
 }
 static int wino_wgrad_kind(const DcfpConvDesc* d) {
     const int mode = conv_winograd_mode();
@@ -1065,7 +1065,7 @@ bool dcfp_wgrad_wants_xform(const DcfpConvDesc* d) { return wino_wgrad_kind(d) =
 
 // share of the nominal multiply-adds issued (the direct kernels execute every K-step: a tile of dW mixes all nine taps)
 double dcfp_wgrad_exec_fraction(const DcfpConvDesc* d) {
-    return wino_wgrad_pass(d) ? wino_fraction(d) : 1.0;
+    return wino_wgrad_pass(d) ? dcfp_wino_exec_fraction(wino_problem(gemm_problem(d, DCFP_CONV_FWD, 0))) : 1.0;
 }
 
 extern "C" size_t dcfp_conv2d_workspace_bytes(const DcfpConvDesc* d, int pass) {

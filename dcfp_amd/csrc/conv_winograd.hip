@@ -18,6 +18,7 @@
 // tcol = j * d + b, so that consecutive tiles read / write consecutive pixels (runs of d).
 #include "igemm2_common.h"
 #include "conv_dispatch.h"
+#include "wino_plan.h"
 
 namespace {
 
@@ -34,11 +35,9 @@ struct WinoPlan {
 
 WinoPlan wino_plan(int N, int H, int W, int d, int M, int Ck) {
     WinoPlan pl;
-    pl.TH = d * ((H + 2 * d - 1) / (2 * d));
-    pl.TW = d * ((W + 2 * d - 1) / (2 * d));
-    pl.TW = (pl.TW + 3) / 4 * 4;                  // GEMM rows of 16-byte quads (the extra tiles have no outputs)
-    pl.T = (long long)N * pl.TH * pl.TW;
-    pl.T16 = (pl.T + 15) / 16 * 16;
+    const WinoTilePlan tp = wino_tile_plan(N, H, W, d, wino_ragged_on(), false);    // (wino_plan.h: the valid tiles only)
+    pl.TH = tp.TH; pl.TW = tp.TW;                 // TW: GEMM rows of 16-byte quads (the extra tiles have no outputs)
+    pl.T = tp.T; pl.T16 = tp.T16;
     pl.CkP = (Ck + dcfp_igemm2_ck_pad() - 1) / dcfp_igemm2_ck_pad() * dcfp_igemm2_ck_pad();
     pl.Mpad = (M + 255) / 256 * 256;
     pl.u_floats = align64(16LL * pl.CkP * pl.Mpad);
@@ -434,7 +433,8 @@ bool dcfp_wino_ok(const WinoProblem& q) {
     if (!dcfp_igemm2_persist()) return false;
     if (q.M < 129 || q.Ck < 128) return false;     // the transforms cost ~ 1/M + 1/Ck of the GEMM (the cost model decides)
     const WinoPlan pl = wino_plan(q);
-    if (4 * pl.T > (long long)q.N * q.H * q.W * 27 / 20) return false;  // > 35 % padding of the 2d x 2d super-blocks
+    // > 35 % padding of the 2d x 2d super-blocks (the full grid, whatever the plan enumerates: routing is unchanged)
+    if (4 * wino_tile_plan(q.N, q.H, q.W, q.d, false, false).T > (long long)q.N * q.H * q.W * 27 / 20) return false;
     if (pl.T16 >= (1LL << 26) || 16LL * pl.T16 >= (1LL << 30)) return false;
     if ((long long)q.Ck * pl.T16 >= (1LL << 29) || (long long)q.M * pl.T16 >= (1LL << 29)) return false;
     // (ragged M - pruned models - runs on the persistent kernel's edge tiles: the batched GEMM never takes the
@@ -451,6 +451,12 @@ size_t dcfp_wino_workspace_bytes(const WinoProblem& q) {
 double dcfp_wino_exec_fraction(const WinoProblem& q) {
     const WinoPlan pl = wino_plan(q);
     return 16.0 * (double)pl.T / (9.0 * (double)q.N * q.H * q.W);
+}
+// ... and of the full grid of super-blocks with 16 components per tile: what the cost models (conv_igemm.hip,
+// conv_wgrad.hip) price a Winograd pass with - their rates were measured against it, and the routing of a conv does not
+// depend on DCFP_WINO_RAGGED
+double dcfp_wino_grid_fraction(const WinoProblem& q) {
+    return 16.0 * (double)wino_tile_plan(q.N, q.H, q.W, q.d, false, false).T / (9.0 * (double)q.N * q.H * q.W);
 }
 
 // Partials (of 128 outputs each) per channel that the output transform can emit for the BatchNorm behind the conv; 0 where
@@ -551,7 +557,7 @@ WinoWgradPlan wino_wgrad_plan(int N, int H, int W, int d, int M, int C) {
 bool dcfp_wino_wgrad_ok(int N, int H, int W, int d, int M, int C) {
     if (M < 128 || C < 128) return false;
     const WinoWgradPlan w = wino_wgrad_plan(N, H, W, d, M, C);
-    if (4 * w.pl.T > (long long)N * H * W * 27 / 20) return false;
+    if (4 * wino_tile_plan(N, H, W, d, false, false).T > (long long)N * H * W * 27 / 20) return false;
     if (w.T16 >= (1LL << 30) || (long long)M * w.T16 >= (1LL << 29) || (long long)C * w.T16 >= (1LL << 29)) return false;
     return M <= 65535 && C <= 65535;
 }

@@ -25,6 +25,7 @@
 // conv_winograd.hip: V written on the side is bit-identical to wino_input_kernel's.
 #include "wino_patch.h"
 #include "conv_dispatch.h"
+#include "wino_plan.h"
 #include <stdlib.h>
 
 namespace {
@@ -48,8 +49,10 @@ struct WinoFusedParams {
     const float* shift;     // BatchNorm folded into the conv (dcfp_conv2d_fwd_fused_f32_nchw)
     const float* residual;  // laid out as out
     int relu;
-    int N, M, Ck, H, W, d, TH, TW;
-    long long T, T16;
+    int N, M, Ck, H, W, d;
+    long long T16;          // row length of V (xform_out; one region then: a tile's index there is its number)
+    // the tile regions of the launch (wino_plan.h), the 16-component one first; tb0 = 0x7fffffff past the last one
+    struct Region { int tb0, r0, nr, c0, nc, cls; long long tiles; } reg[4];     // cls: bit 0 rows3, bit 1 cols3
     int mblocks, tblocks, nk;
     int accumulate;
     int ragged_c;           // Ck % 16 != 0
@@ -61,20 +64,52 @@ struct WinoFusedParams {
 // The K loop is ONE basic block (no branch around the MFMAs: with the accumulators live across a diamond hipcc 7.2 moves
 // all 256 of them through VGPRs / scratch every iteration): conditional work is expressed through buffer offsets - an
 // out-of-range offset makes a load return zeros and drops a store.
-template <int DM, bool SIDE, bool RAGGED>
-__global__ void __launch_bounds__(256, 1) wino_fused_kernel(const WinoFusedParams p) {
+//
+// R3 / S3: the component set of the block's tiles.  A tile whose second output row (column) lies outside the image never
+// uses the row (column) components r = 3 (s = 3): the launcher groups such tiles into regions of their own (wino_plan.h)
+// and their blocks run 12 or 9 slots per K-step instead of 16 - no slot, LDS-DMA piece of Ug, column transform, LDS write
+// or patch load exists for an inactive component, and row transform 3 goes with r = 3.  The active components keep their
+// operations and their order: the outputs inside the image are bit-identical to the 16-component run.
+// The k-th active component is xi = 4 (k / NCOLS) + k % NCOLS.
+template <int DM, bool R3, bool S3> __device__ __forceinline__ constexpr bool patch_load_on(int I) {
+    if (DM == 4) return (R3 || (I >> 2) != 3) && (S3 || (I & 3) != 3);     // load I: patch row I / 4, patch column I % 4
+    return R3 || (I >> 1) != 3;                                               // two loads per patch row, all columns
+}
+template <int DM, bool R3, bool S3> __device__ __forceinline__ constexpr int patch_loads() {
+    int n = 0;
+    for (int i = 0; i < PatchCfg<DM>::NV; ++i) n += patch_load_on<DM, R3, S3>(i) ? 1 : 0;
+    return n;
+}
+template <int DM, bool R3, bool S3> __device__ __forceinline__ constexpr int patch_load_nth(int j) {   // the j-th active load
+    for (int i = 0; i < PatchCfg<DM>::NV; ++i)
+        if (patch_load_on<DM, R3, S3>(i) && j-- == 0) return i;
+    return 0;
+}
+
+template <int DM, bool SIDE, bool RAGGED, bool R3, bool S3>
+__device__ __forceinline__ void wino_fused_body(const WinoFusedParams& p, const int mb, const int tb, const int tb0,
+                                                int r0, int nr, int c0, int nc, const long long rtiles) {
+    // (the region and the thread index as THIS body's own values: otherwise hipcc hoists what the four bodies of a kernel
+    //  have in common - the tile decode, lane offsets - above their dispatch and keeps it alive, in scratch, under the K loop)
+    int tid = threadIdx.x;
+    asm volatile("" : "+s"(r0), "+s"(nr), "+s"(c0), "+s"(nc), "+v"(tid));
+    static_assert(!SIDE || (R3 && S3), "V is kept with all 16 components");
     constexpr int NV = PatchCfg<DM>::NV;
+    constexpr int NROWS = R3 ? 4 : 3, NCOLS = S3 ? 4 : 3, NC = NROWS * NCOLS;      // slots of a K-step: 16 / 12 / 9
+    // LDS-DMA pieces of Ug (1 KB: half a component) per wave.  All columns active: the active components are xi = 0 .. NC - 1,
+    // 2 NC consecutive pieces, a quarter per wave.  Without s = 3: the 6 pieces 8 r .. 8 r + 5 of row r, one row per wave
+    // (three rows: wave 3 copies row 2 once more - the same bytes to the same place).  Either way a wave's pieces are
+    // consecutive: one scalar base, constant offsets.
+    constexpr int PW = S3 ? NC / 2 : 6;
+    constexpr int LS = NC == 16 ? 8 : NC == 12 ? 6 : 3, L0 = NC - LS;       // the last LS slots carry the patch loads
+    constexpr int NVA = patch_loads<DM, R3, S3>();
+    static_assert(PW <= L0 && NROWS <= L0, "patch loads are issued behind the last LDS-DMA piece and the row transform");
     extern __shared__ __attribute__((aligned(16))) float smem[];   // [2 stages][A 8192 | B 8192]
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, wm = wid >> 1, wn = wid & 1;
+    const int lane = tid & 63, wid = tid >> 6, wm = wid >> 1, wn = wid & 1;
     const int l31 = lane & 31, lhi = lane >> 5;
     const int wid_s = __builtin_amdgcn_readfirstlane(wid);
-    // blocks b, b + 8, ... share an XCD (round-robin placement): the mblocks blocks of one tile block sit next to each
-    // other there, so the patches they all read are served by that XCD's L2
-    const int xcd = blockIdx.x & 7, jb = blockIdx.x >> 3;
-    const int mb = jb % p.mblocks, tb = (jb / p.mblocks) * 8 + xcd;
-    if (tb >= p.tblocks) return;                                   // block-uniform
-    const long long t0 = (long long)tb * 64;
-    const int nk = p.nk, d = p.d, H = p.H, W = p.W, TW = p.TW, tpi = p.TH * p.TW, pitch = p.pitch;
+    const long long t0 = (long long)(tb - tb0) * 64;               // first tile of the block, counted inside its region
+    const int nk = p.nk, d = p.d, H = p.H, W = p.W, tpi = nr * nc, pitch = p.pitch;
 
     const unsigned lds0 = (unsigned)(size_t)(lds_ptr)smem;
     const u32x4 a_desc = make_desc(p.ug, 0x7ffffffcu);
@@ -85,10 +120,10 @@ __global__ void __launch_bounds__(256, 1) wino_fused_kernel(const WinoFusedParam
     const long long tp = t0 + 2 * l31;
     unsigned voff[NV];
     {
-        const bool tvalid = tp < p.T;
+        const bool tvalid = tp < rtiles;
         const long long tq = tvalid ? tp : 0;
         const int n = (int)(tq / tpi), tt = (int)(tq - (long long)n * tpi);
-        const int trow = tt / TW, tcol = tt - trow * TW;
+        const int trow = r0 + tt / nc, tcol = c0 + tt % nc;
         const int h0 = trow + d * (trow / d) - d, w0 = tcol + d * (tcol / d) - d;
         const long long base = (long long)n * p.in_nstride + (long long)lhi * H * pitch + p.lead;
 #pragma unroll
@@ -114,25 +149,28 @@ __global__ void __launch_bounds__(256, 1) wino_fused_kernel(const WinoFusedParam
                                                                              p.in_bytes, 0x00020000);
     const unsigned chan_bytes = (unsigned)(H * pitch) * 4u;
     // patches of K-step j live in R[j & 1]: loaded during step j - 3 (slots 8..15), consumed during step j - 1 (slots 0..3)
-    float R[2][4][8], q[4][8];
+    // (the patch rows / columns of inactive components are never loaded: they lie outside the image, and nothing reads them)
+    float R[2][4][8] = {}, q[4][8] = {};
     auto load_step = [&](int kt, auto b_) {          // patches of K-step kt -> R[b]
         constexpr int b = decltype(b_)::value;
         const unsigned soff = __builtin_amdgcn_readfirstlane((unsigned)(kt * FBK + 2 * wid_s) * chan_bytes);
+        unsigned vm[NV];
+#pragma unroll
+        for (int i = 0; i < NV; ++i) vm[i] = voff[i];
         if constexpr (RAGGED) {
-            unsigned vm[NV];
             const bool cok = kt * FBK + ch < p.Ck;
 #pragma unroll
             for (int i = 0; i < NV; ++i) vm[i] = cok ? voff[i] : kOob;
-            load_patches<DM>(in_rsrc, vm, soff, R[b]);
-        } else {
-            load_patches<DM>(in_rsrc, voff, soff, R[b]);
         }
+        static_for<0, NVA>([&](auto j_) { load_one<DM, patch_load_nth<DM, R3, S3>(decltype(j_)::value)>(in_rsrc, vm, soff, R[b]); });
     };
-    auto issue_a = [&](int kt, int buf) {   // the 32 KB A image of K-step kt: 8 of its 32 one-KB pieces per wave
+    // first of this wave's PW pieces (piece 2 xi + half, in the A image of a K-step - global and LDS alike)
+    const int piece0 = S3 ? wid_s * PW : 8 * (wid_s < NROWS - 1 ? wid_s : NROWS - 1);
+    auto issue_a = [&](int kt, int buf) {   // the A image of K-step kt: PW of its one-KB pieces per wave
         const unsigned abase = (unsigned)((kt * p.mblocks + mb) * FSTAGE) * 4u;
-        static_for<0, 8>([&](auto q_) {
+        static_for<0, PW>([&](auto q_) {
             constexpr int qq = decltype(q_)::value;
-            const unsigned piece = (unsigned)(wid_s * 8 + qq);
+            const unsigned piece = (unsigned)(piece0 + qq);
             const unsigned la = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(buf * 2 * FSTAGE) * 4u + piece * 1024u);
             const unsigned a_s = __builtin_amdgcn_readfirstlane(abase + piece * 1024u);
             const unsigned av = lane16;
@@ -145,18 +183,13 @@ __global__ void __launch_bounds__(256, 1) wino_fused_kernel(const WinoFusedParam
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
     };
-    // end of a K-step of the loop: everything but the NV youngest vector-memory operations has landed - those are the patch
-    // loads issued in slots 8..15 (behind the last LDS-DMA piece), which have another whole step to arrive
+    // end of a K-step of the loop: everything but the NVA youngest vector-memory operations has landed - those are the patch
+    // loads issued in the last LS slots (behind the last LDS-DMA piece), which have another whole step to arrive
     // (SIDE: a step that stores V issues its 16 stores in slots 8..15 too, behind the last LDS-DMA piece: 16 more
     //  operations may stay in flight.  The branches around the stores and between the two waits are scalar and hold no MFMA.)
     auto retire_keep_loads = [&](bool stored) {
-        if (SIDE && stored) {
-            if constexpr (NV == 8) asm volatile("s_waitcnt vmcnt(24) lgkmcnt(0)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(32) lgkmcnt(0)" ::: "memory");
-        } else {
-            if constexpr (NV == 8) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)" ::: "memory");
-        }
+        if (SIDE && stored) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "n"(NVA + 16) : "memory");
+        else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "n"(NVA) : "memory");
         __builtin_amdgcn_s_barrier();
     };
     // component XI of the K-step whose row transform sits in q: into the B image of stage `buf` (and V on the side)
@@ -193,13 +226,15 @@ __global__ void __launch_bounds__(256, 1) wino_fused_kernel(const WinoFusedParam
 
     // ---- prologue: stage 0 = K-step 0
     load_step(0, std::integral_constant<int, 0>{});
-    row_transform<DM>(R[0], q);
+    static_for<0, NROWS>([&](auto r_) { row_transform_one<DM, decltype(r_)::value>(R[0], q); });
     __builtin_amdgcn_sched_barrier(0);
     issue_a(0, 0);
     {
         const unsigned vs = side_off(0);
         const bool st = side_on(0);
-        static_for<0, 16>([&](auto xi_) {
+        static_for<0, NC>([&](auto k_) {
+            constexpr int k = decltype(k_)::value;
+            constexpr std::integral_constant<int, 4 * (k / NCOLS) + k % NCOLS> xi_{};
             const f32x2 o = produce(xi_, 0);
             if constexpr (SIDE) {
                 if (st) side_store(xi_, o, 0, vs);
@@ -213,7 +248,7 @@ __global__ void __launch_bounds__(256, 1) wino_fused_kernel(const WinoFusedParam
 
     const int a_lane = wm * 256 + lane * 4;
     const int b_lane = lhi * 64 + wn * 32 + l31;
-    // ---- K loop.  A K-step is 16 slots, one per component g: slot g reads the fragments of component g (consumed one
+    // ---- K loop.  A K-step is NC slots (16 below; 12 / 9 in the reduced classes), one per active component g: slot g reads the fragments of component g (consumed one
     // slot later) and issues the 4 MFMAs of component g - 1; slot 0 issues those of the PREVIOUS step's component 15, whose
     // fragments stay in registers across the barrier - the matrix pipe has work queued while the waves meet and while the
     // first fragments of the new stage arrive.  Beside the MFMAs a slot carries its share of building K-step kt + 1:
@@ -245,12 +280,13 @@ __global__ void __launch_bounds__(256, 1) wino_fused_kernel(const WinoFusedParam
         }
         const unsigned abase = (unsigned)(((kt + 1) * p.mblocks + mb) * FSTAGE) * 4u;
         f32x2 okeep[8];
-        static_for<0, 16>([&](auto g_) {
-            constexpr int g = decltype(g_)::value;
-            constexpr int fb = g & 1, pg = (g + 15) & 15;
-            af[fb] = *reinterpret_cast<const f32x4*>(As + g * 512);
+        static_for<0, NC>([&](auto g_) {
+            constexpr int g = decltype(g_)::value, gp = (g + NC - 1) % NC;
+            constexpr int xi = 4 * (g / NCOLS) + g % NCOLS, pg = 4 * (gp / NCOLS) + gp % NCOLS;     // this slot's component, the previous slot's
+            constexpr int fb = (g + cur * NC) & 1;       // (NC = 9: the fragment buffers alternate across the step boundary too)
+            af[fb] = *reinterpret_cast<const f32x4*>(As + xi * 512);
 #pragma unroll
-            for (int kk = 0; kk < 4; ++kk) bf[fb][kk] = Bs[(g * FBK + 2 * kk) * 64];
+            for (int kk = 0; kk < 4; ++kk) bf[fb][kk] = Bs[(xi * FBK + 2 * kk) * 64];
             // ONE burst of vector / scalar ALU work per slot, in front of its MFMAs (round 4, tools/micro/mfma_shadow.hip: with one
             // wave per SIMD every VALU / SALU instruction costs ~4.5 cycles of matrix-pipe time, every switch MFMA -> ALU -> MFMA
             // ~8 more, and an LDS write right behind the instruction that produced its data ~20; LDS reads / writes by themselves
@@ -258,17 +294,17 @@ __global__ void __launch_bounds__(256, 1) wino_fused_kernel(const WinoFusedParam
             // LDS write of the component follows two MFMAs later.
             f32x2 o = {0.f, 0.f};
             if constexpr (PROD) {
-                if constexpr (g < 4) {
+                if constexpr (g < NROWS) {
                     row_transform_one<DM, g>(R[rb], q);
                     // pin the row here: left alone, hipcc sinks these subtractions to the column transforms of slots 4..15,
                     // which keeps R alive under the loads of slots 8..15 (register copies behind fresh loads = stalls)
 #pragma unroll
                     for (int c = 0; c < PatchCfg<DM>::NCOL; ++c) asm volatile("" : "+v"(q[g][c]));
                 }
-                o = col_transform<DM, g>(q);
+                o = col_transform<DM, xi>(q);
                 asm volatile("" : "+v"(o));
-                if constexpr (g < 8) {        // piece g of this wave's 8 LDS-DMA pieces of the next A image
-                    const unsigned piece = (unsigned)(wid_s * 8 + g);
+                if constexpr (g < PW) {       // piece g of this wave's PW LDS-DMA pieces of the next A image
+                    const unsigned piece = (unsigned)(piece0 + g);
                     const unsigned la = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)((cur ^ 1) * 2 * FSTAGE) * 4u + piece * 1024u);
                     const unsigned a_s = __builtin_amdgcn_readfirstlane(abase + piece * 1024u);
                     const unsigned av = lane16;
@@ -282,9 +318,9 @@ __global__ void __launch_bounds__(256, 1) wino_fused_kernel(const WinoFusedParam
             acc[pg] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[fb ^ 1][1], bf[fb ^ 1][1], acc[pg], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (PROD) {
-                float* bs = smem + (cur ^ 1) * 2 * FSTAGE + FSTAGE + (g * FBK + ch) * 64 + 2 * l31;
+                float* bs = smem + (cur ^ 1) * 2 * FSTAGE + FSTAGE + (xi * FBK + ch) * 64 + 2 * l31;
                 *reinterpret_cast<f32x2*>(bs) = o;
-                if constexpr (SIDE) {
+                if constexpr (SIDE) {         // (NC = 16: xi = g)
                     if constexpr (g < 8) okeep[g] = o;
                     else if (st) {
                         side_store(std::integral_constant<int, g - 8>{}, okeep[g - 8], kt + 1, vs);
@@ -295,9 +331,9 @@ __global__ void __launch_bounds__(256, 1) wino_fused_kernel(const WinoFusedParam
             __builtin_amdgcn_sched_barrier(0);
             acc[pg] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[fb ^ 1][2], bf[fb ^ 1][2], acc[pg], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (PROD && g >= 8) {
-                constexpr int per = NV / 8;
-                static_for<0, per>([&](auto j_) { load_one<DM, (g - 8) * per + decltype(j_)::value>(in_rsrc, vm, l_soff, R[rb]); });
+            if constexpr (PROD && g >= L0) {
+                constexpr int lo = (g - L0) * NVA / LS, hi = (g - L0 + 1) * NVA / LS;
+                static_for<lo, hi>([&](auto j_) { load_one<DM, patch_load_nth<DM, R3, S3>(decltype(j_)::value)>(in_rsrc, vm, l_soff, R[rb]); });
             }
             acc[pg] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[fb ^ 1][3], bf[fb ^ 1][3], acc[pg], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
@@ -316,16 +352,18 @@ __global__ void __launch_bounds__(256, 1) wino_fused_kernel(const WinoFusedParam
     step(std::true_type{}, even, nk - 2);
     retire();
     step(std::false_type{}, odd, nk - 1);
+    constexpr int xi_last = 4 * (NROWS - 1) + NCOLS - 1;
 #pragma unroll
-    for (int kk = 0; kk < 4; ++kk)        // component 15 of the last step
-        acc[15] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[1][kk], bf[1][kk], acc[15], 0, 0, 0);
+    for (int kk = 0; kk < 4; ++kk)        // the last component of the last step (an odd one: its fragments sit in set 1)
+        acc[xi_last] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[1][kk], bf[1][kk], acc[xi_last], 0, 0, 0);
 
-    // ---- epilogue: y = A^T m A per (channel, tile), this lane's tile and 16 channels
+    // ---- epilogue: y = A^T m A per (channel, tile), this lane's tile and 16 channels (the accumulators of inactive
+    // components are the zeros they started as: they reach only outputs outside the image, which are not stored)
     const long long te = t0 + wn * 32 + l31;
-    const bool tv = te < p.T;
+    const bool tv = te < rtiles;
     const long long tq = tv ? te : 0;
     const int n = (int)(tq / tpi), tt = (int)(tq - (long long)n * tpi);
-    const int trow = tt / TW, tcol = tt - trow * TW;
+    const int trow = r0 + tt / nc, tcol = c0 + tt % nc;
     const int ho = trow + d * (trow / d), wo = tcol + d * (tcol / d);
     const bool okr0 = tv && ho < H, okr1 = tv && ho + d < H;
     const bool okc0 = wo < W, okc1 = wo + d < W;
@@ -370,7 +408,7 @@ __global__ void __launch_bounds__(256, 1) wino_fused_kernel(const WinoFusedParam
         const float mean = sum * (1.0f / 128.0f);
         const float d0 = o[0][0] - mean, d1 = o[0][1] - mean, d2 = o[1][0] - mean, d3 = o[1][1] - mean;
         const float m2 = red32((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3));
-        if (l31 == 0 && m < p.M && t0 + wn * 32 < p.T) {      // (T is a multiple of 32 here, not necessarily of 64)
+        if (l31 == 0 && m < p.M && t0 + wn * 32 < rtiles) {   // (one region; T is a multiple of 32 here, not necessarily of 64)
             float* sp = sp0 + (slot * p.M + m) * 2;
             sp[0] = mean; sp[1] = m2;
         }
@@ -444,8 +482,7 @@ __global__ void __launch_bounds__(256, 1) wino_fused_kernel(const WinoFusedParam
             if (acc_out) v += __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(o_rsrc, vo, so, 0));
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), o_rsrc, vo, so, 0);
         });
-        return;
-    }
+    } else {
     float* obase = p.out + (long long)n * p.out_nstride + (long long)ho * W + wo;
     const long long dW = (long long)d * W;
 #pragma unroll
@@ -483,6 +520,33 @@ __global__ void __launch_bounds__(256, 1) wino_fused_kernel(const WinoFusedParam
         }
         if (sp0) stats(m, o);
     }
+    }
+}
+
+// ONE launch over all regions: a block finds its region (block-uniform, scalar) and runs the body of that component class.
+template <int DM, bool SIDE, bool RAGGED>
+__global__ void __launch_bounds__(256, 1) wino_fused_kernel(const WinoFusedParams p) {
+    // blocks b, b + 8, ... share an XCD (round-robin placement): the mblocks blocks of one tile block sit next to each
+    // other there, so the patches they all read are served by that XCD's L2
+    const int xcd = blockIdx.x & 7, jb = blockIdx.x >> 3;
+    const int mb = jb % p.mblocks, tb = (jb / p.mblocks) * 8 + xcd;
+    if (tb >= p.tblocks) return;                                   // block-uniform
+    int tb0 = p.reg[0].tb0, r0 = p.reg[0].r0, nr = p.reg[0].nr, c0 = p.reg[0].c0, nc = p.reg[0].nc, cls = p.reg[0].cls;
+    long long tiles = p.reg[0].tiles;
+#pragma unroll
+    for (int i = 1; i < 4; ++i)
+        if (tb >= p.reg[i].tb0) {
+            tb0 = p.reg[i].tb0; r0 = p.reg[i].r0; nr = p.reg[i].nr; c0 = p.reg[i].c0; nc = p.reg[i].nc; cls = p.reg[i].cls;
+            tiles = p.reg[i].tiles;
+        }
+    if constexpr (SIDE) {
+        wino_fused_body<DM, true, RAGGED, true, true>(p, mb, tb, tb0, r0, nr, c0, nc, tiles);     // (one region: the launcher)
+    } else {
+        if (cls == 3) wino_fused_body<DM, false, RAGGED, true, true>(p, mb, tb, tb0, r0, nr, c0, nc, tiles);
+        else if (cls == 2) wino_fused_body<DM, false, RAGGED, false, true>(p, mb, tb, tb0, r0, nr, c0, nc, tiles);
+        else if (cls == 1) wino_fused_body<DM, false, RAGGED, true, false>(p, mb, tb, tb0, r0, nr, c0, nc, tiles);
+        else wino_fused_body<DM, false, RAGGED, false, false>(p, mb, tb, tb0, r0, nr, c0, nc, tiles);
+    }
 }
 
 // Ug[cb][mb][xi][wm][lane][kk] = (G g G^T)[xi] of g = w[m * sAm + c * sAc + tap] (flip: 8 - tap), c = 8 cb + 2 kk + lane / 32,
@@ -495,20 +559,20 @@ __global__ void __launch_bounds__(256) wino_filter2_kernel(const float* __restri
 }
 
 struct FusedPlan {
-    int TH, TW, mblocks, tblocks, nk, CkP, Mpad;
-    long long T, T16, ug_floats;
+    int mblocks, nk, CkP, Mpad;
+    long long tblocks, T16, ug_floats;
+    WinoTilePlan tiles;
 };
-FusedPlan fused_plan(int N, int H, int W, int d, int M, int Ck) {
+// `classes`: cut the tile grid into component classes (wino_plan.h); not where the tile numbering is visible outside the
+// kernel (V kept on the side, BatchNorm partials - which only exist on maps without half tiles anyway)
+FusedPlan fused_plan(int N, int H, int W, int d, int M, int Ck, bool classes = true) {
     FusedPlan pl;
-    pl.TH = d * ((H + 2 * d - 1) / (2 * d));
-    pl.TW = d * ((W + 2 * d - 1) / (2 * d));
-    pl.TW = (pl.TW + 3) / 4 * 4;
-    pl.T = (long long)N * pl.TH * pl.TW;
-    pl.T16 = (pl.T + 15) / 16 * 16;
+    pl.tiles = wino_tile_plan(N, H, W, d, wino_ragged_on(), classes);
+    pl.T16 = pl.tiles.T16;
     pl.CkP = (Ck + 15) / 16 * 16;                 // an even number of K-steps (the K loop's body is two steps)
     pl.Mpad = (M + 63) / 64 * 64;
     pl.mblocks = pl.Mpad / 64;
-    pl.tblocks = (int)((pl.T + 63) / 64);
+    pl.tblocks = pl.tiles.tblocks;
     pl.nk = pl.CkP / 8;
     pl.ug_floats = ((long long)16 * pl.CkP * pl.Mpad + 63) / 64 * 64;
     return pl;
@@ -531,7 +595,7 @@ bool dcfp_wino_fused_ok(const WinoProblem& q) {
     if (wino_fused_mode() == 0) return false;
     if (q.M < 48 || q.Ck < 48) return false;       // (the cost model of conv_igemm.hip decides above that)
     const FusedPlan pl = fused_plan(q.N, q.H, q.W, q.d, q.M, q.Ck);
-    if (pl.T16 >= (1LL << 30) || (long long)pl.tblocks * pl.mblocks + 8 * pl.mblocks >= (1LL << 31)) return false;
+    if (pl.T16 >= (1LL << 30) || pl.tblocks >= (1LL << 30) || pl.tblocks * pl.mblocks + 8 * pl.mblocks >= (1LL << 31)) return false;
     if ((long long)pl.CkP * pl.Mpad * 16 * 4 >= 0x7fffff00LL) return false;
     return fused_mode(q) >= 0;
 }
@@ -555,7 +619,7 @@ int dcfp_wino_fused_run(const GemmProblem& g, const float* in, const float* w, f
     const int flip = g.offstep < 0;          // dgrad: the taps rotated by 180 degrees
     const long long in_nstride = g.in_nstride, out_nstride = g.out_nstride;
     float* const xform_out = x.xform_out;
-    const FusedPlan pl = fused_plan(N, H, W, d, M, Ck);
+    const FusedPlan pl = fused_plan(N, H, W, d, M, Ck, !xform_out && !x.stat_part);
     if (!workspace || !dcfp_aligned16(workspace) || workspace_bytes < (size_t)pl.ug_floats * sizeof(float))
         return DCFP_E_WORKSPACE;
     const int pitch = q.in_pitch > 0 ? q.in_pitch : W;
@@ -581,9 +645,13 @@ int dcfp_wino_fused_run(const GemmProblem& g, const float* in, const float* w, f
     p.xform_out = xform_out;
     p.stat_part = x.stat_part;
     p.scale = x.scale; p.shift = x.shift; p.residual = x.residual; p.relu = x.relu;
-    p.N = N; p.M = M; p.Ck = Ck; p.H = H; p.W = W; p.d = d; p.TH = pl.TH; p.TW = pl.TW;
-    p.T = pl.T; p.T16 = pl.T16;
-    p.mblocks = pl.mblocks; p.tblocks = pl.tblocks; p.nk = pl.nk;
+    p.N = N; p.M = M; p.Ck = Ck; p.H = H; p.W = W; p.d = d;
+    p.T16 = pl.T16;
+    for (int i = 0; i < 4; ++i) {
+        const WinoRegion& r = pl.tiles.reg[i];
+        p.reg[i] = {r.tb0, r.r0, r.nr, r.c0, r.nc, (r.rows3 ? 1 : 0) | (r.cols3 ? 2 : 0), r.tiles};
+    }
+    p.mblocks = pl.mblocks; p.tblocks = (int)pl.tblocks; p.nk = pl.nk;
     p.accumulate = x.accumulate;
     p.ragged_c = (Ck % 16) != 0;
     {
@@ -594,7 +662,7 @@ int dcfp_wino_fused_run(const GemmProblem& g, const float* in, const float* w, f
         static const int no_vec = [] { const char* e = getenv("DCFP_WF_SCALAR_EPI"); return e ? atoi(e) : 0; }();
         if (no_vec) p.vec_epi = 0;
     }
-    const long long grid = (long long)((pl.tblocks + 7) / 8) * 8 * pl.mblocks;
+    const long long grid = (pl.tblocks + 7) / 8 * 8 * pl.mblocks;
     const size_t lds = (size_t)4 * FSTAGE * sizeof(float);
     auto launch = [&](auto kern) -> int {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,

@@ -24,6 +24,7 @@
 // in `s_waitcnt lgkmcnt(0)` + barrier and the patch loads issued three K-steps ahead are waited for where they are used.
 #include "wino_patch.h"
 #include "conv_dispatch.h"
+#include "wino_plan.h"
 #include <stdlib.h>
 
 namespace {
@@ -441,11 +442,9 @@ int wg_mode(int N, int H, int W, int d, int M, int C, long long x_nstride, int x
 
 WgPlan wg_plan(int N, int H, int W, int d, int M, int C) {
     WgPlan pl;
-    pl.TH = d * ((H + 2 * d - 1) / (2 * d));
-    pl.TW = d * ((W + 2 * d - 1) / (2 * d));
-    pl.TW = (pl.TW + 3) / 4 * 4;               // (conv_winograd.hip's tile grid: even, so a pair never straddles a tile row)
-    pl.T = (long long)N * pl.TH * pl.TW;
-    pl.T16 = (pl.T + 15) / 16 * 16;
+    const WinoTilePlan tp = wino_tile_plan(N, H, W, d, wino_ragged_on(), false);    // (wino_plan.h: the valid tiles only)
+    pl.TH = tp.TH; pl.TW = tp.TW;              // (TW even, so a pair never straddles a tile row)
+    pl.T = tp.T; pl.T16 = tp.T16;
     pl.mblocks = (M + 63) / 64;
     pl.cblocks = (C + 63) / 64;
     // split K so that blocks fill whole rounds of the CUs (one workgroup per CU), each at least 32 K-steps long

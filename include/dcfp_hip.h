@@ -21,7 +21,10 @@
  *     DCFP_WINO_VEC, DCFP_WINO_FUSED (0 three-pass Winograd only / 1 fused kernel where it wins, default / 2 wherever it
  *     applies), DCFP_WINO_WGRAD_FUSED (0 batched Winograd weight gradient on the kept transform only / 1 the fused
  *     weight-gradient kernel where the cost model prefers it, default / 2 wherever it applies and beats the direct
- *     kernel), DCFP_WINO_WGRAD_RATE (TF the cost model prices that kernel at), DCFP_CONV_STEM (0: the Cin = 3 stem conv
+ *     kernel), DCFP_WINO_RAGGED (0: every Winograd path enumerates the full grid of 2d x 2d super-blocks and the fused
+ *     kernel runs all 16 components of every tile; 1, default: tiles without an output inside the image are not enumerated
+ *     and tiles whose second output row / column lies outside run 12 or 9 components - forward and dgrad results are
+ *     bit-identical either way), DCFP_WINO_WGRAD_RATE (TF the cost model prices that kernel at), DCFP_CONV_STEM (0: the Cin = 3 stem conv
  *     through the general kernels), DCFP_IGEMM_NT (1 / 2: nt / sc1 output stores of the 1x1 kernel, A/B), DCFP_WF_SCALAR_EPI, DCFP_CONV_GEMV (0: 1x1 convs on a 1 x 1 map through the general kernels),
  *     DCFP_CE_BWD_CELLS (0: the per-output fused upsample + CE backward instead of the cell-organised one, at every
  *     class count) -
@@ -182,8 +185,18 @@ int dcfp_conv2d_kernel_name(const DcfpConvDesc* d, int pass, char* buf, int buf_
  * < 1 for dilated 3x3 convs whose dilation is comparable to the image height (ASPP 12 / 24 / 36 on 128 rows,
  * networks/tools/aspp.py:37-39): the 9-tap LDS-DMA kernels skip, per pixel tile, the kernel rows that lie
  * wholly in the zero padding (x + 0*w == x: same bits for finite weights).  Accounting only (bench.py reports
- * `executed_frac` beside `frac`); DCFP_IGEMM_TAPSKIP=0 disables the skipping. */
+ * `executed_frac` beside `frac`); DCFP_IGEMM_TAPSKIP=0 disables the skipping.  A Winograd pass counts the tiles its
+ * plan enumerates at 16 components each (16/36 x tile padding; ragged maps: dcfp_wino_tile_plan). */
 double dcfp_conv2d_executed_fraction(const DcfpConvDesc* d, int pass);
+
+/* The tile plan the Winograd F(2x2, 3x3) paths share for an N x H x W map with dilation d (tests, tools).
+ * ragged: 0 the full grid of super-blocks, 1 only tile rows / columns with an output inside the image, -1 what
+ * DCFP_WINO_RAGGED selects; classes != 0: the grid cut into the component classes of the fused forward / dgrad kernel.
+ * out (39 values): TH, TW, T, T16, regions, 64-tile blocks, then per region (four slots) r0, nr, c0, nc, rows3, cols3,
+ * first block, blocks - tile rows r0 .. r0 + nr - 1 x tile columns c0 .. c0 + nc - 1 of every image; rows3 / cols3 = 0: the
+ * tiles' second output row / column lies outside the image and the components r = 3 / s = 3 are not computed; out[38]:
+ * the components issued over all tiles (dcfp_conv2d_executed_fraction counts 16 per enumerated tile). */
+int dcfp_wino_tile_plan(int N, int H, int W, int d, int ragged, int classes, int64_t* out);
 
 /* y = conv(x, w) (+ bias[co] when bias != NULL).  y_nstride: batch stride of y in
  * elements (0 => Cout*Hout*Wout), lets a branch write into a channel slice of a
