@@ -129,6 +129,7 @@ AUG_SATURATION, AUG_HUE = 1, 2
 SGD_CHUNK = 16384
 FILTER_ABS_SUM, FILTER_L2, FILTER_DOT_SQ_ACC = 0, 1, 2    # DCFP_FILTER_* of include/dcfp_hip.h
 FPGM_TILE = 64                                            # DCFP_FPGM_TILE
+DIGEST_CHUNK, DIGEST_MAX_BLOCKS = 4096, 2048              # DCFP_DIGEST_*
 CONV_FWD, CONV_DGRAD, CONV_WGRAD = 0, 1, 2
 E_BADDESC, E_UNSUPPORTED, E_WORKSPACE = -1, -2, -3   # DCFP_E_* of include/dcfp_hip.h
 
@@ -263,6 +264,8 @@ SIGNATURES = {
     "dcfp_filter_reduce_f32": (_I, [_P, _I, _L, _I, _P]),
     "dcfp_fpgm_workspace_bytes": (_Z, [_I]),
     "dcfp_fpgm_f32": (_I, [_P, _I, _L, _P, _Z, _P]),
+    "dcfp_state_digest_workspace_bytes": (_Z, [_Z]),
+    "dcfp_state_digest_u64": (_I, [_P, _Z, C.c_uint64, _P, _Z, _P, _P]),
     "dcfp_engine_open": (_I, [C.c_char_p, C.POINTER(_P), C.c_char_p, _Z]),
     "dcfp_engine_open_memory": (_I, [_P, _Z, C.POINTER(_P), C.c_char_p, _Z]),
     "dcfp_engine_close": (None, [_P]),

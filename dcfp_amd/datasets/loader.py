@@ -53,12 +53,35 @@ class TrainLoader:
         self.num_samples = -(-len(dataset) // self.world_size)
         self._id_table = None
         self.last_pixels = None          # resample: the pixel every sample's crop was placed on (None: plain draws)
+        self._cursor = None              # (epoch being iterated, batches of it already yielded); None: between epochs
+        self._skip = 0                   # batches the next __iter__ leaves out (load_state_dict)
 
     def __len__(self):
         return self.num_samples // self.batch_size
 
     def set_epoch(self, epoch):
         self.epoch = int(epoch)
+        self._cursor, self._skip = None, 0
+
+    def state_dict(self):
+        """Where the loader stands: the epoch, the batches of it already yielded and the draw generator's state.  That is
+        all of it: the order of an epoch (and a `resample` dataset's epoch index) is a function of (seed, epoch), and the
+        draws of a batch - the per-sample child generators of the `resample` path included - are taken from `self.rng`
+        when the batch is collated, never for a batch that is only decoding ahead."""
+        epoch, batch = self._cursor if self._cursor is not None else (self.epoch, self._skip)
+        if batch >= len(self):           # the epoch's last batch has been yielded: the next one starts
+            epoch, batch = epoch + 1, 0
+        return {"epoch": int(epoch), "batch": int(batch), "rng": self.rng.getstate()}
+
+    def load_state_dict(self, state):
+        """The next __iter__ continues the epoch of `state` behind its cursor; the batches before it are not decoded."""
+        epoch, batch = int(state["epoch"]), int(state["batch"])
+        if epoch < 0 or not 0 <= batch < max(1, len(self)):
+            raise ValueError("TrainLoader.load_state_dict: batch %d of epoch %d does not exist (%d batches per epoch)"
+                             % (batch, epoch, len(self)))
+        rng = state["rng"]
+        self.rng.setstate((rng[0], tuple(rng[1]), rng[2]))
+        self.epoch, self._skip, self._cursor = epoch, batch, None
 
     def indices(self, epoch):
         """This rank's sample order of one epoch (DistributedSampler's: permutation, wrap-around padding, stride)."""
@@ -80,13 +103,20 @@ class TrainLoader:
     def __iter__(self):
         self.dataset.pre_processing(self.epoch, None)
         idx = self.indices(self.epoch)
+        epoch, first = self.epoch, self._skip
         self.epoch += 1
+        self._skip = 0
+        self._cursor = (epoch, first)
         batches = [idx[i:i + self.batch_size] for i in range(0, len(self) * self.batch_size, self.batch_size)]
+        batches = batches[first:]                          # a restored cursor: the batches before it are never decoded
         pending = self._submit(batches[0]) if batches else None
         for b, cur in enumerate(batches):
             decoded = [f.result() for f in pending]
             pending = self._submit(batches[b + 1]) if b + 1 < len(batches) else None     # decode ahead of the device
-            yield self.collate(decoded, cur)
+            out = self.collate(decoded, cur)
+            self._cursor = (epoch, first + b + 1)
+            yield out
+        self._cursor = None
 
     def collate(self, decoded, idx=None):
         """decoded: [(uint8 [H,W,3] BGR, uint8 [H,W] or None)] -> (images, labels) on the device."""

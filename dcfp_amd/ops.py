@@ -2552,3 +2552,30 @@ def component_pixel(components, n, k):
         check(_lib.lib().dcfp_component_pixel_i32(c.records, c.N, _p(c.work), c.work.numel(), _p(c._counts_dev),
                                                   _p(nk[0]), _p(nk[1]), _p(yx), _stream()), "component_pixel")
     return yx
+
+
+def state_digest_device(t, base=0):
+    """The digest of `state_digest`, left on the device: int64 [2] holding (d0, d1) as bits.  No host synchronisation."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError("dcfp_amd: state_digest takes a CUDA/HIP tensor (no CPU fallback exists)")
+    if t.element_size() != 4 or not t.is_contiguous():
+        raise RuntimeError("state_digest: a contiguous tensor of a 4-byte dtype expected, got %s%s"
+                           % (t.dtype, "" if t.is_contiguous() else " (not contiguous)"))
+    base = int(base)
+    if not 0 <= base < 1 << 64:
+        raise ValueError("state_digest: base is an unsigned 64-bit index")
+    n = t.numel()
+    L = _lib.lib()
+    out = torch.empty(2, dtype=torch.int64, device=t.device)
+    with torch.cuda.device(t.device):
+        ws = _workspace("state_digest", L.dcfp_state_digest_workspace_bytes(n), t.device)
+        check(L.dcfp_state_digest_u64(_p(t) if n else None, n, base, _p(ws), ws.numel(), _p(out), _stream()),
+              "state_digest")
+    return out
+
+
+def state_digest(t, base=0):
+    """(d0, d1) of a contiguous CUDA tensor of a 4-byte dtype read as 32-bit words w_i, mod 2^64:
+    d0 = sum w_i, d1 = sum (base + i + 1) * w_i.  Two Python ints in [0, 2^64); reading them is one host synchronisation."""
+    d0, d1 = state_digest_device(t, base).tolist()
+    return d0 & 0xFFFFFFFFFFFFFFFF, d1 & 0xFFFFFFFFFFFFFFFF

@@ -25,7 +25,7 @@ import torch.nn as nn
 from .. import _lib
 from .._lib import FilterEntry, FpgmEntry, GateEntry, check
 from .channel_pruner import build_graph
-from .dcfp_pruner import DCFPPruner
+from .dcfp_pruner import DCFPPruner, adopt_scores
 
 WEIGHT_CRITERIA = ("slimming", "l1", "l2", "fpgm")
 TAYLOR_MODES = {"gate": "taylor", "weight": "taylor_w"}
@@ -197,6 +197,25 @@ class taylor_pruning(_GateTable):
 
     def get_eic(self):
         return self.state_dict
+
+    def get_state(self):
+        """What a continued run needs of this scorer (train_state): the running sums and the step count
+        `scores()` divides them by."""
+        return {"eic": dict(self.state_dict["eic"]), "steps": int(self.steps), "criterion": self.criterion}
+
+    def set_state(self, state, device=None):
+        """Take back what get_state() gave - the twin of dcfp_pruning.set_eic: the sums become views into one fresh
+        arena (on `device` if given), which the next step() copies into the arena its table points at."""
+        if state.get("criterion", self.criterion) != self.criterion:
+            raise ValueError("taylor_pruning.set_state: the state is of criterion %r, this scorer of %r"
+                             % (state.get("criterion"), self.criterion))
+        for n, v in state["eic"].items():
+            if isinstance(v, torch.Tensor) and n in self._channels and v.numel() != self._channels[n]:
+                raise ValueError("taylor_pruning.set_state: %s has %d channels, the state %d"
+                                 % (n, self._channels[n], v.numel()))
+        self.state_dict["eic"] = adopt_scores(state["eic"], self._names, device, "taylor_pruning.set_state", self)
+        self.steps = int(state["steps"])
+        self._key = None
 
     def scores(self):
         """{bn: FloatTensor[C]} on the CPU: the running sums over the steps run, divided by their number."""

@@ -21,6 +21,29 @@ from .._lib import EicEntry, check
 from .channel_pruner import ChannelPruner
 
 
+def adopt_scores(eic, names, device, who, owner):
+    """{name: view into one fresh fp32 arena} holding the vectors of `eic` in the order of `names` (the arena is left in
+    owner._arena); a state whose every entry is still the starting 0 stays that.  Shared by the online scorers."""
+    if list(eic) != list(names):
+        odd = next((a for a, b in zip(list(eic), list(names)) if a != b), None)
+        raise ValueError("%s: the state holds %d layers and this model scores %d%s"
+                         % (who, len(eic), len(names), "" if odd is None else " (first difference at %r)" % odd))
+    if not any(isinstance(v, torch.Tensor) for v in eic.values()):
+        return {n: 0 for n in names}
+    for n, v in eic.items():
+        if not isinstance(v, torch.Tensor) or v.dim() != 1:
+            raise ValueError("%s: %s is not a vector" % (who, n))
+    arena = torch.cat([eic[n].detach().to(torch.float32) for n in names]).clone()
+    if device is not None:
+        arena = arena.to(device)
+    owner._arena = arena
+    out, off = {}, 0
+    for n in names:
+        out[n] = arena[off:off + eic[n].numel()]
+        off += eic[n].numel()
+    return out
+
+
 class dcfp_pruning():
     def __init__(self, model, r=0.99, **kwards):
         self.r = r
@@ -76,6 +99,13 @@ class dcfp_pruning():
 
     def get_eic(self):
         return self.state_dict
+
+    def set_eic(self, state, device=None):
+        """Take back what get_eic() gave (train_state): state["eic"] = {bn name: FloatTensor[C]} for exactly
+        the scored layers, in their order.  The vectors become views into one fresh arena (on `device` if given, else
+        where they are); the next step() rebuilds its table and copies them, bit for bit, next to the gradients."""
+        self.state_dict["eic"] = adopt_scores(state["eic"], self._names, device, "dcfp_pruning.set_eic", self)
+        self._key = None
 
     def export_eic(self, path):
         """score.pth = {'eic': {bn_name: FloatTensor[C]}} (dcfp_pruner.py:25-26)."""

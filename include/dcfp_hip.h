@@ -986,6 +986,26 @@ size_t dcfp_fpgm_workspace_bytes(int C);
 int dcfp_fpgm_f32(const DcfpFpgmEntry* table, int n_entries, int64_t total_tiles, void* workspace,
                   size_t workspace_bytes, dcfp_stream_t stream);
 
+/* ------------------------------------------------ state digest (csrc/digest.hip)
+ * A 128-bit digest of a device buffer viewed as n_words 32-bit words w_0 .. w_{n-1}, all arithmetic mod 2^64:
+ *   out2[0] = sum_i w_i          out2[1] = sum_i (index_base + i + 1) * w_i
+ * Integer sums: the result does not depend on any reduction order (no atomics, the same pair from every call), the
+ * words are read as bits (-0.0 and 0.0 differ), a swap of two different words changes out2[1], and a buffer digested
+ * in pieces gives the whole's digest as the sum of digest(piece, index_base + the piece's first index).
+ * data: any 4-byte aligned device address (16-byte loads from the first 16-byte boundary on).  The body is cut into
+ * chunks of DCFP_DIGEST_CHUNK words, at most DCFP_DIGEST_MAX_BLOCKS blocks stride over them and leave 16 bytes each in
+ * the workspace; a second one-block launch adds those and the up to 3 + 3 words outside the 16-byte vectors.
+ * dcfp_state_digest_workspace_bytes(n_words) is enough at every alignment (0 for n_words < 4).  out2: device, 2 values,
+ * 8-byte aligned, written by the second launch on `stream`.
+ * n_words == 0 gives (0, 0) and reads nothing.  Null or misaligned data with n_words > 0 and a null or misaligned out2
+ * are DCFP_E_BADDESC; a workspace that is needed and null, not 8-byte aligned or too small DCFP_E_WORKSPACE; n_words
+ * above 2^60 DCFP_E_UNSUPPORTED.  All of it is checked before any HIP call. */
+#define DCFP_DIGEST_CHUNK 4096
+#define DCFP_DIGEST_MAX_BLOCKS 2048
+size_t dcfp_state_digest_workspace_bytes(size_t n_words);
+int dcfp_state_digest_u64(const void* data, size_t n_words, uint64_t index_base, void* workspace,
+                          size_t workspace_bytes, uint64_t* out2 /* device, 2 values */, dcfp_stream_t stream);
+
 /* ------------------------------------------------ Lovasz-Softmax loss (csrc/lovasz.hip)
  * The Lovasz-Softmax loss (Berman et al. 2018, classes = 'present') of the bilinearly upsampled logits, with the sort
  * replaced by an integer histogram of quantised errors.  Arguments as dcfp_upsample_ce_*: logits fp32 [N,C,h,w], labels

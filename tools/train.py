@@ -10,6 +10,9 @@ teacher; `--loss-para '{"pa_weight": 1.0, "pa_pool": 2}'` sets its
 (DESIGN §18); `--loss-para '{"lovasz_weight": 1.0, "lovasz_bins": 1024}'` sets its weight and its error bins.
 `--prune-type taylor | taylor_w` scores by first-order Taylor instead of `dcfp`, `--slim-lambda` adds the Network
 Slimming L1 term to the BN weight gradients (the baseline criteria).
+`--state-every N` writes the whole training state after every N-th step and `-c/--continue FILE` runs on from such a
+file, leaving the bits the uninterrupted run leaves (dcfp_amd/train_state.py); `--log-digest N` prints a
+128-bit digest of the parameter arena every N steps, so two runs can be compared from their logs.
 One process per GPU: `python -m torch.distributed.run --nproc-per-node N tools/train.py ...`."""
 import argparse
 import json
@@ -21,7 +24,7 @@ import time
 sys.path.insert(0, osp.dirname(osp.dirname(osp.abspath(__file__))))
 import torch  # noqa: E402
 
-from dcfp_amd import networks, pruners  # noqa: E402
+from dcfp_amd import networks, pruners, train_state  # noqa: E402
 from dcfp_amd.engine import Engine  # noqa: E402
 from dcfp_amd.loss.criterion import build_criterions  # noqa: E402
 from dcfp_amd.optimizer import adjust_learning_rate, build_optimizer  # noqa: E402
@@ -96,6 +99,12 @@ def get_parser():
                    help='JSON: "root" and "list_path" of the dataset, further DataSet keywords '
                         '("resample": true for the class-balanced sampler of the fine-tune recipes; "target_class" for '
                         '--balance 2 without it)')
+    p.add_argument("--state-every", type=int, default=0,
+                   help="after every N-th step write train_state_<k>.pth into --snapshot-dir: everything -c/--continue "
+                        "needs to run on bit-identically (0 = off); DESIGN §20")
+    p.add_argument("--keep-states", type=int, default=2, help="state files kept after a successful write (0 = all)")
+    p.add_argument("--log-digest", type=int, default=0,
+                   help="every N steps print `digest it=<k> params=<d0>:<d1>`, the 128-bit digest of the parameter arena")
     p.add_argument("--log-time", type=str2bool, default="False",
                    help="synchronise after every iteration and print its device time (batch synthesis excluded)")
     return p
@@ -129,6 +138,13 @@ def check_args(args):
         raise ValueError("--prune-type %s: the Taylor scorers are %s" % (args.prune_type, ", ".join(sorted(TAYLOR_TYPES))))
     if not args.slim_lambda >= 0.0:
         raise ValueError("--slim-lambda %r: the sparsity weight is >= 0 (0 = off)" % args.slim_lambda)
+    if getattr(args, "continue_fpath", None):
+        if args.resume:
+            raise ValueError("-c/--continue restores the weights itself: give it without --resume")
+        if args.start_iters != 0:
+            raise ValueError("-c/--continue takes the step counter from the state file: give it without --start-iters")
+    if args.state_every < 0 or args.keep_states < 0 or args.log_digest < 0:
+        raise ValueError("--state-every, --keep-states and --log-digest are >= 0")
 
 
 def build_teacher(args, num_classes, device):
@@ -179,6 +195,15 @@ def main(argv=None):
                 torch.save(channel_cfg, osp.join(args.snapshot_dir, "channel_cfg.pth"))
         if args.resume:
             load_model(seg_model, args.resume)
+        wants_state = bool(args.continue_fpath) or args.state_every > 0
+        state_fp = train_state.fingerprint(args, seg_model, dataset.num_classes, engine.world_size) if wants_state else None
+        state, start_iters = None, args.start_iters
+        if args.continue_fpath:
+            # the weights go in where --resume puts them: before the move to the device and before the optimizer's arena
+            # adopts them, so the permuted copies and kept filters of the first forward are built from the loaded weights
+            with train_state.Timer() as t_restore:
+                state = train_state.load(args.continue_fpath)
+                start_iters = train_state.restore_model(state, seg_model, state_fp)
         device = torch.device("cuda", engine.local_rank)
         seg_model.to(device)
         optimizer = build_optimizer(args, seg_model)
@@ -207,7 +232,17 @@ def main(argv=None):
                 while True:
                     yield from loader
             batches = epochs()
-        for it in range(args.start_iters, args.num_steps):
+        source = dataset if batches is None else loader
+        if state is not None:
+            # (after torch.manual_seed above and after everything that draws while the model is built)
+            with train_state.Timer() as t_rest:
+                train_state.restore_rest(state, optimizer, train_pruning, device, source,
+                                         rank=torch.distributed.get_rank() if engine.distributed else 0)
+            if main_flag:
+                print("continued from %s at iteration %d (restore %.3f s)"
+                      % (args.continue_fpath, start_iters, t_restore.seconds + t_rest.seconds), flush=True)
+            state = None
+        for it in range(start_iters, args.num_steps):
             if batches is None:
                 images, labels = dataset.batch(per_rank, device)
             else:
@@ -255,6 +290,19 @@ def main(argv=None):
                 done = it + 1
                 if done >= args.save_steps and ((args.num_steps - done) % args.save_pred_every == 0 or done >= args.num_steps):
                     torch.save(seg_model.state_dict(), osp.join(args.snapshot_dir, "CS_scenes_%d.pth" % done))
+            if args.log_digest > 0 and (it + 1) % args.log_digest == 0 and main_flag:
+                from dcfp_amd import ops as _ops
+                print("digest it=%d params=%s" % (it + 1, train_state.format_digest(
+                    _ops.state_digest(optimizer.arena().flat_param))), flush=True)
+            if args.state_every > 0 and (it + 1) % args.state_every == 0:
+                with train_state.Timer() as t_save:          # (every rank: the digests are compared across the ranks)
+                    snap = train_state.capture(it + 1, seg_model, optimizer, train_pruning, device, source, state_fp)
+                    if not engine.distributed or torch.distributed.get_rank() == 0:
+                        path = train_state.save(snap, train_state.state_path(args.snapshot_dir, it + 1))
+                        train_state.prune_old(args.snapshot_dir, args.keep_states)
+                    snap = None
+                if not engine.distributed or torch.distributed.get_rank() == 0:
+                    print("state %s (save %.3f s)" % (path, t_save.seconds), flush=True)
         if main_flag and train_pruning is not None:
             train_pruning.export_eic(osp.join(args.snapshot_dir, "score.pth"))
         from dcfp_amd import syncbn_p2p, ops as _ops
