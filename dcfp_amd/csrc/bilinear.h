@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include <type_traits>
+
 namespace dcfp_bilinear {
 
 struct Lerp {
@@ -39,6 +41,16 @@ __device__ __forceinline__ Lerp lerp_of(int dst, float scale, int in_size) {
 inline float host_scale(int in, int out, int align) {
     if (align) return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f;
     return (float)in / (float)out;
+}
+
+// The host's align_corners flag as the kernels' ALIGN template argument: f(std::true_type{}) or f(std::false_type{}),
+//     with_align(align_corners, [&](auto A) { hipLaunchKernelGGL(kernel<A.value>, ...); });
+template <class F>
+inline void with_align(int align_corners, F&& f) {
+    if (align_corners)
+        f(std::true_type{});
+    else
+        f(std::false_type{});
 }
 
 // Conservative [lo, hi] range of destination indices whose taps may include source cell i.

@@ -1,8 +1,8 @@
 // lovasz.hip — Lovasz-Softmax loss (Berman, Triki, Blaschko, CVPR 2018; classes = 'present') of the bilinearly
 // upsampled low-resolution logits, without a sort and without the N x C x H x W probabilities.
 //
-// Per valid pixel (label in [0, C), not ignore_index) and class c:  z = bilinear upsample of the logits (bilinear.h, the
-// interpolation expression of upsample_ce_fwd_kernel),  p = exp(z - lse),  e = (label == c) ? 1 - p : p,
+// Per valid pixel (label in [0, C), not ignore_index) and class c:  z = bilinear upsample of the logits (bilinear.h,
+// logit_of() of upsample_logits.h),  p = exp(z - lse),  e = (label == c) ? 1 - p : p,
 //     q = min(2^20, floor(e * 2^20 + 0.5)),      b = min(B - 1, q >> (20 - log2 B)),       B = bins.
 // Per class and bin four integers: nF / nB count the foreground (label == c) / background pixels of the bin, SF / SB
 // add their q.  With G = sum_b nF[b] (> 0: the class is present) and F_above / G_above the foreground / background
@@ -23,8 +23,8 @@
 //              adds only: the table does not depend on the order of arrival.
 //   scan       one workgroup per class: suffix sums over the bins, the weights and loss_c in fp64 in a fixed order;
 //              a last kernel counts the present classes P, writes the loss and the fp32 table [C][B][2] = (wF, wB) / P.
-//   backward   one pass writes A = sum_c a_c p_c per pixel; a gather organised by cells, in the manner of
-//              upsample_ce_bwd_cells_chunk_kernel, adds wy wx p_c (a_c - A) over the destination pixels of every
+//   backward   one pass writes A = sum_c a_c p_c per pixel; the gather organised by cells that the CE backward
+//              uses (cell_gather.h) adds wy wx p_c (a_c - A) over the destination pixels of every
 //              low-resolution element, each pixel evaluated once per window of 20 classes.  No atomics.
 //   errors     q of every (n, c, Y, X) as uint32, 0xFFFFFFFF at invalid pixels: for tests and for looking at the
 //              error distribution, never part of a training step.
@@ -33,11 +33,20 @@
 #include "bilinear.h"
 #include "common.h"
 
+// From here on every expression compiles without FMAs, those of the two headers below included: contraction is fixed
+// where an expression is parsed, not where a template is instantiated.  bilinear.h stays above the pragma - lerp_of and
+// dst_range are the coordinate rules of every file and keep the contraction they have everywhere else - while the
+// per-pixel helpers (logit_of, lse_at) and the cell gather's accumulates must be this file's: uncontracted, like
+// lovasz_term(), so that the histogram and the backward see the same z, p, q and b.
 #pragma clang fp contract(off)
+
+#include "cell_gather.h"
+#include "upsample_logits.h"
 
 namespace {
 
-using namespace dcfp_bilinear;
+using namespace dcfp_bilinear;   // Lerp, lerp_of, host_scale, with_align; Tap, tap_of, logit_of, lse_at, Pix, pix_of
+using namespace dcfp_cells;      // kCellTH, kCellTW, kCellThreads, kCellCount, cell_block, cell_gather
 
 constexpr int kQ = 20;                       // q = e * 2^20, rounded
 constexpr int kThreads = 256;
@@ -46,36 +55,17 @@ constexpr int kHistSlots = 4096;             // (class, bin) pairs of a chunk: 4
 constexpr long long kTileMin = 2048, kTileMax = 65536;      // pixels per histogram workgroup (low word: 2^16 * 2^14)
 constexpr int kMaxBlocks = 1 << 16;
 
-// the stencil of a destination pixel: four offsets into a class plane and the four lerp factors
-struct Tap {
-    int o00, o01, o10, o11;
-    float h0, h1, w0, w1;
-};
-
-__device__ __forceinline__ Tap tap_of(const Lerp& Lh, const Lerp& Lw, int w) {
-    Tap t;
-    t.o00 = Lh.i0 * w + Lw.i0; t.o01 = Lh.i0 * w + Lw.i1;
-    t.o10 = Lh.i1 * w + Lw.i0; t.o11 = Lh.i1 * w + Lw.i1;
-    t.h0 = Lh.l0; t.h1 = Lh.l1; t.w0 = Lw.l0; t.w1 = Lw.l1;
-    return t;
-}
-
-__device__ __forceinline__ float logit_at(const float* __restrict__ p, const Tap& t) {
-    return t.h0 * (t.w0 * p[t.o00] + t.w1 * p[t.o01]) + t.h1 * (t.w0 * p[t.o10] + t.w1 * p[t.o11]);
-}
-
 struct Term {
     float z, p;
     unsigned q;
     int b;
 };
 
-// (pixel, class) -> z, p, q, b from the class's four stencil values; shift = 20 - log2 B.  The interpolation is the
-// expression of logit_at() on the same values, so it does not matter whether a kernel holds them in registers.
+// (pixel, class) -> z, p, q, b from the class's four stencil values; shift = 20 - log2 B
 __device__ __forceinline__ Term lovasz_term(float v00, float v01, float v10, float v11, float h0, float h1, float w0,
                                             float w1, float lse, bool fg, int shift, int last_bin) {
     Term r;
-    r.z = h0 * (w0 * v00 + w1 * v01) + h1 * (w0 * v10 + w1 * v11);
+    r.z = logit_of(v00, v01, v10, v11, h0, h1, w0, w1);
     r.p = expf(r.z - lse);
     const float e = fg ? 1.0f - r.p : r.p;
     const float s = floorf(e * (float)(1 << kQ) + 0.5f);          // exact: a power-of-two scale, then |x| < 2^23
@@ -92,36 +82,8 @@ __device__ __forceinline__ Term lovasz_term(const float* __restrict__ plane, con
                        last_bin);
 }
 
-// log-sum-exp of the pixel's C interpolated logits (the running form of upsample_ce_fwd_kernel)
-__device__ __forceinline__ float lse_at(const float* __restrict__ base, long long plane, int C, const Tap& t) {
-    float m = -INFINITY, s = 0.f;
-    for (int c = 0; c < C; ++c) {
-        const float z = logit_at(base + c * plane, t);
-        if (z > m) {
-            s = s * expf(m - z) + 1.f;
-            m = z;
-        } else {
-            s += expf(z - m);
-        }
-    }
-    return m + logf(s);
-}
-
 __device__ __forceinline__ bool label_valid(long long label, int C, int ignore_index) {
     return label >= 0 && label < C && label != ignore_index;
-}
-
-struct Pix {
-    int n, Y, X;
-};
-
-__device__ __forceinline__ Pix pix_of(long long pix, int H, int W) {
-    Pix r;
-    r.X = (int)(pix % W);
-    const long long t = pix / W;
-    r.Y = (int)(t % H);
-    r.n = (int)(t / H);
-    return r;
 }
 
 // ------------------------------------------------------------------------------------------------ histogram
@@ -285,152 +247,55 @@ lovasz_asum_kernel(const float* __restrict__ logits, const long long* __restrict
     }
 }
 
-// The gather, organised by CELLS as upsample_ce_bwd_cells_chunk_kernel is.  The cell of a destination pixel is the
-// low-resolution position (i0, j0) its stencil starts at; a pixel lies in exactly one cell and touches only that cell's
-// four corners.  A lane pair owns a cell and a window of CT classes [c0, c0 + CT): it holds the four corner logit vectors
-// in registers, evaluates each destination pixel of the cell once (label, lse, A and the stencil once per pixel, not
-// once per class and corner) and accumulates the four corner sums.  A workgroup covers 7 x 15 low-resolution outputs =
-// 8 x 16 cells (one halo row and column recomputed by the neighbour), parks the corner sums in LDS and adds, per output
-// and class, the <= 4 (cell, corner) terms that land on it in a fixed order: no atomics, two calls leave the same bits.
-// A phantom class of the tail window is never loaded, evaluated or stored.
-constexpr int kCellTH = 7, kCellTW = 15, kCellThreads = 256;
-constexpr int kCellCount = (kCellTH + 1) * (kCellTW + 1);
+// The gather is cell_gather.h's, in windows of kCellCT classes; what a destination pixel contributes per class is here.
 constexpr int kCellCT = 20;            // classes per window: 19 in one, 4 x 20 accumulators and corners per lane
 
-template <bool ALIGN, int CT, bool TAIL>
-__device__ __forceinline__ void lovasz_bwd_cells_body(
-    float (*corner)[4][CT + 1], const float* __restrict__ base /* logits of (n, c0) */,
-    const long long* __restrict__ lab, const float* __restrict__ ls, const float* __restrict__ as,
-    const float* __restrict__ table /* of class c0 */, int ignore_index, int C, int c0, int nc, int h, int w, int H, int W,
-    float sh, float sw, int shift, int B, float gs, float* __restrict__ out /* dlogits of (n, c0) */, int I0, int J0) {
-    const int tid = threadIdx.x;
-    const long long plane = (long long)h * w;
-    const int cell = tid >> 1, part = tid & 1;
-    if (cell < kCellCount) {
-        const int ci = I0 - 1 + cell / (kCellTW + 1), cj = J0 - 1 + cell % (kCellTW + 1);
-        float a00[CT], a01[CT], a10[CT], a11[CT];
-#pragma unroll
-        for (int c = 0; c < CT; ++c) a00[c] = a01[c] = a10[c] = a11[c] = 0.f;
-        if (ci >= 0 && ci < h && cj >= 0 && cj < w) {
-            const int i1 = ci + (ci < h - 1 ? 1 : 0), j1 = cj + (cj < w - 1 ? 1 : 0);
-            float p00[CT], p01[CT], p10[CT], p11[CT];
-#pragma unroll
-            for (int c = 0; c < CT; ++c) {
-                p00[c] = p01[c] = p10[c] = p11[c] = 0.f;
-                if (TAIL && c >= nc) continue;
-                const float* p = base + c * plane;
-                p00[c] = p[ci * w + cj]; p01[c] = p[ci * w + j1];
-                p10[c] = p[i1 * w + cj]; p11[c] = p[i1 * w + j1];
-            }
-            int ylo, yhi, xlo, xhi;
-            dst_range<ALIGN>(ci, sh, H, ylo, yhi);
-            dst_range<ALIGN>(cj, sw, W, xlo, xhi);
-            for (int Y = ylo + part; Y <= yhi; Y += 2) {
-                const Lerp Lh = lerp_of<ALIGN>(Y, sh, h);
-                if (Lh.i0 != ci) continue;
-                for (int X = xlo; X <= xhi; ++X) {
-                    const Lerp Lw = lerp_of<ALIGN>(X, sw, w);
-                    if (Lw.i0 != cj) continue;
-                    const long long q = (long long)Y * W + X;
-                    const long long label = lab[q];
-                    if (!label_valid(label, C, ignore_index)) continue;
-                    const float lq = ls[q], Aq = as[q];
-                    const long long lrel = label - c0;      // the label's position in this window, if it is in it
-                    const float w00 = Lh.l0 * Lw.l0, w01 = Lh.l0 * Lw.l1;
-                    const float w10 = Lh.l1 * Lw.l0, w11 = Lh.l1 * Lw.l1;
-#pragma unroll
-                    for (int c = 0; c < CT; ++c) {
-                        if (TAIL && c >= nc) continue;
-                        const bool fg = lrel == c;
-                        const Term r = lovasz_term(p00[c], p01[c], p10[c], p11[c], Lh.l0, Lh.l1, Lw.l0, Lw.l1, lq, fg,
-                                                   shift, B - 1);
-                        const float g = r.p * (coeff_of(table, c, B, r, fg) - Aq);
-                        a00[c] += w00 * g; a01[c] += w01 * g;
-                        a10[c] += w10 * g; a11[c] += w11 * g;
-                    }
-                }
-            }
-        }
-        // the two lanes of a cell: even rows + odd rows, always in that order
-#pragma unroll
-        for (int c = 0; c < CT; ++c) {
-            a00[c] += __shfl_xor(a00[c], 1, 64); a01[c] += __shfl_xor(a01[c], 1, 64);
-            a10[c] += __shfl_xor(a10[c], 1, 64); a11[c] += __shfl_xor(a11[c], 1, 64);
-        }
-        if (part == 0) {
-#pragma unroll
-            for (int c = 0; c < CT; ++c) {
-                corner[cell][0][c] = a00[c]; corner[cell][1][c] = a01[c];
-                corner[cell][2][c] = a10[c]; corner[cell][3][c] = a11[c];
-            }
-        }
-    }
-    __syncthreads();
-    // output (i, j) collects corner (a, b) of cell (ci, cj) wherever ci + (a && ci < h-1) == i and
-    // cj + (b && cj < w-1) == j; candidates are ci in {i-1, i}, cj in {j-1, j}; fixed visiting order
-    for (int o = tid; o < kCellTH * kCellTW * nc; o += kCellThreads) {
-        const int c = o / (kCellTH * kCellTW);
-        const int r = o - c * (kCellTH * kCellTW);
-        const int li = r / kCellTW, lj = r - li * kCellTW;
-        const int i = I0 + li, j = J0 + lj;
-        if (i >= h || j >= w) continue;
-        float acc = 0.f;
-#pragma unroll
-        for (int di = 0; di < 2; ++di) {
-            const int ci = i - 1 + di;
-            if (ci < 0) continue;
-#pragma unroll
-            for (int a = 0; a < 2; ++a) {
-                if (ci + ((a && ci < h - 1) ? 1 : 0) != i) continue;
-#pragma unroll
-                for (int dj = 0; dj < 2; ++dj) {
-                    const int cj = j - 1 + dj;
-                    if (cj < 0) continue;
-#pragma unroll
-                    for (int bb = 0; bb < 2; ++bb) {
-                        if (cj + ((bb && cj < w - 1) ? 1 : 0) != j) continue;
-                        acc += corner[(li + di) * (kCellTW + 1) + (lj + dj)][a * 2 + bb][c];
-                    }
-                }
-            }
-        }
-        out[c * plane + (long long)i * w + j] = acc * gs;
-    }
-}
+struct LovaszCellLoss {
+    const long long* __restrict__ lab;      // of the image
+    const float* __restrict__ ls;
+    const float* __restrict__ as;
+    const float* __restrict__ table;        // of class c0
+    int ignore_index, C, c0, shift, B;
 
-// block <-> (image, tile row, tile column, class window); the window varies fastest, so the blocks that read the same
-// tile's labels, lse and A are neighbours in dispatch order
+    struct Pixel {
+        float pw, lq, Aq;
+        long long lrel;                     // the label's position in this window, if it is in it
+    };
+
+    __device__ __forceinline__ bool pixel(long long q, Pixel& px) const {
+        const long long label = lab[q];
+        if (!label_valid(label, C, ignore_index)) return false;
+        px.pw = 1.f;
+        px.lq = ls[q];
+        px.Aq = as[q];
+        px.lrel = label - c0;
+        return true;
+    }
+
+    __device__ __forceinline__ float grad(const Pixel& px, int c, float v00, float v01, float v10, float v11,
+                                          const Lerp& Lh, const Lerp& Lw) const {
+        const bool fg = px.lrel == c;
+        const Term r = lovasz_term(v00, v01, v10, v11, Lh.l0, Lh.l1, Lw.l0, Lw.l1, px.lq, fg, shift, B - 1);
+        return r.p * (coeff_of(table, c, B, r, fg) - px.Aq);
+    }
+};
+
 template <bool ALIGN, int CT>
 __global__ void __launch_bounds__(kCellThreads, 2)
-lovasz_bwd_cells_kernel(const float* __restrict__ logits, const long long* __restrict__ labels, int ignore_index, int N,
-                        int C, int h, int w, int H, int W, float sh, float sw, int log2B, const float* __restrict__ lse,
+lovasz_bwd_cells_kernel(const float* __restrict__ logits, const long long* __restrict__ labels, int ignore_index, int C,
+                        int h, int w, int H, int W, float sh, float sw, int log2B, const float* __restrict__ lse,
                         const float* __restrict__ table, const float* __restrict__ asum,
                         const float* __restrict__ grad_scale, float* __restrict__ dlogits, int tiles_w, int tiles_h,
                         int chunks) {
     __shared__ float corner[kCellCount][4][CT + 1];
-    const int B = 1 << log2B, shift = kQ - log2B;
-    long long b = blockIdx.x;
-    const int chunk = (int)(b % chunks);
-    b /= chunks;
-    const int tw = (int)(b % tiles_w);
-    b /= tiles_w;
-    const int th = (int)(b % tiles_h);
-    const int n = (int)(b / tiles_h);
-    const int c0 = chunk * CT;
-    const int nc = C - c0 < CT ? C - c0 : CT;
-    const long long plane = (long long)h * w, img = (long long)n * H * W;
-    const float* base = logits + ((long long)n * C + c0) * plane;
-    float* out = dlogits + ((long long)n * C + c0) * plane;
-    const float* tab = table + (long long)c0 * B * 2;
-    const float gs = grad_scale[0];
-    if (nc == CT)
-        lovasz_bwd_cells_body<ALIGN, CT, false>(corner, base, labels + img, lse + img, asum + img, tab, ignore_index, C,
-                                                c0, nc, h, w, H, W, sh, sw, shift, B, gs, out, th * kCellTH,
-                                                tw * kCellTW);
-    else
-        lovasz_bwd_cells_body<ALIGN, CT, true>(corner, base, labels + img, lse + img, asum + img, tab, ignore_index, C,
-                                               c0, nc, h, w, H, W, sh, sw, shift, B, gs, out, th * kCellTH,
-                                               tw * kCellTW);
+    const int B = 1 << log2B;
+    const CellBlock blk = cell_block<CT, false>(C, tiles_w, tiles_h, chunks);
+    const long long img = (long long)blk.n * H * W;
+    const long long first = ((long long)blk.n * C + blk.c0) * h * w;      // (n, c0) of logits and dlogits
+    const LovaszCellLoss loss{labels + img, lse + img, asum + img, table + (long long)blk.c0 * B * 2,
+                              ignore_index,  C,         blk.c0,     kQ - log2B,
+                              B};
+    cell_gather<ALIGN, CT, false>(corner, logits + first, loss, blk, h, w, H, W, sh, sw, grad_scale[0], dlogits + first);
 }
 
 // ------------------------------------------------------------------------------------------------ error dump
@@ -525,12 +390,10 @@ extern "C" int dcfp_lovasz_hist_f32(const float* logits, const int64_t* labels, 
     const int chunk = kHistSlots / bins;                   // classes whose accumulators share the LDS: 64 ... 1
     const float sh = host_scale(h, H, align_corners), sw = host_scale(w, W, align_corners);
     const long long* lab = reinterpret_cast<const long long*>(labels);
-    if (align_corners)
-        hipLaunchKernelGGL(lovasz_hist_kernel<true>, dim3(blocks), dim3(kHistThreads), 0, st, logits, lab, ignore_index,
-                           N, C, h, w, H, W, sh, sw, log2B, chunk, tile, lse, ws.SF, ws.SB, ws.nF, ws.nB);
-    else
-        hipLaunchKernelGGL(lovasz_hist_kernel<false>, dim3(blocks), dim3(kHistThreads), 0, st, logits, lab, ignore_index,
-                           N, C, h, w, H, W, sh, sw, log2B, chunk, tile, lse, ws.SF, ws.SB, ws.nF, ws.nB);
+    with_align(align_corners, [&](auto A) {
+        hipLaunchKernelGGL(lovasz_hist_kernel<A.value>, dim3(blocks), dim3(kHistThreads), 0, st, logits, lab,
+                           ignore_index, N, C, h, w, H, W, sh, sw, log2B, chunk, tile, lse, ws.SF, ws.SB, ws.nF, ws.nB);
+    });
     DCFP_RETURN_LAUNCH();
 }
 
@@ -557,28 +420,19 @@ extern "C" int dcfp_lovasz_bwd_f32(const float* logits, const int64_t* labels, i
     const int log2B = log2_bins(bins);
     if (!logits || !labels || !lse || !weights || !grad_scale || !asum || !dlogits || log2B < 0) return DCFP_E_BADDESC;
     if (const int e = check_shape(N, C, h, w, H, W)) return e;
-    if ((long long)N * ((h + kCellTH - 1) / kCellTH) * ((w + kCellTW - 1) / kCellTW) * ((C + kCellCT - 1) / kCellCT) >
-        0x7fffffffLL)
-        return DCFP_E_UNSUPPORTED;
+    const int tiles_h = cell_tiles_h(h), tiles_w = cell_tiles_w(w), chunks = (C + kCellCT - 1) / kCellCT;
+    const long long cell_blocks = (long long)N * tiles_h * tiles_w * chunks;
+    if (cell_blocks > 0x7fffffffLL) return DCFP_E_UNSUPPORTED;
     hipStream_t st = dcfp_s(stream);
     const float sh = host_scale(h, H, align_corners), sw = host_scale(w, W, align_corners);
     const long long* lab = reinterpret_cast<const long long*>(labels);
-    const int tiles_h = (h + kCellTH - 1) / kCellTH, tiles_w = (w + kCellTW - 1) / kCellTW;
-    const int chunks = (C + kCellCT - 1) / kCellCT;
-    const unsigned g1 = grid_for((long long)N * H * W), g2 = (unsigned)((long long)N * tiles_h * tiles_w * chunks);
-    if (align_corners) {
-        hipLaunchKernelGGL(lovasz_asum_kernel<true>, dim3(g1), dim3(kThreads), 0, st, logits, lab, ignore_index, N, C, h,
-                           w, H, W, sh, sw, log2B, lse, weights, asum);
-        hipLaunchKernelGGL((lovasz_bwd_cells_kernel<true, kCellCT>), dim3(g2), dim3(kCellThreads), 0, st, logits, lab,
-                           ignore_index, N, C, h, w, H, W, sh, sw, log2B, lse, weights, asum, grad_scale, dlogits, tiles_w,
-                           tiles_h, chunks);
-    } else {
-        hipLaunchKernelGGL(lovasz_asum_kernel<false>, dim3(g1), dim3(kThreads), 0, st, logits, lab, ignore_index, N, C, h,
-                           w, H, W, sh, sw, log2B, lse, weights, asum);
-        hipLaunchKernelGGL((lovasz_bwd_cells_kernel<false, kCellCT>), dim3(g2), dim3(kCellThreads), 0, st, logits, lab,
-                           ignore_index, N, C, h, w, H, W, sh, sw, log2B, lse, weights, asum, grad_scale, dlogits, tiles_w,
-                           tiles_h, chunks);
-    }
+    with_align(align_corners, [&](auto A) {
+        hipLaunchKernelGGL(lovasz_asum_kernel<A.value>, dim3(grid_for((long long)N * H * W)), dim3(kThreads), 0, st,
+                           logits, lab, ignore_index, N, C, h, w, H, W, sh, sw, log2B, lse, weights, asum);
+        hipLaunchKernelGGL((lovasz_bwd_cells_kernel<A.value, kCellCT>), dim3((unsigned)cell_blocks), dim3(kCellThreads),
+                           0, st, logits, lab, ignore_index, C, h, w, H, W, sh, sw, log2B, lse, weights, asum,
+                           grad_scale, dlogits, tiles_w, tiles_h, chunks);
+    });
     DCFP_RETURN_LAUNCH();
 }
 
@@ -588,12 +442,9 @@ extern "C" int dcfp_lovasz_errors_u32(const float* logits, const int64_t* labels
     if (const int e = check_shape(N, C, h, w, H, W)) return e;
     const float sh = host_scale(h, H, align_corners), sw = host_scale(w, W, align_corners);
     const long long* lab = reinterpret_cast<const long long*>(labels);
-    const unsigned g = grid_for((long long)N * H * W);
-    if (align_corners)
-        hipLaunchKernelGGL(lovasz_errors_kernel<true>, dim3(g), dim3(kThreads), 0, dcfp_s(stream), logits, lab,
-                           ignore_index, N, C, h, w, H, W, sh, sw, errors);
-    else
-        hipLaunchKernelGGL(lovasz_errors_kernel<false>, dim3(g), dim3(kThreads), 0, dcfp_s(stream), logits, lab,
-                           ignore_index, N, C, h, w, H, W, sh, sw, errors);
+    with_align(align_corners, [&](auto A) {
+        hipLaunchKernelGGL(lovasz_errors_kernel<A.value>, dim3(grid_for((long long)N * H * W)), dim3(kThreads), 0,
+                           dcfp_s(stream), logits, lab, ignore_index, N, C, h, w, H, W, sh, sw, errors);
+    });
     DCFP_RETURN_LAUNCH();
 }

@@ -11,6 +11,8 @@
 // Coordinate rules: bilinear.h (ATen's area_pixel_compute_scale / _source_index).
 #include "common.h"
 #include "bilinear.h"
+#include "cell_gather.h"
+#include "upsample_logits.h"
 #include "vote_core.h"
 #include <math.h>
 #include <stdlib.h>
@@ -20,7 +22,9 @@ namespace {
 constexpr int kThreads = dcfp_vote::kThreads;   // 256; the confusion kernels share vote_core.h's bin loops
 constexpr int kLossBlocks = 2048;
 
-using namespace dcfp_bilinear;   // Lerp, lerp_of, host_scale, dst_range, tap_weight (bilinear.h)
+using namespace dcfp_bilinear;   // Lerp, lerp_of, host_scale, with_align, dst_range, tap_weight (bilinear.h);
+                                 // Pix, pix_of, Tap, tap_of, logit_of, logit_at, lse_step (upsample_logits.h)
+using namespace dcfp_cells;      // the cell gather and its tile constants (cell_gather.h)
 
 // ------------------------------------------------------------ plain upsample
 template <bool ALIGN>
@@ -83,26 +87,14 @@ upsample_ce_fwd_kernel(const float* __restrict__ logits, const long long* __rest
     float loss = 0.f, cnt = 0.f;
     for (long long pix = (long long)blockIdx.x * kThreads + threadIdx.x; pix < total;
          pix += (long long)gridDim.x * kThreads) {
-        const int X = (int)(pix % W);
-        const long long t = pix / W;
-        const int Y = (int)(t % H);
-        const int n = (int)(t / H);
-        const Lerp Lh = lerp_of<ALIGN>(Y, sh, h), Lw = lerp_of<ALIGN>(X, sw, w);
-        const int o00 = Lh.i0 * w + Lw.i0, o01 = Lh.i0 * w + Lw.i1;
-        const int o10 = Lh.i1 * w + Lw.i0, o11 = Lh.i1 * w + Lw.i1;
-        const float* base = logits + (long long)n * C * plane;
+        const Pix P = pix_of(pix, H, W);
+        const Tap t = tap_of(lerp_of<ALIGN>(P.Y, sh, h), lerp_of<ALIGN>(P.X, sw, w), w);
+        const float* base = logits + (long long)P.n * C * plane;
         const long long label = labels[pix];
         float m = -INFINITY, s = 0.f, zl = 0.f;
         for (int c = 0; c < C; ++c) {
-            const float* p = base + c * plane;
-            const float z = Lh.l0 * (Lw.l0 * p[o00] + Lw.l1 * p[o01]) +
-                            Lh.l1 * (Lw.l0 * p[o10] + Lw.l1 * p[o11]);
-            if (z > m) {
-                s = s * expf(m - z) + 1.f;
-                m = z;
-            } else {
-                s += expf(z - m);
-            }
+            const float z = logit_at(base + c * plane, t);
+            lse_step(z, m, s);
             if (c == label) zl = z;
         }
         const float lse = m + logf(s);
@@ -146,15 +138,18 @@ __global__ void __launch_bounds__(256) loss_final_kernel(const float* __restrict
     }
 }
 
-// thread <-> one element of dlogits[n,c,i,j]
+// dlogits[n,c,i,j] = gs * sum_pix wy wx [pw] (softmax - onehot)   (gather form), thread <-> one element of dlogits.
+// Plain CE: a nullable keep mask and grad_scale[0]; weighted CE: a weight map pw (0 where a pixel does not count) and
+// grad_scale[n].  A pixel's factor is wx for plain and (wx * pw) for weighted: with an all-ones map the two are the
+// same bits.
 template <bool ALIGN>
 __global__ void __launch_bounds__(kThreads)
 upsample_ce_bwd_kernel(const float* __restrict__ logits, const long long* __restrict__ labels,
-                       const uint8_t* __restrict__ keep, int ignore_index, int N, int C, int h,
-                       int w, int H, int W, float sh, float sw, const float* __restrict__ lse,
-                       const float* __restrict__ grad_scale, float* __restrict__ dlogits) {
+                       const uint8_t* __restrict__ keep /* nullable */, const float* __restrict__ pix_weight /* nullable */,
+                       int ignore_index, int N, int C, int h, int w, int H, int W, float sh, float sw,
+                       const float* __restrict__ lse, const float* __restrict__ grad_scale,
+                       int scale_per_image /* grad_scale[n] instead of grad_scale[0] */, float* __restrict__ dlogits) {
     const long long total = (long long)N * C * h * w;
-    const float gs = grad_scale[0];
     for (long long idx = (long long)blockIdx.x * kThreads + threadIdx.x; idx < total;
          idx += (long long)gridDim.x * kThreads) {
         const int j = (int)(idx % w);
@@ -167,6 +162,7 @@ upsample_ce_bwd_kernel(const float* __restrict__ logits, const long long* __rest
         const long long* lab = labels + (long long)n * H * W;
         const float* ls = lse + (long long)n * H * W;
         const uint8_t* kp = keep ? keep + (long long)n * H * W : nullptr;
+        const float* wp = pix_weight ? pix_weight + (long long)n * H * W : nullptr;
         int ylo, yhi, xlo, xhi;
         dst_range<ALIGN>(i, sh, H, ylo, yhi);
         dst_range<ALIGN>(j, sw, W, xlo, xhi);
@@ -175,24 +171,25 @@ upsample_ce_bwd_kernel(const float* __restrict__ logits, const long long* __rest
             const Lerp Lh = lerp_of<ALIGN>(Y, sh, h);
             const float wy = tap_weight(Lh, i);
             if (wy == 0.f) continue;
-            const float* r0 = p + Lh.i0 * w;
-            const float* r1 = p + Lh.i1 * w;
             float row = 0.f;
             for (int X = xlo; X <= xhi; ++X) {
                 const Lerp Lw = lerp_of<ALIGN>(X, sw, w);
-                const float wx = tap_weight(Lw, j);
+                float wx = tap_weight(Lw, j);
                 if (wx == 0.f) continue;
                 const long long q = (long long)Y * W + X;
                 const long long label = lab[q];
                 if (label == ignore_index || (kp && !kp[q])) continue;
-                const float z = Lh.l0 * (Lw.l0 * r0[Lw.i0] + Lw.l1 * r0[Lw.i1]) +
-                                Lh.l1 * (Lw.l0 * r1[Lw.i0] + Lw.l1 * r1[Lw.i1]);
-                const float prob = expf(z - ls[q]);
-                row += wx * (prob - (label == c ? 1.f : 0.f));
+                if (wp) {
+                    const float pwq = wp[q];
+                    if (pwq == 0.f) continue;
+                    wx *= pwq;
+                }
+                const float z = logit_at(p, tap_of(Lh, Lw, w));
+                row += wx * (expf(z - ls[q]) - (label == c ? 1.f : 0.f));
             }
             acc += wy * row;
         }
-        dlogits[idx] = acc * gs;
+        dlogits[idx] = acc * grad_scale[scale_per_image ? n : 0];
     }
 }
 
@@ -248,16 +245,11 @@ upsample_ce_bwd_classes_kernel(const float* __restrict__ logits, const long long
                     if (pwq == 0.f) continue;
                     wgt *= pwq;
                 }
-                const int o00 = Lh.i0 * w + Lw.i0, o01 = Lh.i0 * w + Lw.i1;
-                const int o10 = Lh.i1 * w + Lw.i0, o11 = Lh.i1 * w + Lw.i1;
+                const Tap t = tap_of(Lh, Lw, w);
                 const float lq = ls[q];
 #pragma unroll
-                for (int c = 0; c < CT; ++c) {
-                    const float* p = base + c * plane;
-                    const float z = Lh.l0 * (Lw.l0 * p[o00] + Lw.l1 * p[o01]) +
-                                    Lh.l1 * (Lw.l0 * p[o10] + Lw.l1 * p[o11]);
-                    acc[c] += wgt * (expf(z - lq) - (label == c ? 1.f : 0.f));
-                }
+                for (int c = 0; c < CT; ++c)
+                    acc[c] += wgt * (expf(logit_at(base + c * plane, t) - lq) - (label == c ? 1.f : 0.f));
             }
         }
 #pragma unroll
@@ -273,150 +265,18 @@ upsample_ce_bwd_classes_kernel(const float* __restrict__ logits, const long long
     }
 }
 
-// The same gradient organised by CELLS (19 classes, the training path).  The cell of a destination pixel is the
-// low-resolution position (i0, j0) its stencil starts at; every destination pixel lies in exactly one cell and
-// touches only that cell's four corners (i0|i1, j0|j1).  The kernel above visits every destination pixel once per
-// corner it touches - four softmax evaluations per pixel; here a lane pair owns a cell, holds the four corner
-// logit vectors in registers, evaluates each of its ~8 x 8 destination pixels ONCE and accumulates the four
-// corner sums (4 x 19 registers).  A workgroup covers a 7 x 15 tile of low-resolution outputs = 8 x 16 cells (one
-// halo row / column above and left is recomputed by the neighbour: 1.2x instead of 4x), parks the corner sums in
-// LDS and gathers, per output and class, the <= 4 (cell, corner) terms that land on it in a fixed order - no
-// atomics, deterministic.  Interpolation and softmax expressions are the forward's.
-constexpr int kCellTH = 7, kCellTW = 15, kCellThreads = 256;      // 8 x 16 cells x 2 lanes: four full waves, two
-                                                                   // workgroups per CU at 219 registers (an 8 x 16 tile
-                                                                   // with 320 threads left 3 of 8 wave slots empty)
-constexpr int kCellCount = (kCellTH + 1) * (kCellTW + 1);
-
-template <bool ALIGN, int CT>
-__global__ void __launch_bounds__(kCellThreads, 2)
-upsample_ce_bwd_cells_kernel(const float* __restrict__ logits, const long long* __restrict__ labels,
-                             const uint8_t* __restrict__ keep, int ignore_index, int N, int h, int w, int H,
-                             int W, float sh, float sw, const float* __restrict__ lse,
-                             const float* __restrict__ grad_scale, float* __restrict__ dlogits,
-                             const float* __restrict__ pix_weight, int scale_per_image, int tiles_w, int tiles_h) {
-    __shared__ float corner[kCellCount][4][CT + 1];
-    const int tid = threadIdx.x;
-    int b = blockIdx.x;
-    const int tw = b % tiles_w;
-    b /= tiles_w;
-    const int th = b % tiles_h;
-    const int n = b / tiles_h;
-    const int I0 = th * kCellTH, J0 = tw * kCellTW;
-    const long long plane = (long long)h * w;
-    const float* base = logits + (long long)n * CT * plane;
-    const long long* lab = labels + (long long)n * H * W;
-    const float* ls = lse + (long long)n * H * W;
-    const uint8_t* kp = keep ? keep + (long long)n * H * W : nullptr;
-    const float* wp = pix_weight ? pix_weight + (long long)n * H * W : nullptr;
-
-    const int cell = tid >> 1, part = tid & 1;
-    if (cell < kCellCount) {
-        const int ci = I0 - 1 + cell / (kCellTW + 1), cj = J0 - 1 + cell % (kCellTW + 1);
-        float a00[CT], a01[CT], a10[CT], a11[CT];
-#pragma unroll
-        for (int c = 0; c < CT; ++c) a00[c] = a01[c] = a10[c] = a11[c] = 0.f;
-        if (ci >= 0 && ci < h && cj >= 0 && cj < w) {
-            const int i1 = ci + (ci < h - 1 ? 1 : 0), j1 = cj + (cj < w - 1 ? 1 : 0);
-            float p00[CT], p01[CT], p10[CT], p11[CT];
-#pragma unroll
-            for (int c = 0; c < CT; ++c) {
-                const float* p = base + c * plane;
-                p00[c] = p[ci * w + cj]; p01[c] = p[ci * w + j1];
-                p10[c] = p[i1 * w + cj]; p11[c] = p[i1 * w + j1];
-            }
-            int ylo, yhi, xlo, xhi;
-            dst_range<ALIGN>(ci, sh, H, ylo, yhi);
-            dst_range<ALIGN>(cj, sw, W, xlo, xhi);
-            for (int Y = ylo + part; Y <= yhi; Y += 2) {
-                const Lerp Lh = lerp_of<ALIGN>(Y, sh, h);
-                if (Lh.i0 != ci) continue;
-                for (int X = xlo; X <= xhi; ++X) {
-                    const Lerp Lw = lerp_of<ALIGN>(X, sw, w);
-                    if (Lw.i0 != cj) continue;
-                    const long long q = (long long)Y * W + X;
-                    const long long label = lab[q];
-                    if (label == ignore_index || (kp && !kp[q])) continue;
-                    float pw = 1.f;
-                    if (wp) {
-                        pw = wp[q];
-                        if (pw == 0.f) continue;
-                    }
-                    const float lq = ls[q];
-                    const float w00 = Lh.l0 * Lw.l0 * pw, w01 = Lh.l0 * Lw.l1 * pw;
-                    const float w10 = Lh.l1 * Lw.l0 * pw, w11 = Lh.l1 * Lw.l1 * pw;
-#pragma unroll
-                    for (int c = 0; c < CT; ++c) {
-                        const float z = Lh.l0 * (Lw.l0 * p00[c] + Lw.l1 * p01[c]) +
-                                        Lh.l1 * (Lw.l0 * p10[c] + Lw.l1 * p11[c]);
-                        const float g = expf(z - lq) - (label == c ? 1.f : 0.f);
-                        a00[c] += w00 * g; a01[c] += w01 * g;
-                        a10[c] += w10 * g; a11[c] += w11 * g;
-                    }
-                }
-            }
-        }
-        // the two lanes of a cell: even rows + odd rows, always in that order
-#pragma unroll
-        for (int c = 0; c < CT; ++c) {
-            a00[c] += __shfl_xor(a00[c], 1, 64); a01[c] += __shfl_xor(a01[c], 1, 64);
-            a10[c] += __shfl_xor(a10[c], 1, 64); a11[c] += __shfl_xor(a11[c], 1, 64);
-        }
-        if (part == 0) {
-#pragma unroll
-            for (int c = 0; c < CT; ++c) {
-                corner[cell][0][c] = a00[c]; corner[cell][1][c] = a01[c];
-                corner[cell][2][c] = a10[c]; corner[cell][3][c] = a11[c];
-            }
-        }
-    }
-    __syncthreads();
-    // gather: output (i, j) collects corner (a, b) of cell (ci, cj) wherever ci + (a && ci < h-1) == i and
-    // cj + (b && cj < w-1) == j; candidates are ci in {i-1, i}, cj in {j-1, j}; fixed visiting order
-    const float gs = grad_scale[scale_per_image ? n : 0];
-    for (int o = tid; o < kCellTH * kCellTW * CT; o += kCellThreads) {
-        const int c = o / (kCellTH * kCellTW);
-        const int r = o - c * (kCellTH * kCellTW);
-        const int li = r / kCellTW, lj = r - li * kCellTW;
-        const int i = I0 + li, j = J0 + lj;
-        if (i >= h || j >= w) continue;
-        float acc = 0.f;
-#pragma unroll
-        for (int di = 0; di < 2; ++di) {
-            const int ci = i - 1 + di;
-            if (ci < 0) continue;
-#pragma unroll
-            for (int a = 0; a < 2; ++a) {
-                if (ci + ((a && ci < h - 1) ? 1 : 0) != i) continue;
-#pragma unroll
-                for (int dj = 0; dj < 2; ++dj) {
-                    const int cj = j - 1 + dj;
-                    if (cj < 0) continue;
-#pragma unroll
-                    for (int bb = 0; bb < 2; ++bb) {
-                        if (cj + ((bb && cj < w - 1) ? 1 : 0) != j) continue;
-                        acc += corner[(li + di) * (kCellTW + 1) + (lj + dj)][a * 2 + bb][c];
-                    }
-                }
-            }
-        }
-        dlogits[((long long)n * CT + c) * plane + (long long)i * w + j] = acc * gs;
-    }
-}
-
-// The cell kernel for any class count (Pascal-Context 59, ADE 150, COCO-Stuff 171): once the per-pixel LSE is
-// known the softmax factorises over classes, so a workgroup runs the cell kernel's arithmetic on a class WINDOW
-// [c0, c0 + CT) of the C-class tensor, c0 = chunk * CT.  The class-independent work of a destination pixel (stencils,
-// label, LSE, weight) is repeated ceil(C / CT) times instead of C times, and each class of a pixel is evaluated once
-// instead of four times.  One launch covers every chunk; the chunk index varies fastest, so the blocks that read the
-// same tile's labels, LSE and weights are neighbours in dispatch order.  The tail chunk holds nc = C - c0 < CT real
-// classes: a phantom class is never loaded, never evaluated (no expf term exists for it) and never stored.  Full
-// chunks run the body without any of those guards (TAIL = false); the branch between the two is block-uniform.
-// Summation order per output: the 19-class kernel's (even rows + odd rows per cell, then the <= 4 (cell, corner)
-// terms in a fixed order) - no atomics, run-to-run bit-identical, and a chunk's result does not depend on any other
-// chunk's logits.  The 19-class instantiation above is left as it is: its code object is the training path's.
+// The same gradient organised by interpolation CELLS (cell_gather.h): each destination pixel is evaluated once per
+// window of CT classes instead of once per class and corner (four softmax evaluations), and the class-independent work
+// of a pixel - stencils, label, LSE, weight - is repeated ceil(C / CT) times instead of C times.  Once the per-pixel LSE
+// is known the softmax factorises over classes, so a workgroup works on the window [c0, c0 + CT) of the C-class tensor
+// alone; one launch covers every window.  Interpolation and softmax expressions are the forward's.
 //
-// Budget at CT = 20: 8 x 20 corner / accumulator registers per lane (the 19-class kernel: 8 x 19, 219 VGPRs of the
-// 256 that two workgroups of four waves per CU leave each lane), LDS 128 x 4 x 21 x 4 B = 43 KB per workgroup.
+// Two instantiations: CT = kCeChunk for any class count (Pascal-Context 59, ADE 150, COCO-Stuff 171), and CT = 19 with
+// WHOLE set, where Cityscapes' classes are the one full window (the "cells19" route of the training path: no chunk
+// decode, never a tail).  Times of both against the separate 19-class kernel this replaced: DESIGN §13a.
+//
+// Budget: 8 x CT corner / accumulator registers per lane (216 VGPRs at 19, 211 at 20, of the 256 that two workgroups
+// of four waves per CU leave each lane), LDS 128 x 4 x (CT + 1) x 4 B = 40 KB at 19, 42 KB at 20 per workgroup.
 #ifndef DCFP_CE_CHUNK
 #define DCFP_CE_CHUNK 20          // the chunk width; the candidates' times are in DESIGN §13a
 #endif
@@ -424,141 +284,68 @@ constexpr int kCeChunk = DCFP_CE_CHUNK;
 constexpr int kCeChunkMinC = 2;   // the smallest class count timed; faster than the per-output kernels from there on
                                   // (DESIGN §13a).  C == 1 (gradient identically zero) stays where it was
 
-template <bool ALIGN, int CT, bool TAIL>
-__device__ __forceinline__ void ce_bwd_cells_chunk_body(
-    float (*corner)[4][CT + 1], const float* __restrict__ base /* logits of (n, c0) */,
-    const long long* __restrict__ lab, const uint8_t* __restrict__ kp, const float* __restrict__ wp,
-    const float* __restrict__ ls, int ignore_index, int c0, int nc, int h, int w, int H, int W, float sh, float sw,
-    float gs, float* __restrict__ out /* dlogits of (n, c0) */, int I0, int J0) {
-    const int tid = threadIdx.x;
-    const long long plane = (long long)h * w;
-    const int cell = tid >> 1, part = tid & 1;
-    if (cell < kCellCount) {
-        const int ci = I0 - 1 + cell / (kCellTW + 1), cj = J0 - 1 + cell % (kCellTW + 1);
-        float a00[CT], a01[CT], a10[CT], a11[CT];
-#pragma unroll
-        for (int c = 0; c < CT; ++c) a00[c] = a01[c] = a10[c] = a11[c] = 0.f;
-        if (ci >= 0 && ci < h && cj >= 0 && cj < w) {
-            const int i1 = ci + (ci < h - 1 ? 1 : 0), j1 = cj + (cj < w - 1 ? 1 : 0);
-            float p00[CT], p01[CT], p10[CT], p11[CT];
-#pragma unroll
-            for (int c = 0; c < CT; ++c) {
-                p00[c] = p01[c] = p10[c] = p11[c] = 0.f;
-                if (TAIL && c >= nc) continue;
-                const float* p = base + c * plane;
-                p00[c] = p[ci * w + cj]; p01[c] = p[ci * w + j1];
-                p10[c] = p[i1 * w + cj]; p11[c] = p[i1 * w + j1];
-            }
-            int ylo, yhi, xlo, xhi;
-            dst_range<ALIGN>(ci, sh, H, ylo, yhi);
-            dst_range<ALIGN>(cj, sw, W, xlo, xhi);
-            for (int Y = ylo + part; Y <= yhi; Y += 2) {
-                const Lerp Lh = lerp_of<ALIGN>(Y, sh, h);
-                if (Lh.i0 != ci) continue;
-                for (int X = xlo; X <= xhi; ++X) {
-                    const Lerp Lw = lerp_of<ALIGN>(X, sw, w);
-                    if (Lw.i0 != cj) continue;
-                    const long long q = (long long)Y * W + X;
-                    const long long label = lab[q];
-                    if (label == ignore_index || (kp && !kp[q])) continue;
-                    float pw = 1.f;
-                    if (wp) {
-                        pw = wp[q];
-                        if (pw == 0.f) continue;
-                    }
-                    const float lq = ls[q];
-                    const long long lrel = label - c0;      // the label's position in this window, if it is in it
-                    const float w00 = Lh.l0 * Lw.l0 * pw, w01 = Lh.l0 * Lw.l1 * pw;
-                    const float w10 = Lh.l1 * Lw.l0 * pw, w11 = Lh.l1 * Lw.l1 * pw;
-#pragma unroll
-                    for (int c = 0; c < CT; ++c) {
-                        if (TAIL && c >= nc) continue;
-                        const float z = Lh.l0 * (Lw.l0 * p00[c] + Lw.l1 * p01[c]) +
-                                        Lh.l1 * (Lw.l0 * p10[c] + Lw.l1 * p11[c]);
-                        const float g = expf(z - lq) - (lrel == c ? 1.f : 0.f);
-                        a00[c] += w00 * g; a01[c] += w01 * g;
-                        a10[c] += w10 * g; a11[c] += w11 * g;
-                    }
-                }
-            }
-        }
-        // the two lanes of a cell: even rows + odd rows, always in that order
-#pragma unroll
-        for (int c = 0; c < CT; ++c) {
-            a00[c] += __shfl_xor(a00[c], 1, 64); a01[c] += __shfl_xor(a01[c], 1, 64);
-            a10[c] += __shfl_xor(a10[c], 1, 64); a11[c] += __shfl_xor(a11[c], 1, 64);
-        }
-        if (part == 0) {
-#pragma unroll
-            for (int c = 0; c < CT; ++c) {
-                corner[cell][0][c] = a00[c]; corner[cell][1][c] = a01[c];
-                corner[cell][2][c] = a10[c]; corner[cell][3][c] = a11[c];
-            }
-        }
-    }
-    __syncthreads();
-    // gather, as in the 19-class kernel, over the nc real classes of the window
-    for (int o = tid; o < kCellTH * kCellTW * nc; o += kCellThreads) {
-        const int c = o / (kCellTH * kCellTW);
-        const int r = o - c * (kCellTH * kCellTW);
-        const int li = r / kCellTW, lj = r - li * kCellTW;
-        const int i = I0 + li, j = J0 + lj;
-        if (i >= h || j >= w) continue;
-        float acc = 0.f;
-#pragma unroll
-        for (int di = 0; di < 2; ++di) {
-            const int ci = i - 1 + di;
-            if (ci < 0) continue;
-#pragma unroll
-            for (int a = 0; a < 2; ++a) {
-                if (ci + ((a && ci < h - 1) ? 1 : 0) != i) continue;
-#pragma unroll
-                for (int dj = 0; dj < 2; ++dj) {
-                    const int cj = j - 1 + dj;
-                    if (cj < 0) continue;
-#pragma unroll
-                    for (int bb = 0; bb < 2; ++bb) {
-                        if (cj + ((bb && cj < w - 1) ? 1 : 0) != j) continue;
-                        acc += corner[(li + di) * (kCellTW + 1) + (lj + dj)][a * 2 + bb][c];
-                    }
-                }
-            }
-        }
-        out[c * plane + (long long)i * w + j] = acc * gs;
-    }
-}
+// what a destination pixel contributes to class c0 + c: pw * (softmax - onehot).
+//
+// ROUNDING19 spells out how z is rounded in the 19-class instantiation.  With contraction left to the compiler, which of
+// the two products of a row w0 * v00 + w1 * v01 is fused into the add depends on the code around the expression, and
+// the 19-class kernel, when it was a kernel of its own, came out as fma(w0, v00, w1 * v01) per row and an unfused
+// h0 * top + h1 * bot, while the chunked kernel, through logit_of(), comes out as fma(w1, v01, w0 * v00) per row.  The
+// training path's gradients keep their bits, so that choice is written down here instead of being left to chance.
+template <bool ROUNDING19>
+struct CeCellLoss {
+    const long long* __restrict__ lab;      // of the image
+    const uint8_t* __restrict__ kp;         // nullable
+    const float* __restrict__ wp;           // GSRL weights, nullable
+    const float* __restrict__ ls;
+    int ignore_index, c0;
 
-template <bool ALIGN, int CT>
+    struct Pixel {
+        float pw, lq;
+        long long lrel;                     // the label's position in this window, if it is in it
+    };
+
+    __device__ __forceinline__ bool pixel(long long q, Pixel& px) const {
+        const long long label = lab[q];
+        if (label == ignore_index || (kp && !kp[q])) return false;
+        px.pw = 1.f;
+        if (wp) {
+            px.pw = wp[q];
+            if (px.pw == 0.f) return false;
+        }
+        px.lq = ls[q];
+        px.lrel = label - c0;
+        return true;
+    }
+
+    __device__ __forceinline__ float grad(const Pixel& px, int c, float v00, float v01, float v10, float v11,
+                                          const Lerp& Lh, const Lerp& Lw) const {
+        float z;
+        if (ROUNDING19) {
+#pragma clang fp contract(off)
+            const float top = __builtin_fmaf(Lw.l0, v00, Lw.l1 * v01), bot = __builtin_fmaf(Lw.l0, v10, Lw.l1 * v11);
+            z = Lh.l0 * top + Lh.l1 * bot;
+        } else {
+            z = logit_of(v00, v01, v10, v11, Lh.l0, Lh.l1, Lw.l0, Lw.l1);
+        }
+        return expf(z - px.lq) - (px.lrel == c ? 1.f : 0.f);
+    }
+};
+
+template <bool ALIGN, int CT, bool WHOLE /* C == CT: the cells19 route */>
 __global__ void __launch_bounds__(kCellThreads, 2)
-upsample_ce_bwd_cells_chunk_kernel(const float* __restrict__ logits, const long long* __restrict__ labels,
-                                   const uint8_t* __restrict__ keep, int ignore_index, int N, int C, int h, int w,
-                                   int H, int W, float sh, float sw, const float* __restrict__ lse,
-                                   const float* __restrict__ grad_scale, float* __restrict__ dlogits,
-                                   const float* __restrict__ pix_weight, int scale_per_image, int tiles_w,
-                                   int tiles_h, int chunks) {
+ce_bwd_cells_kernel(const float* __restrict__ logits, const long long* __restrict__ labels,
+                    const uint8_t* __restrict__ keep, int ignore_index, int C, int h, int w, int H, int W, float sh,
+                    float sw, const float* __restrict__ lse, const float* __restrict__ grad_scale,
+                    float* __restrict__ dlogits, const float* __restrict__ pix_weight, int scale_per_image,
+                    int tiles_w, int tiles_h, int chunks) {
     __shared__ float corner[kCellCount][4][CT + 1];
-    int b = blockIdx.x;
-    const int chunk = b % chunks;
-    b /= chunks;
-    const int tw = b % tiles_w;
-    b /= tiles_w;
-    const int th = b % tiles_h;
-    const int n = b / tiles_h;
-    const int c0 = chunk * CT;
-    const int nc = C - c0 < CT ? C - c0 : CT;
-    const long long plane = (long long)h * w;
-    const long long img = (long long)n * H * W;
-    const float* base = logits + ((long long)n * C + c0) * plane;     // batch stride C * plane, not CT * plane
-    float* out = dlogits + ((long long)n * C + c0) * plane;
-    const uint8_t* kp = keep ? keep + img : nullptr;
-    const float* wp = pix_weight ? pix_weight + img : nullptr;
-    const float gs = grad_scale[scale_per_image ? n : 0];
-    if (nc == CT)
-        ce_bwd_cells_chunk_body<ALIGN, CT, false>(corner, base, labels + img, kp, wp, lse + img, ignore_index, c0, nc,
-                                                  h, w, H, W, sh, sw, gs, out, th * kCellTH, tw * kCellTW);
-    else
-        ce_bwd_cells_chunk_body<ALIGN, CT, true>(corner, base, labels + img, kp, wp, lse + img, ignore_index, c0, nc,
-                                                 h, w, H, W, sh, sw, gs, out, th * kCellTH, tw * kCellTW);
+    const CellBlock blk = cell_block<CT, WHOLE>(C, tiles_w, tiles_h, chunks);
+    const long long img = (long long)blk.n * H * W;
+    const long long first = ((long long)blk.n * C + blk.c0) * h * w;      // (n, c0): batch stride C * plane, not CT
+    const CeCellLoss<WHOLE> loss{labels + img, keep ? keep + img : nullptr, pix_weight ? pix_weight + img : nullptr,
+                          lse + img,    ignore_index,                blk.c0};
+    cell_gather<ALIGN, CT, WHOLE>(corner, logits + first, loss, blk, h, w, H, W, sh, sw,
+                           grad_scale[scale_per_image ? blk.n : 0], dlogits + first);
 }
 
 // OHEM threshold search input (loss/ohem.py:20-33): the reference zooms the full-resolution
@@ -599,9 +386,7 @@ ohem_zoom_kernel(const float* __restrict__ logits, const long long* __restrict__
                     const int Y = y0 + dy, X = x0 + dx;
                     const double wgt = (dy ? ty : 1.0 - ty) * (dx ? tx : 1.0 - tx);
                     if (Y > H - 1 || X > W - 1 || wgt == 0.0) continue;   // mode='constant', cval=0
-                    const Lerp Lh = lerp_of<ALIGN>(Y, sh, h), Lw = lerp_of<ALIGN>(X, sw, w);
-                    const float z = Lh.l0 * (Lw.l0 * p[Lh.i0 * w + Lw.i0] + Lw.l1 * p[Lh.i0 * w + Lw.i1]) +
-                                    Lh.l1 * (Lw.l0 * p[Lh.i1 * w + Lw.i0] + Lw.l1 * p[Lh.i1 * w + Lw.i1]);
+                    const float z = logit_at(p, tap_of(lerp_of<ALIGN>(Y, sh, h), lerp_of<ALIGN>(X, sw, w), w));
                     acc += wgt * (double)expf(z - lse[((long long)n * H + Y) * W + X]);
                 }
             }
@@ -621,27 +406,15 @@ upsample_margin_kernel(const float* __restrict__ logits, int N, int C, int h, in
     const long long plane = (long long)h * w;
     for (long long pix = (long long)blockIdx.x * kThreads + threadIdx.x; pix < total;
          pix += (long long)gridDim.x * kThreads) {
-        const int X = (int)(pix % W);
-        const long long t = pix / W;
-        const int Y = (int)(t % H);
-        const int n = (int)(t / H);
-        const Lerp Lh = lerp_of<ALIGN>(Y, sh, h), Lw = lerp_of<ALIGN>(X, sw, w);
-        const int o00 = Lh.i0 * w + Lw.i0, o01 = Lh.i0 * w + Lw.i1;
-        const int o10 = Lh.i1 * w + Lw.i0, o11 = Lh.i1 * w + Lw.i1;
-        const float* base = logits + (long long)n * C * plane;
-        float m1 = -INFINITY, m2 = -INFINITY, s = 0.f;
+        const Pix P = pix_of(pix, H, W);
+        const Tap t = tap_of(lerp_of<ALIGN>(P.Y, sh, h), lerp_of<ALIGN>(P.X, sw, w), w);
+        const float* base = logits + (long long)P.n * C * plane;
+        float m1 = -INFINITY, m2 = -INFINITY, s = 0.f;      // the running log-sum-exp, and the runner-up m2
         for (int c = 0; c < C; ++c) {
-            const float* p = base + c * plane;
-            const float z = Lh.l0 * (Lw.l0 * p[o00] + Lw.l1 * p[o01]) +
-                            Lh.l1 * (Lw.l0 * p[o10] + Lw.l1 * p[o11]);
-            if (z > m1) {
-                s = s * expf(m1 - z) + 1.f;
-                m2 = m1;
-                m1 = z;
-            } else {
-                s += expf(z - m1);
-                m2 = z > m2 ? z : m2;
-            }
+            const float z = logit_at(base + c * plane, t);
+            const float lower = z > m1 ? m1 : z;            // whichever of (z, m1) is not the maximum after this step
+            lse_step(z, m1, s);
+            m2 = lower > m2 ? lower : m2;
         }
         // p1 = exp(m1 - lse) = 1/s ; p2 = exp(m2 - m1)/s
         margin[pix] = (1.f - (C > 1 ? expf(m2 - m1) : 0.f)) / s;
@@ -688,16 +461,12 @@ upsample_wce_fwd_kernel(const float* __restrict__ logits, const long long* __res
          q += (long long)gridDim.x * kThreads) {
         const int X = (int)(q % W), Y = (int)(q / W);
         const long long pix = n * HWl + q;
-        const Lerp Lh = lerp_of<ALIGN>(Y, sh, h), Lw = lerp_of<ALIGN>(X, sw, w);
-        const int o00 = Lh.i0 * w + Lw.i0, o01 = Lh.i0 * w + Lw.i1;
-        const int o10 = Lh.i1 * w + Lw.i0, o11 = Lh.i1 * w + Lw.i1;
+        const Tap t = tap_of(lerp_of<ALIGN>(Y, sh, h), lerp_of<ALIGN>(X, sw, w), w);
         const long long label = labels[pix];
         float m = -INFINITY, s = 0.f, zl = 0.f;
         for (int c = 0; c < C; ++c) {
-            const float* p = base + c * plane;
-            const float z = Lh.l0 * (Lw.l0 * p[o00] + Lw.l1 * p[o01]) +
-                            Lh.l1 * (Lw.l0 * p[o10] + Lw.l1 * p[o11]);
-            if (z > m) { s = s * expf(m - z) + 1.f; m = z; } else { s += expf(z - m); }
+            const float z = logit_at(base + c * plane, t);
+            lse_step(z, m, s);
             if (c == label) zl = z;
         }
         const float lse = m + logf(s);
@@ -726,55 +495,6 @@ __global__ void wce_final_kernel(const float* __restrict__ part, int nblocks, fl
     out[2 * n + 1] = (float)b;
 }
 
-// dlogits[n,c,i,j] = gs[n] * sum_pix wt * pw[pix] * (softmax - onehot)   (gather form)
-template <bool ALIGN>
-__global__ void __launch_bounds__(kThreads)
-upsample_wce_bwd_kernel(const float* __restrict__ logits, const long long* __restrict__ labels,
-                        const float* __restrict__ pw, int ignore_index, int N, int C, int h, int w,
-                        int H, int W, float sh, float sw, const float* __restrict__ lse,
-                        const float* __restrict__ gs, float* __restrict__ dlogits) {
-    const long long total = (long long)N * C * h * w;
-    for (long long idx = (long long)blockIdx.x * kThreads + threadIdx.x; idx < total;
-         idx += (long long)gridDim.x * kThreads) {
-        const int j = (int)(idx % w);
-        long long t = idx / w;
-        const int i = (int)(t % h);
-        t /= h;
-        const int c = (int)(t % C);
-        const int n = (int)(t / C);
-        const float* p = logits + ((long long)n * C + c) * h * w;
-        const long long* lab = labels + (long long)n * H * W;
-        const float* ls = lse + (long long)n * H * W;
-        const float* wp = pw + (long long)n * H * W;
-        int ylo, yhi, xlo, xhi;
-        dst_range<ALIGN>(i, sh, H, ylo, yhi);
-        dst_range<ALIGN>(j, sw, W, xlo, xhi);
-        float acc = 0.f;
-        for (int Y = ylo; Y <= yhi; ++Y) {
-            const Lerp Lh = lerp_of<ALIGN>(Y, sh, h);
-            const float wy = tap_weight(Lh, i);
-            if (wy == 0.f) continue;
-            const float* r0 = p + Lh.i0 * w;
-            const float* r1 = p + Lh.i1 * w;
-            float row = 0.f;
-            for (int X = xlo; X <= xhi; ++X) {
-                const Lerp Lw = lerp_of<ALIGN>(X, sw, w);
-                const float wx = tap_weight(Lw, j);
-                if (wx == 0.f) continue;
-                const long long q = (long long)Y * W + X;
-                const long long label = lab[q];
-                const float wgt = wp[q];
-                if (label == ignore_index || wgt == 0.f) continue;
-                const float z = Lh.l0 * (Lw.l0 * r0[Lw.i0] + Lw.l1 * r0[Lw.i1]) +
-                                Lh.l1 * (Lw.l0 * r1[Lw.i0] + Lw.l1 * r1[Lw.i1]);
-                row += wx * wgt * (expf(z - ls[q]) - (label == c ? 1.f : 0.f));
-            }
-            acc += wy * row;
-        }
-        dlogits[idx] = acc * gs[n];
-    }
-}
-
 template <bool ALIGN>
 __global__ void __launch_bounds__(kThreads)
 upsample_argmax_kernel(const float* __restrict__ logits, int N, int C, int h, int w, int H, int W,
@@ -783,20 +503,13 @@ upsample_argmax_kernel(const float* __restrict__ logits, int N, int C, int h, in
     const long long plane = (long long)h * w;
     for (long long pix = (long long)blockIdx.x * kThreads + threadIdx.x; pix < total;
          pix += (long long)gridDim.x * kThreads) {
-        const int X = (int)(pix % W);
-        const long long t = pix / W;
-        const int Y = (int)(t % H);
-        const int n = (int)(t / H);
-        const Lerp Lh = lerp_of<ALIGN>(Y, sh, h), Lw = lerp_of<ALIGN>(X, sw, w);
-        const int o00 = Lh.i0 * w + Lw.i0, o01 = Lh.i0 * w + Lw.i1;
-        const int o10 = Lh.i1 * w + Lw.i0, o11 = Lh.i1 * w + Lw.i1;
-        const float* base = logits + (long long)n * C * plane;
+        const Pix P = pix_of(pix, H, W);
+        const Tap t = tap_of(lerp_of<ALIGN>(P.Y, sh, h), lerp_of<ALIGN>(P.X, sw, w), w);
+        const float* base = logits + (long long)P.n * C * plane;
         float best = -INFINITY;
         int bi = 0;
         for (int c = 0; c < C; ++c) {
-            const float* p = base + c * plane;
-            const float z = Lh.l0 * (Lw.l0 * p[o00] + Lw.l1 * p[o01]) +
-                            Lh.l1 * (Lw.l0 * p[o10] + Lw.l1 * p[o11]);
+            const float z = logit_at(base + c * plane, t);
             if (z > best) { best = z; bi = c; }     // first maximum wins, like torch.argmax / np.argmax
         }
         pred[pix] = bi;
@@ -845,12 +558,10 @@ extern "C" int dcfp_upsample_bilinear_fwd_f32(const float* x, float* y, int N, i
     if (!x || !y || N <= 0 || C <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return DCFP_E_BADDESC;
     const long long total = (long long)N * C * H * W;
     const float sh = host_scale(h, H, align_corners), sw = host_scale(w, W, align_corners);
-    if (align_corners)
-        hipLaunchKernelGGL(upsample_fwd_kernel<true>, dim3(stream_grid(total)), dim3(kThreads), 0,
+    with_align(align_corners, [&](auto A) {
+        hipLaunchKernelGGL(upsample_fwd_kernel<A.value>, dim3(stream_grid(total)), dim3(kThreads), 0,
                            dcfp_s(stream), x, y, total, h, w, H, W, sh, sw);
-    else
-        hipLaunchKernelGGL(upsample_fwd_kernel<false>, dim3(stream_grid(total)), dim3(kThreads), 0,
-                           dcfp_s(stream), x, y, total, h, w, H, W, sh, sw);
+    });
     DCFP_RETURN_LAUNCH();
 }
 
@@ -860,12 +571,10 @@ extern "C" int dcfp_upsample_bilinear_bwd_f32(const float* dy, float* dx, int N,
     if (!dy || !dx || N <= 0 || C <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return DCFP_E_BADDESC;
     const long long total = (long long)N * C * h * w;
     const float sh = host_scale(h, H, align_corners), sw = host_scale(w, W, align_corners);
-    if (align_corners)
-        hipLaunchKernelGGL(upsample_bwd_kernel<true>, dim3(stream_grid(total)), dim3(kThreads), 0,
+    with_align(align_corners, [&](auto A) {
+        hipLaunchKernelGGL(upsample_bwd_kernel<A.value>, dim3(stream_grid(total)), dim3(kThreads), 0,
                            dcfp_s(stream), dy, dx, total, h, w, H, W, sh, sw);
-    else
-        hipLaunchKernelGGL(upsample_bwd_kernel<false>, dim3(stream_grid(total)), dim3(kThreads), 0,
-                           dcfp_s(stream), dy, dx, total, h, w, H, W, sh, sw);
+    });
     DCFP_RETURN_LAUNCH();
 }
 
@@ -889,63 +598,28 @@ extern "C" int dcfp_upsample_ce_fwd_f32(const float* logits, const int64_t* labe
     float* part = static_cast<float*>(workspace);
     const float sh = host_scale(h, H, align_corners), sw = host_scale(w, W, align_corners);
     const long long* lab = reinterpret_cast<const long long*>(labels);
-    if (align_corners)
-        hipLaunchKernelGGL(upsample_ce_fwd_kernel<true>, dim3((unsigned)blocks), dim3(kThreads), 0,
+    with_align(align_corners, [&](auto A) {
+        hipLaunchKernelGGL(upsample_ce_fwd_kernel<A.value>, dim3((unsigned)blocks), dim3(kThreads), 0,
                            dcfp_s(stream), logits, lab, pixel_keep, ignore_index, N, C, h, w, H, W,
                            sh, sw, lse, gt_prob, part);
-    else
-        hipLaunchKernelGGL(upsample_ce_fwd_kernel<false>, dim3((unsigned)blocks), dim3(kThreads), 0,
-                           dcfp_s(stream), logits, lab, pixel_keep, ignore_index, N, C, h, w, H, W,
-                           sh, sw, lse, gt_prob, part);
+    });
     hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, dcfp_s(stream), part, (int)blocks,
                        out2);
     DCFP_RETURN_LAUNCH();
 }
 
-// 19-class backward: the cell-organised kernel (DCFP_CE_BWD_CELLS=0: the per-output kernel, for A/B)
-template <bool ALIGN>
-static void launch_ce_bwd_19(const float* logits, const long long* lab, const uint8_t* keep, int ignore_index, int N,
-                             int h, int w, int H, int W, float sh, float sw, const float* lse, const float* gscale,
-                             float* dlogits, const float* pix_weight, int per_image, hipStream_t st) {
-    static const bool cells = [] { const char* e = getenv("DCFP_CE_BWD_CELLS"); return !e || atoi(e) != 0; }();
-    if (cells) {
-        const int tiles_w = (w + kCellTW - 1) / kCellTW, tiles_h = (h + kCellTH - 1) / kCellTH;
-        hipLaunchKernelGGL((upsample_ce_bwd_cells_kernel<ALIGN, 19>), dim3((unsigned)(N * tiles_h * tiles_w)),
-                           dim3(kCellThreads), 0, st, logits, lab, keep, ignore_index, N, h, w, H, W, sh, sw, lse,
-                           gscale, dlogits, pix_weight, per_image, tiles_w, tiles_h);
-        return;
-    }
-    const long long tot2 = (long long)N * h * w * 4;   // 4 lanes per low-resolution pixel
-    const unsigned b2 = (unsigned)((tot2 + kThreads - 1) / kThreads);
-    hipLaunchKernelGGL((upsample_ce_bwd_classes_kernel<ALIGN, 19>), dim3(b2), dim3(kThreads), 0, st, logits, lab,
-                       keep, ignore_index, N, h, w, H, W, sh, sw, lse, gscale, dlogits, pix_weight, per_image);
-}
-
-// Which backward kernel a shape gets: the one decision both launchers and dcfp_upsample_ce_bwd_plan make.
+// Which backward kernel a shape gets: the one decision launch_ce_bwd and dcfp_upsample_ce_bwd_plan make.
 enum { kCePlanCells19 = 0, kCePlanCellsChunked = 1, kCePlanPerOutput = 2 };
 struct CeBwdPlan { int variant, chunk_width, chunks; };
 
 static CeBwdPlan ce_bwd_plan(int N, int C, int h, int w) {
     static const bool cells = [] { const char* e = getenv("DCFP_CE_BWD_CELLS"); return !e || atoi(e) != 0; }();
-    const long long tiles = (long long)N * ((h + kCellTH - 1) / kCellTH) * ((w + kCellTW - 1) / kCellTW);
-    if (C == 19)   // launch_ce_bwd_19 (the 32-bit block count holds whenever the entry points' own check does)
-        return cells ? CeBwdPlan{kCePlanCells19, 19, 1} : CeBwdPlan{kCePlanPerOutput, 0, 0};
-    const int chunks = (C + kCeChunk - 1) / kCeChunk;
-    if (cells && C >= kCeChunkMinC && tiles * chunks <= 0x7fffffffLL)
-        return CeBwdPlan{kCePlanCellsChunked, kCeChunk, chunks};
+    const int CT = C == 19 ? 19 : kCeChunk;   // Cityscapes (datasets/CSdatasets.py:13): all classes in one window
+    const int chunks = (C + CT - 1) / CT;
+    const long long tiles = (long long)N * cell_tiles_h(h) * cell_tiles_w(w);
+    if (cells && C >= kCeChunkMinC && tiles * chunks <= 0x7fffffffLL)     // the cell kernels' 32-bit block count
+        return CeBwdPlan{C == 19 ? kCePlanCells19 : kCePlanCellsChunked, CT, chunks};
     return CeBwdPlan{kCePlanPerOutput, 0, 0};
-}
-
-template <bool ALIGN>
-static void launch_ce_bwd_chunked(const CeBwdPlan& plan, const float* logits, const long long* lab,
-                                  const uint8_t* keep, int ignore_index, int N, int C, int h, int w, int H, int W,
-                                  float sh, float sw, const float* lse, const float* gscale, float* dlogits,
-                                  const float* pix_weight, int per_image, hipStream_t st) {
-    const int tiles_w = (w + kCellTW - 1) / kCellTW, tiles_h = (h + kCellTH - 1) / kCellTH;
-    hipLaunchKernelGGL((upsample_ce_bwd_cells_chunk_kernel<ALIGN, kCeChunk>),
-                       dim3((unsigned)((long long)N * tiles_h * tiles_w * plan.chunks)), dim3(kCellThreads), 0, st,
-                       logits, lab, keep, ignore_index, N, C, h, w, H, W, sh, sw, lse, gscale, dlogits, pix_weight,
-                       per_image, tiles_w, tiles_h, plan.chunks);
 }
 
 extern "C" int dcfp_upsample_ce_bwd_plan(int N, int C, int h, int w, int H, int W, int* variant, int* chunk_width,
@@ -960,6 +634,40 @@ extern "C" int dcfp_upsample_ce_bwd_plan(int N, int C, int h, int w, int H, int 
     return DCFP_OK;
 }
 
+// The backward of plain CE (nullable keep mask, grad_scale[0]) and of weighted CE (weight map, grad_scale[n]), on the
+// route ce_bwd_plan names.  The per-output route at 19 classes is upsample_ce_bwd_classes_kernel, the A/B partner of
+// the cell kernel under DCFP_CE_BWD_CELLS=0.
+static int launch_ce_bwd(const float* logits, const int64_t* labels, const uint8_t* keep, const float* pix_weight,
+                         int per_image, int ignore_index, int N, int C, int h, int w, int H, int W, int align_corners,
+                         const float* lse, const float* gscale, float* dlogits, hipStream_t st) {
+    const long long blocks = ((long long)N * C * h * w + kThreads - 1) / kThreads;
+    if (blocks > 0x7fffffffLL) return DCFP_E_UNSUPPORTED;
+    const float sh = host_scale(h, H, align_corners), sw = host_scale(w, W, align_corners);
+    const long long* lab = reinterpret_cast<const long long*>(labels);
+    const CeBwdPlan plan = ce_bwd_plan(N, C, h, w);
+    const int tiles_w = cell_tiles_w(w), tiles_h = cell_tiles_h(h);
+    const dim3 cell_grid((unsigned)((long long)N * tiles_h * tiles_w * plan.chunks));
+    with_align(align_corners, [&](auto A) {
+        if (plan.variant == kCePlanCells19)
+            hipLaunchKernelGGL((ce_bwd_cells_kernel<A.value, 19, true>), cell_grid, dim3(kCellThreads), 0, st, logits, lab, keep,
+                               ignore_index, C, h, w, H, W, sh, sw, lse, gscale, dlogits, pix_weight, per_image, tiles_w,
+                               tiles_h, plan.chunks);
+        else if (plan.variant == kCePlanCellsChunked)
+            hipLaunchKernelGGL((ce_bwd_cells_kernel<A.value, kCeChunk, false>), cell_grid, dim3(kCellThreads), 0, st, logits, lab,
+                               keep, ignore_index, C, h, w, H, W, sh, sw, lse, gscale, dlogits, pix_weight, per_image,
+                               tiles_w, tiles_h, plan.chunks);
+        else if (C == 19)   // 4 lanes per low-resolution pixel
+            hipLaunchKernelGGL((upsample_ce_bwd_classes_kernel<A.value, 19>),
+                               dim3((unsigned)(((long long)N * h * w * 4 + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+                               st, logits, lab, keep, ignore_index, N, h, w, H, W, sh, sw, lse, gscale, dlogits,
+                               pix_weight, per_image);
+        else
+            hipLaunchKernelGGL(upsample_ce_bwd_kernel<A.value>, dim3((unsigned)blocks), dim3(kThreads), 0, st, logits, lab,
+                               keep, pix_weight, ignore_index, N, C, h, w, H, W, sh, sw, lse, gscale, per_image, dlogits);
+    });
+    DCFP_RETURN_LAUNCH();
+}
+
 extern "C" int dcfp_upsample_ce_bwd_f32(const float* logits, const int64_t* labels,
                                         const uint8_t* pixel_keep, int ignore_index, int N, int C,
                                         int h, int w, int H, int W, int align_corners,
@@ -968,40 +676,8 @@ extern "C" int dcfp_upsample_ce_bwd_f32(const float* logits, const int64_t* labe
     if (!logits || !labels || !lse || !grad_scale || !dlogits || N <= 0 || C <= 0 || h <= 0 ||
         w <= 0 || H <= 0 || W <= 0)
         return DCFP_E_BADDESC;
-    const long long total = (long long)N * C * h * w;
-    const float sh = host_scale(h, H, align_corners), sw = host_scale(w, W, align_corners);
-    const long long* lab = reinterpret_cast<const long long*>(labels);
-    long long blocks = (total + kThreads - 1) / kThreads;
-    if (blocks > 0x7fffffffLL) return DCFP_E_UNSUPPORTED;
-    if (C == 19 && (long long)N * ((h + kCellTH - 1) / kCellTH) * ((w + kCellTW - 1) / kCellTW) <= 0x7fffffffLL) {
-        // Cityscapes (datasets/CSdatasets.py:13): all classes in registers
-        if (align_corners)
-            launch_ce_bwd_19<true>(logits, lab, pixel_keep, ignore_index, N, h, w, H, W, sh, sw, lse, grad_scale,
-                                   dlogits, nullptr, 0, dcfp_s(stream));
-        else
-            launch_ce_bwd_19<false>(logits, lab, pixel_keep, ignore_index, N, h, w, H, W, sh, sw, lse, grad_scale,
-                                    dlogits, nullptr, 0, dcfp_s(stream));
-        DCFP_RETURN_LAUNCH();
-    }
-    const CeBwdPlan plan = ce_bwd_plan(N, C, h, w);
-    if (plan.variant == kCePlanCellsChunked) {   // every other class count: the cell kernel per class chunk
-        if (align_corners)
-            launch_ce_bwd_chunked<true>(plan, logits, lab, pixel_keep, ignore_index, N, C, h, w, H, W, sh, sw, lse,
-                                        grad_scale, dlogits, nullptr, 0, dcfp_s(stream));
-        else
-            launch_ce_bwd_chunked<false>(plan, logits, lab, pixel_keep, ignore_index, N, C, h, w, H, W, sh, sw, lse,
-                                         grad_scale, dlogits, nullptr, 0, dcfp_s(stream));
-        DCFP_RETURN_LAUNCH();
-    }
-    if (align_corners)
-        hipLaunchKernelGGL(upsample_ce_bwd_kernel<true>, dim3((unsigned)blocks), dim3(kThreads), 0,
-                           dcfp_s(stream), logits, lab, pixel_keep, ignore_index, N, C, h, w, H, W,
-                           sh, sw, lse, grad_scale, dlogits);
-    else
-        hipLaunchKernelGGL(upsample_ce_bwd_kernel<false>, dim3((unsigned)blocks), dim3(kThreads), 0,
-                           dcfp_s(stream), logits, lab, pixel_keep, ignore_index, N, C, h, w, H, W,
-                           sh, sw, lse, grad_scale, dlogits);
-    DCFP_RETURN_LAUNCH();
+    return launch_ce_bwd(logits, labels, pixel_keep, nullptr, 0, ignore_index, N, C, h, w, H, W, align_corners, lse,
+                         grad_scale, dlogits, dcfp_s(stream));
 }
 
 extern "C" int dcfp_ohem_zoom_gt_prob_f32(const float* logits, const int64_t* labels, const float* lse,
@@ -1014,12 +690,10 @@ extern "C" int dcfp_ohem_zoom_gt_prob_f32(const float* logits, const int64_t* la
     const long long total = (long long)N * H8 * W8;
     const float sh = host_scale(h, H, align_corners), sw = host_scale(w, W, align_corners);
     const long long* lab = reinterpret_cast<const long long*>(labels);
-    if (align_corners)
-        hipLaunchKernelGGL(ohem_zoom_kernel<true>, dim3(stream_grid(total)), dim3(kThreads), 0,
+    with_align(align_corners, [&](auto A) {
+        hipLaunchKernelGGL(ohem_zoom_kernel<A.value>, dim3(stream_grid(total)), dim3(kThreads), 0,
                            dcfp_s(stream), logits, lab, lse, N, C, h, w, H, W, sh, sw, H8, W8, pred8, lab8);
-    else
-        hipLaunchKernelGGL(ohem_zoom_kernel<false>, dim3(stream_grid(total)), dim3(kThreads), 0,
-                           dcfp_s(stream), logits, lab, lse, N, C, h, w, H, W, sh, sw, H8, W8, pred8, lab8);
+    });
     DCFP_RETURN_LAUNCH();
 }
 
@@ -1028,12 +702,10 @@ extern "C" int dcfp_upsample_margin_f32(const float* logits, int N, int C, int h
     if (!logits || !margin || N <= 0 || C <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return DCFP_E_BADDESC;
     const long long total = (long long)N * H * W;
     const float sh = host_scale(h, H, align_corners), sw = host_scale(w, W, align_corners);
-    if (align_corners)
-        hipLaunchKernelGGL(upsample_margin_kernel<true>, dim3(stream_grid(total)), dim3(kThreads), 0,
+    with_align(align_corners, [&](auto A) {
+        hipLaunchKernelGGL(upsample_margin_kernel<A.value>, dim3(stream_grid(total)), dim3(kThreads), 0,
                            dcfp_s(stream), logits, N, C, h, w, H, W, sh, sw, margin);
-    else
-        hipLaunchKernelGGL(upsample_margin_kernel<false>, dim3(stream_grid(total)), dim3(kThreads), 0,
-                           dcfp_s(stream), logits, N, C, h, w, H, W, sh, sw, margin);
+    });
     DCFP_RETURN_LAUNCH();
 }
 
@@ -1068,12 +740,10 @@ extern "C" int dcfp_upsample_wce_fwd_f32(const float* logits, const int64_t* lab
     const float sh = host_scale(h, H, align_corners), sw = host_scale(w, W, align_corners);
     const long long* lab = reinterpret_cast<const long long*>(labels);
     dim3 grid((unsigned)blocks, (unsigned)N);
-    if (align_corners)
-        hipLaunchKernelGGL(upsample_wce_fwd_kernel<true>, grid, dim3(kThreads), 0, dcfp_s(stream), logits, lab,
+    with_align(align_corners, [&](auto A) {
+        hipLaunchKernelGGL(upsample_wce_fwd_kernel<A.value>, grid, dim3(kThreads), 0, dcfp_s(stream), logits, lab,
                            pix_weight, ignore_index, C, h, w, H, W, sh, sw, lse, part);
-    else
-        hipLaunchKernelGGL(upsample_wce_fwd_kernel<false>, grid, dim3(kThreads), 0, dcfp_s(stream), logits, lab,
-                           pix_weight, ignore_index, C, h, w, H, W, sh, sw, lse, part);
+    });
     hipLaunchKernelGGL(wce_final_kernel, dim3((unsigned)N), dim3(64), 0, dcfp_s(stream), part, (int)blocks,
                        out_per_image);
     DCFP_RETURN_LAUNCH();
@@ -1087,39 +757,8 @@ extern "C" int dcfp_upsample_wce_bwd_f32(const float* logits, const int64_t* lab
     if (!logits || !labels || !pix_weight || !lse || !grad_scale_per_image || !dlogits || N <= 0 ||
         C <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0)
         return DCFP_E_BADDESC;
-    const long long total = (long long)N * C * h * w;
-    const float sh = host_scale(h, H, align_corners), sw = host_scale(w, W, align_corners);
-    const long long* lab = reinterpret_cast<const long long*>(labels);
-    long long blocks = (total + kThreads - 1) / kThreads;
-    if (blocks > 0x7fffffffLL) return DCFP_E_UNSUPPORTED;
-    if (C == 19) {   // all classes in registers (see upsample_ce_bwd_cells_kernel)
-        if (align_corners)
-            launch_ce_bwd_19<true>(logits, lab, nullptr, ignore_index, N, h, w, H, W, sh, sw, lse,
-                                   grad_scale_per_image, dlogits, pix_weight, 1, dcfp_s(stream));
-        else
-            launch_ce_bwd_19<false>(logits, lab, nullptr, ignore_index, N, h, w, H, W, sh, sw, lse,
-                                    grad_scale_per_image, dlogits, pix_weight, 1, dcfp_s(stream));
-        DCFP_RETURN_LAUNCH();
-    }
-    const CeBwdPlan plan = ce_bwd_plan(N, C, h, w);
-    if (plan.variant == kCePlanCellsChunked) {
-        if (align_corners)
-            launch_ce_bwd_chunked<true>(plan, logits, lab, nullptr, ignore_index, N, C, h, w, H, W, sh, sw, lse,
-                                        grad_scale_per_image, dlogits, pix_weight, 1, dcfp_s(stream));
-        else
-            launch_ce_bwd_chunked<false>(plan, logits, lab, nullptr, ignore_index, N, C, h, w, H, W, sh, sw, lse,
-                                         grad_scale_per_image, dlogits, pix_weight, 1, dcfp_s(stream));
-        DCFP_RETURN_LAUNCH();
-    }
-    if (align_corners)
-        hipLaunchKernelGGL(upsample_wce_bwd_kernel<true>, dim3((unsigned)blocks), dim3(kThreads), 0,
-                           dcfp_s(stream), logits, lab, pix_weight, ignore_index, N, C, h, w, H, W, sh, sw,
-                           lse, grad_scale_per_image, dlogits);
-    else
-        hipLaunchKernelGGL(upsample_wce_bwd_kernel<false>, dim3((unsigned)blocks), dim3(kThreads), 0,
-                           dcfp_s(stream), logits, lab, pix_weight, ignore_index, N, C, h, w, H, W, sh, sw,
-                           lse, grad_scale_per_image, dlogits);
-    DCFP_RETURN_LAUNCH();
+    return launch_ce_bwd(logits, labels, nullptr, pix_weight, 1, ignore_index, N, C, h, w, H, W, align_corners, lse,
+                         grad_scale_per_image, dlogits, dcfp_s(stream));
 }
 
 extern "C" int dcfp_upsample_argmax_f32(const float* logits, int N, int C, int h, int w, int H, int W,
@@ -1127,12 +766,10 @@ extern "C" int dcfp_upsample_argmax_f32(const float* logits, int N, int C, int h
     if (!logits || !pred || N <= 0 || C <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return DCFP_E_BADDESC;
     const long long total = (long long)N * H * W;
     const float sh = host_scale(h, H, align_corners), sw = host_scale(w, W, align_corners);
-    if (align_corners)
-        hipLaunchKernelGGL(upsample_argmax_kernel<true>, dim3(stream_grid(total)), dim3(kThreads), 0,
+    with_align(align_corners, [&](auto A) {
+        hipLaunchKernelGGL(upsample_argmax_kernel<A.value>, dim3(stream_grid(total)), dim3(kThreads), 0,
                            dcfp_s(stream), logits, N, C, h, w, H, W, sh, sw, pred);
-    else
-        hipLaunchKernelGGL(upsample_argmax_kernel<false>, dim3(stream_grid(total)), dim3(kThreads), 0,
-                           dcfp_s(stream), logits, N, C, h, w, H, W, sh, sw, pred);
+    });
     DCFP_RETURN_LAUNCH();
 }
 

@@ -1,6 +1,6 @@
-"""The class-chunked cell kernel of the fused upsample + CE backward (`upsample_ce_bwd_cells_chunk_kernel`, every class
-count but 19): fp64 parity, exact independence of the class chunks, determinism, the plan query and the
-`DCFP_CE_BWD_CELLS=0` route.
+"""The cell kernel of the fused upsample + CE backward in class chunks (`ce_bwd_cells_kernel<ALIGN, kCeChunk>`, every
+class count but 19; 19 is the same kernel with one chunk of 19): fp64 parity, exact independence of the class chunks,
+determinism, equal bits of the plain and the weighted route, the plan query and the `DCFP_CE_BWD_CELLS=0` route.
 
 Class counts are placed around the chunk width CT, read from `ops.ce_backward_plan`: CT+1 (a tail chunk of one class),
 2CT-1 (a tail chunk one short), 2CT (no tail), 2CT+1, and the datasets' 59 / 150 / 171.  Geometries stress the 7 x 15
@@ -263,6 +263,23 @@ def test_deterministic_and_fully_written(cuda, count, kind):
     assert torch.equal(a, b)
 
 
+@pytest.mark.parametrize("count", ["19", "CT+1", "59"])
+@pytest.mark.parametrize("geom", [GEOMS[2], GEOMS[3]], ids=_gid)
+def test_keep_and_weighted_routes_equal_bits(cuda, geom, count):
+    """Plain CE without a keep mask and weighted CE under an all-ones weight map and one scale for every image are the
+    same function; both entry points go through one launcher and one kernel, where the weight multiplies by exactly 1:
+    their dlogits are the same bits."""
+    Cc = _count(count, _ct())
+    N, h, w, H, W, align, _ = geom
+    z, lab, lse, _, _ = _direct_inputs(cuda, "keep", geom, Cc, _seed("routes", _gid(geom), count))
+    ones = torch.ones((N, H, W), dtype=torch.float32, device=cuda)
+    scale = torch.full((N,), 1.0 / (N * H * W), dtype=torch.float32, device=cuda)
+    plain = _direct(cuda, "keep", z, lab, lse, None, scale[:1], (H, W), align)
+    weighted = _direct(cuda, "wce", z, lab, lse, ones, scale, (H, W), align)
+    assert torch.isfinite(plain).all() and bool((plain != 0).any())
+    assert torch.equal(plain, weighted)
+
+
 # ------------------------------------------------------------------------------------------------------ the plan
 def test_plan(cuda):
     from dcfp_amd import ops
@@ -276,7 +293,7 @@ def test_plan(cuda):
 
 
 def test_c19_control(cuda):
-    """C == 19 keeps its own instantiation (`cells19`), held to fp64 as before"""
+    """C == 19 keeps its own instantiation (`cells19`: one chunk of 19 classes, no tail), held to fp64 as before"""
     from dcfp_amd import ops
     geom = GEOMS[2]
     N, h, w, H, W, _, _ = geom

@@ -202,11 +202,11 @@ def test_maxfilter_grid_stride_and_even_k(cuda):
 
 
 # ------------------------------------------------------------------------------------------------ 3. weighted CE
-# Routing (not observable from Python: these entry points have no kernel-name query), by function name in
-# upsample_ce.hip.  dcfp_upsample_wce_bwd_f32: C == 19 -> launch_ce_bwd_19 with pix_weight and scale_per_image = 1, i.e.
-# upsample_ce_bwd_cells_kernel<*,19>, or upsample_ce_bwd_classes_kernel<*,19> when the process started with
-# DCFP_CE_BWD_CELLS=0; any other C -> upsample_wce_bwd_kernel.  dcfp_upsample_ce_bwd_f32: C == 19 -> the same pair with
-# pixel_keep and scale_per_image = 0, any other C -> upsample_ce_bwd_kernel.
+# Routing, by function name in upsample_ce.hip (ops.ce_backward_plan reports it).  dcfp_upsample_wce_bwd_f32 and
+# dcfp_upsample_ce_bwd_f32 both go through launch_ce_bwd, the first with pix_weight and scale_per_image = 1, the second
+# with pixel_keep and scale_per_image = 0: C == 19 -> ce_bwd_cells_kernel<*,19>, or upsample_ce_bwd_classes_kernel<*,19>
+# when the process started with DCFP_CE_BWD_CELLS=0; any other C > 1 -> ce_bwd_cells_kernel<*,kCeChunk>, or
+# upsample_ce_bwd_kernel under DCFP_CE_BWD_CELLS=0; C == 1 -> upsample_ce_bwd_kernel.
 def _wce_weights(g, lab):
     """non-negative weights, zero on a random 30 % of the pixels, independent of the labels: non-zero on ignored ones"""
     wgt = torch.rand(lab.shape, generator=g) * 2.0 + 0.05
