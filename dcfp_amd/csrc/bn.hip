@@ -133,6 +133,10 @@ __device__ __forceinline__ bool mask_bit(const unsigned long long* __restrict__ 
     const unsigned long long wv = row_words[(i_wave >> 8) * 4 + k];
     return (wv >> (threadIdx.x & 63)) & 1ull;
 }
+// ... and the same bit by pixel index i of the row (the 4-byte kernels, which walk a row one pixel per thread)
+__device__ __forceinline__ bool mask_bit_at(const unsigned long long* __restrict__ row_words, int i) {
+    return (row_words[(i >> 8) * 4 + (i & 3)] >> ((i & 255) >> 2)) & 1ull;
+}
 
 // ---- apply: one (n,c) row segment per block
 template <bool VEC, bool MASK = false>
@@ -248,6 +252,8 @@ bn_bwd_reduce_partial_kernel(const float* __restrict__ dy, long long dy_nstride,
             const float xv = x[n * x_nstride + coff + i];
             if (RELU == 1) g = y[n * y_nstride + coff + i] > 0.f ? g : 0.f;
             else if (RELU == 2) g = bn_val(xv, mu, istd, gm, bt) > 0.f ? g : 0.f;
+            else if (RELU == 3)
+                g = mask_bit_at(reinterpret_cast<const unsigned long long*>(y) + (n * C + c) * (long long)(HW >> 6), i) ? g : 0.f;
             s1 += g;
             s2 += g * (xv - mu);
         }
@@ -514,6 +520,7 @@ bn_bwd_apply_kernel(const float* __restrict__ dy, long long dy_nstride,
             float g = dyr[i];
             if (RELU == 1) g = yr[i] > 0.f ? g : 0.f;
             else if (RELU == 2) g = bn_val(xr[i], mu, istd, gm, bt) > 0.f ? g : 0.f;
+            else if (RELU == 3) g = mask_bit_at(reinterpret_cast<const unsigned long long*>(y) + row * (HW >> 6), i) ? g : 0.f;
             const float o = (g - mean_dy - (xr[i] - mu) * k) * gi;
             if (dx_pitch) { const int h = i / W; dxr[h * dx_pitch + (i - h * W)] = o; }
             else dxr[i] = o;
@@ -908,8 +915,10 @@ extern "C" int dcfp_bn_bwd_reduce_f32(const float* dy, int64_t dy_nstride, const
     hipLaunchKernelGGL((bn_bwd_reduce_partial_kernel<V, R>), grid, dim3(kThreads), 0,             \
                        dcfp_s(stream), dy, (long long)dy_nstride, x, y, (long long)y_nstride,     \
                        mean, var, gamma, beta, eps, C, HW, E, p.chunk_elems, p.chunks, part)
-    if (relu == 3 && !(vec && HW % 256 == 0 && dy_nstride == (int64_t)C * HW)) return DCFP_E_UNSUPPORTED;
-    if (vec) { if (relu == 3) LAUNCH_RED(true, 3); else if (relu == 2) LAUNCH_RED(true, 2); else if (relu == 1) LAUNCH_RED(true, 1); else LAUNCH_RED(true, 0); }
+    if (relu == 3 && HW % 256 != 0) return DCFP_E_UNSUPPORTED;      // (the mask's layout)
+    // (the mask mode's 16-byte kernel walks dense images; a batch-strided or 4-byte aligned dy / x reads the mask by pixel)
+    if (relu == 3 && !(vec && dy_nstride == (int64_t)C * HW)) LAUNCH_RED(false, 3);
+    else if (vec) { if (relu == 3) LAUNCH_RED(true, 3); else if (relu == 2) LAUNCH_RED(true, 2); else if (relu == 1) LAUNCH_RED(true, 1); else LAUNCH_RED(true, 0); }
     else     { if (relu == 2) LAUNCH_RED(false, 2); else if (relu == 1) LAUNCH_RED(false, 1); else LAUNCH_RED(false, 0); }
 #undef LAUNCH_RED
     hipLaunchKernelGGL(bn_pair_final_kernel, dim3((unsigned)C), dim3(64), 0, dcfp_s(stream), C,
@@ -956,8 +965,9 @@ extern "C" int dcfp_bn_bwd_apply_f32(const float* dy, int64_t dy_nstride, const 
                        mean, var, gamma, beta, eps, sum_dy, sum_dy_xmu, inv_count, count_dev, dx, \
                        d_residual, C,                                                             \
                        HW, colchunks, kColsPerBlock, W, dx_pitch)
-    if (relu == 3 && !(vec && HW % 256 == 0)) return DCFP_E_UNSUPPORTED;
-    if (vec) { if (relu == 3) LAUNCH_APP(true, 3); else if (relu == 2) LAUNCH_APP(true, 2); else if (relu == 1) LAUNCH_APP(true, 1); else LAUNCH_APP(true, 0); }
+    if (relu == 3 && HW % 256 != 0) return DCFP_E_UNSUPPORTED;      // (the mask's layout)
+    if (relu == 3 && !vec) LAUNCH_APP(false, 3);
+    else if (vec) { if (relu == 3) LAUNCH_APP(true, 3); else if (relu == 2) LAUNCH_APP(true, 2); else if (relu == 1) LAUNCH_APP(true, 1); else LAUNCH_APP(true, 0); }
     else     { if (relu == 2) LAUNCH_APP(false, 2); else if (relu == 1) LAUNCH_APP(false, 1); else LAUNCH_APP(false, 0); }
 #undef LAUNCH_APP
     DCFP_RETURN_LAUNCH();

@@ -75,6 +75,9 @@ inline bool wgrad_dma_on() {
     return v;
 }
 
+// An operand the 16-byte paths may read or write: on the 16-byte grid, images a whole number of quads apart
+inline bool dcfp_quad_operand(const void* p, long long nstride) { return dcfp_aligned16(p) && nstride % 4 == 0; }
+
 // ---------------------------------------------------------------- the problem view
 // A forward or data-gradient pass as the implicit GEMM the kernels run (the table at the top of conv_igemm.hip):
 //   Out[m][p] = sum over (tap, c) of A[m][tap, c] * B[c][pixel p shifted by the tap]
@@ -141,7 +144,9 @@ struct GemmExtras {
 
 // ---------------------------------------------------------------- conv_igemm2.hip
 enum Igemm2Family { IGEMM2_TILE, IGEMM2_DMA, IGEMM2_DMA1P, IGEMM2_DMA8 };
-// The kernel dcfp_igemm2_run launches for (problem, options, output alignment), and its tiling
+// The kernel dcfp_igemm2_run launches for (problem, options, operand alignment), and its tiling.  vec_store: the output
+// takes 16-byte stores; vec_load: the B source is 16-byte aligned with an image stride of whole quads - what every LDS-DMA
+// family needs of the address it copies from (the register-staged tile family takes any 4-byte aligned address)
 struct Igemm2Route {
     int family;             // Igemm2Family
     int cfg, bm, bn;        // tile configuration (0: 32x512  1: 64x512  2: 128x256  3: 128x128  4: 256x256  5: 128x256
@@ -152,7 +157,7 @@ struct Igemm2Route {
     int tiles_per_img, tiles_n_total, tiles_m;
     int Hc, Wc, tiles_per_phase, zfold;     // strided dgrad (Igemm2Params)
 };
-Igemm2Route igemm2_route(const GemmProblem& g, const GemmExtras& x, bool vec_store);
+Igemm2Route igemm2_route(const GemmProblem& g, const GemmExtras& x, bool vec_store, bool vec_load = true);
 int dcfp_igemm2_run(const GemmProblem& g, const float* in, const float* w, float* out, void* workspace, size_t workspace_bytes,
                     const GemmExtras& x, hipStream_t stream);
 size_t dcfp_igemm2_workspace_bytes(const GemmProblem& g);

@@ -105,7 +105,10 @@ size_t dcfp_conv2d_fwd_dgrad_workspace_bytes_(const DcfpConvDesc* d, int pass) {
             const size_t u = dcfp_wino_fused_workspace_bytes(q), direct = dcfp_igemm2_workspace_bytes(g);
             return u > direct ? u : direct;
         }
-        return wk == 1 ? dcfp_wino_workspace_bytes(q) : dcfp_wino_fused_workspace_bytes(q);
+        if (wk == 1) return dcfp_wino_workspace_bytes(q);
+        // (the fused kernel only: a source off the 16-byte grid runs the direct kernel in the same workspace)
+        const size_t u = dcfp_wino_fused_workspace_bytes(q), direct = dcfp_igemm2_workspace_bytes(g);
+        return u > direct ? u : direct;
     }
     const size_t b2 = dcfp_igemm2_workspace_bytes(g);
     const size_t b3 = igemm3_ok(g) ? dcfp_igemm3_workspace_bytes(g.T, g.M, g.Ck) : 0;
@@ -203,7 +206,8 @@ extern "C" int dcfp_conv2d_fwd_f32_nchw(const DcfpConvDesc* d, const float* x, c
     GemmExtras ex;
     ex.bias = bias; ex.wp_valid = wp_valid;
     if (dcfp_gemv_shape(d)) return dcfp_gemv_fwd(d, x, w, bias, y, y_nstride, dcfp_s(stream));
-    if (dcfp_stem_shape(d)) return dcfp_stem_fwd(d, x, w, y, y_nstride, ex, dcfp_s(stream));     // Cin = 3, stride 2: conv_stem.hip
+    // Cin = 3, stride 2: conv_stem.hip (16-byte stores only: an output off that grid takes the strided tile kernel below)
+    if (dcfp_stem_shape(d) && dcfp_quad_operand(y, g.out_nstride)) return dcfp_stem_fwd(d, x, w, y, y_nstride, ex, dcfp_s(stream));
     if (!bias && wino_pass(d, DCFP_CONV_FWD)) {
         ex.wp_valid = wino_wp_valid(d, DCFP_CONV_FWD, wp_valid);
         return dcfp_wino_run(g, x, w, y, workspace, workspace_bytes, ex, dcfp_s(stream));

@@ -1028,10 +1028,12 @@ bool dcfp_igemm2_dma_shape(const GemmProblem& g) {
 
 // THE route: which kernel dcfp_igemm2_run launches and how it tiles the problem.  Every query below reads it (with no
 // options and vec_store = true: the plain call with dense, 16-byte-aligned outputs); nothing else repeats its conditions.
-Igemm2Route igemm2_route(const GemmProblem& g, const GemmExtras& x, bool vec_store) {
+Igemm2Route igemm2_route(const GemmProblem& g, const GemmExtras& x, bool vec_store, bool vec_load) {
     const TileCfg c = pick_cfg(g.M, g.px(), g.sd);
     const bool plain = !x.scale && !x.relu && !x.stat_part;     // (bias is handled by the ragged-M kernel's epilogue)
-    const bool d8 = plain && !x.wp_nstride && !x.fan_src && dcfp_igemm2_use_dma8(g);
+    // (the ragged-M kernel has 8-byte stores on whole quads of pixels only, and like every LDS-DMA family it copies 16 bytes
+    //  at a time from the source: an output or a source off the 16-byte grid takes the tile family)
+    const bool d8 = plain && !x.wp_nstride && !x.fan_src && vec_store && vec_load && dcfp_igemm2_use_dma8(g);
     const bool off_grid = ((g.off0 | g.offstep) & 3) != 0;      // tap shifts that are no multiples of 4 columns
     Igemm2Route r = {};
     r.cfg = c.id; r.bm = d8 ? 256 : c.bm; r.bn = d8 ? 256 : c.bn;
@@ -1057,7 +1059,7 @@ Igemm2Route igemm2_route(const GemmProblem& g, const GemmExtras& x, bool vec_sto
     r.tiles_m = r.Mpad / r.bm;
     if (d8)
         r.family = IGEMM2_DMA8;
-    else if (r.dma_shape && vec_store && !x.bias && !x.scale && !x.relu && !(x.stat_part && x.accumulate)) {
+    else if (r.dma_shape && vec_store && vec_load && !x.bias && !x.scale && !x.relu && !(x.stat_part && x.accumulate)) {
         r.family = (g.T == 1 && dcfp_igemm2_persist()) ? IGEMM2_DMA1P : IGEMM2_DMA;
         r.mixed = g.T == 9 && off_grid && !g.pitched();      // pitched rows: shifted quads need no border handling
     } else
@@ -1193,9 +1195,15 @@ int dcfp_igemm2_run(const GemmProblem& g, const float* in, const float* w, float
                     const GemmExtras& x, hipStream_t stream) {
     if (x.red && !x.fan_src) return DCFP_E_BADDESC;
     const int T = g.T;
-    const bool vec_store = (g.P() % 4 == 0) && (g.out_nstride % 4 == 0) && dcfp_aligned16(out);
-    const Igemm2Route r = igemm2_route(g, x, vec_store);
+    // (the inference epilogue reads its residual, laid out as the output, with the output's vector width)
+    const bool vec_store = (g.P() % 4 == 0) && dcfp_quad_operand(out, g.out_nstride) && dcfp_aligned16(x.residual);
+    const bool vec_load = dcfp_quad_operand(in, g.in_nstride);
+    const Igemm2Route r = igemm2_route(g, x, vec_store, vec_load);
     const bool d8 = r.family == IGEMM2_DMA8;
+    // everything that refuses the call comes before the first launch (the weight permute below)
+    if ((x.wp_nstride || x.fan_src) && r.family != IGEMM2_DMA1P) return DCFP_E_UNSUPPORTED;   // per-image weights / masked fan-in: the persistent 1x1 kernel only
+    if (x.fan_src && (g.M % 256 != 0 || g.P() % 256 != 0 || !dcfp_aligned16(x.fan_src) || (x.red && !dcfp_aligned16(x.red->x))))
+        return DCFP_E_UNSUPPORTED;
     Igemm2Params p = {};
     set_tiling(p, g, r);
     p.stat_part = x.stat_part;
@@ -1209,8 +1217,8 @@ int dcfp_igemm2_run(const GemmProblem& g, const float* in, const float* w, float
     if (g.pitched()) {   // only the 9-tap LDS-DMA kernels read pitched sources; every tap's column shift must fit the tail
         const int reach = g.off0 < 0 ? -g.off0 : g.off0;      // |first tap shift|; the last is off0 + 2*offstep = -off0 (pad = dil)
         if (T != 9 || p.in_pitch < g.Wi + reach || g.off0 + 2 * g.offstep != -g.off0 || (p.in_pitch & 3) ||
-            (!d8 && (x.bias || !r.dma_shape)) || x.scale || x.relu)
-            return DCFP_E_UNSUPPORTED;
+            (!d8 && (x.bias || !r.dma_shape)) || x.scale || x.relu || r.family == IGEMM2_TILE)
+            return DCFP_E_UNSUPPORTED;                  // (a pitched source or its output off the 16-byte grid included)
         if (!d8 && x.stat_part && dcfp_igemm2_use_dma8(g))
             return DCFP_E_UNSUPPORTED;                  // (cannot happen: such shapes report no statistics slots)
     }
@@ -1232,10 +1240,7 @@ int dcfp_igemm2_run(const GemmProblem& g, const float* in, const float* w, float
         hipLaunchKernelGGL(permute_weights_kernel, dim3((unsigned)b), dim3(256), 0, stream, w, wp, T,
                            g.Ck, p.CkP, g.M, p.Mpad, g.sAm, g.sAc, d8 ? 1 : 0);
     }
-    if (d8) {
-        if (!p.vec_store || x.wp_nstride || x.fan_src) return DCFP_E_UNSUPPORTED;
-        return dcfp_igemm2n_launch(p, T, stream);
-    }
+    if (d8) return dcfp_igemm2n_launch(p, T, stream);
     if (r.family != IGEMM2_TILE) {
         const long long groups = ((long long)p.tiles_n_total + 7) / 8;
         const long long blocks = groups * 8 * p.tiles_m;
@@ -1250,16 +1255,13 @@ int dcfp_igemm2_run(const GemmProblem& g, const float* in, const float* w, float
         };
         const bool accumulate = x.accumulate != 0;
         if (T == 1) {
-            if (x.fan_src && (g.M % 256 != 0 || p.P % 256 != 0 || r.family != IGEMM2_DMA1P)) return DCFP_E_UNSUPPORTED;
             if (r.family == IGEMM2_DMA1P) return dcfp_igemm2p_launch(p, stream);
-            if (x.wp_nstride) return DCFP_E_UNSUPPORTED;
             return accumulate ? launch(igemm2_dma_kernel<1, false, true>) : launch(igemm2_dma_kernel<1, false, false>);
         }
         if (!r.mixed)
             return accumulate ? launch(igemm2_dma_kernel<9, false, true>) : launch(igemm2_dma_kernel<9, false, false>);
         return accumulate ? launch(igemm2_dma_kernel<9, true, true>) : launch(igemm2_dma_kernel<9, true, false>);
     }
-    if (x.wp_nstride || x.fan_src) return DCFP_E_UNSUPPORTED;     // per-image weights / masked fan-in: the persistent 1x1 kernel only
     return T == 1 ? launch_taps<1>(p, r.cfg, stream) : launch_taps<9>(p, r.cfg, stream);
 }
 

@@ -288,7 +288,8 @@ bool dcfp_stem_shape(const DcfpConvDesc* d) {
 // (mean, M2) partials over 128 pixels each that the forward can emit for the BatchNorm behind the conv, or 0
 long long dcfp_stem_stat_slots(const DcfpConvDesc* d, const float* y, long long y_nstride) {
     if (d->Wout % 128 != 0) return 0;
-    (void)y; (void)y_nstride;
+    // (the kernel has 16-byte stores only: an output off that grid is written by the tile kernels, without statistics)
+    if (!dcfp_aligned16(y) || (y_nstride ? y_nstride : (long long)d->Cout * d->Hout * d->Wout) % 4 != 0) return 0;
     return (long long)d->N * d->Hout * d->Wout / 128;
 }
 

@@ -761,7 +761,9 @@ bool dma_geometry(const DcfpConvDesc* d) {
     return wgrad_dma_on() && d->stride == 1 && d->Hout == d->H && d->Wout == d->W && d->W % 16 == 0;
 }
 
-Plan make_plan(const DcfpConvDesc* d) {
+// dma = false: the plan of a call whose dy or x the LDS-DMA kernels cannot copy from (off the 16-byte grid) - the
+// register-staged tiles only
+Plan make_plan(const DcfpConvDesc* d, bool dma = true) {
     Plan pl;
     const int M = d->Cout, Nn = d->Cin * d->KH * d->KW;
     // cfg: 0 = 256x256, 1 = 128x256, 2 = 64x64 (one wave), and - round 2 - tiles for the lop-sided weight
@@ -787,7 +789,7 @@ Plan make_plan(const DcfpConvDesc* d) {
         static const int mode = [] { const char* e = getenv("DCFP_WGRAD_WIDE"); return e ? atoi(e) : 1; }();
         const bool mixed = d->KH == 3 && ((d->pad | d->dil) & 3) != 0;
         const bool x_pitched = d->x_pitch && d->x_pitch != d->W;
-        const bool eligible = mode != 0 && !math_bf16x3() && dma_geometry(d) && Nn > 128 && (!mixed || x_pitched) &&
+        const bool eligible = dma && mode != 0 && !math_bf16x3() && dma_geometry(d) && Nn > 128 && (!mixed || x_pitched) &&
                               !(d->KH == 3 && d->pad != d->dil);
         if (eligible) {
             const long long old_rows = (long long)((M + pl.bm - 1) / pl.bm) * pl.bm, new_rows = (long long)((M + 31) / 32) * 32;
@@ -803,7 +805,7 @@ Plan make_plan(const DcfpConvDesc* d) {
     pl.half = false;
     {
         static const bool on = [] { const char* e = getenv("DCFP_WGRAD_HALF"); return !e || atoi(e) != 0; }();   // =0: off
-        if (on && pl.cfg == 0 && !pl.wide && d->KH == 1 && M % 128 == 0 && !math_bf16x3() && dma_geometry(d)) {
+        if (dma && on && pl.cfg == 0 && !pl.wide && d->KH == 1 && M % 128 == 0 && !math_bf16x3() && dma_geometry(d)) {
             pl.half = true; pl.bm = 128;
         }
     }
@@ -1068,10 +1070,20 @@ double dcfp_wgrad_exec_fraction(const DcfpConvDesc* d) {
     return wino_wgrad_pass(d) ? dcfp_wino_exec_fraction(wino_problem(gemm_problem(d, DCFP_CONV_FWD, 0))) : 1.0;
 }
 
+// split-K slabs of the direct kernels: the larger of the two plans a call can take (LDS-DMA / register-staged only)
+static size_t direct_workspace_bytes(const DcfpConvDesc* d) {
+    const Plan a = make_plan(d, true), b = make_plan(d, false);
+    const int splits = a.splits > b.splits ? a.splits : b.splits;
+    return splits > 1 ? (size_t)splits * d->Cout * d->Cin * d->KH * d->KW * sizeof(float) : 0;
+}
+
 extern "C" size_t dcfp_conv2d_workspace_bytes(const DcfpConvDesc* d, int pass) {
     if (pass == DCFP_CONV_FWD || pass == DCFP_CONV_DGRAD) return dcfp_conv2d_fwd_dgrad_workspace_bytes_(d, pass);
     if (pass != DCFP_CONV_WGRAD || check_desc(d) != DCFP_OK) return 0;
-    if (dcfp_stem_shape(d)) return dcfp_stem_wgrad_workspace_bytes(d);
+    if (dcfp_stem_shape(d)) {      // (or the general kernels, for a dy off the 16-byte grid)
+        const size_t a = dcfp_stem_wgrad_workspace_bytes(d), b = direct_workspace_bytes(d);
+        return a > b ? a : b;
+    }
     if (const int wk = wino_wgrad_kind(d)) {
         // (kind 2 can fall back to the batched path at run time - a dy slice whose image stride breaks the 31-bit offsets -
         //  so the query covers both where both apply)
@@ -1081,14 +1093,11 @@ extern "C" size_t dcfp_conv2d_workspace_bytes(const DcfpConvDesc* d, int pass) {
         // kind 2 falls back at run time when the REAL image stride of dy (a channel slice of a wider tensor) breaks the
         // kernel's 31-bit offsets: to the batched path where that applies, else to the direct kernels - the query covers all
         const size_t b2 = dcfp_wino_wgrad_fused_workspace_bytes(d->N, d->H, d->W, d->dil, d->Cout, d->Cin);
-        const Plan pl = make_plan(d);
-        const size_t b0 = pl.splits > 1 ? (size_t)pl.splits * d->Cout * d->Cin * d->KH * d->KW * sizeof(float) : 0;
+        const size_t b0 = direct_workspace_bytes(d);
         const size_t m = b1 > b0 ? b1 : b0;
         return b2 > m ? b2 : m;
     }
-    const Plan pl = make_plan(d);
-    if (pl.splits <= 1) return 0;
-    return (size_t)pl.splits * d->Cout * d->Cin * d->KH * d->KW * sizeof(float);
+    return direct_workspace_bytes(d);
 }
 
 extern "C" int dcfp_conv2d_wgrad_f32_nchw(const DcfpConvDesc* d, const float* dy,
@@ -1100,12 +1109,15 @@ extern "C" int dcfp_conv2d_wgrad_f32_nchw(const DcfpConvDesc* d, const float* dy
     if (!dy || !x || !dw) return DCFP_E_BADDESC;
     if (dcfp_gemv_shape(d) && !db)      // a 1x1 conv on a 1 x 1 map (ASPP image pool): conv_gemv.hip
         return dcfp_gemv_wgrad(d, dy, dy_nstride, x, dw, dcfp_s(stream));
-    if (dcfp_stem_shape(d) && !db)      // Cin = 3, stride 2 (backbone.conv1.0): conv_stem.hip
+    // Cin = 3, stride 2 (backbone.conv1.0): conv_stem.hip (16-byte loads of dy: off that grid, the general kernels below)
+    if (dcfp_stem_shape(d) && !db && dcfp_quad_operand(dy, dy_nstride ? dy_nstride : (long long)d->Cout * d->Hout * d->Wout))
         return dcfp_stem_wgrad(d, dy, dy_nstride, x, dw, workspace, workspace_bytes, dcfp_s(stream));
     int wk = wino_wgrad_kind(d);
     const WgradOperands o = wgrad_operands(d, dy_nstride);
     // (the descriptor-level decision assumed a dense batch stride for dy: check the real one)
-    if (wk == 2 && !dcfp_wino_wgrad_fused_ok(d->N, d->H, d->W, d->dil, d->Cout, d->Cin, o.xn, o.xp, o.dyn, o.dyp))
+    // every LDS-DMA weight-gradient kernel copies 16 bytes at a time from dy and x
+    const bool quads = dcfp_quad_operand(dy, o.dyn) && dcfp_quad_operand(x, o.xn);
+    if (wk == 2 && (!quads || !dcfp_wino_wgrad_fused_ok(d->N, d->H, d->W, d->dil, d->Cout, d->Cin, o.xn, o.xp, o.dyn, o.dyp)))
         wk = dcfp_wino_wgrad_ok(d->N, d->H, d->W, d->dil, d->Cout, d->Cin) ? 1 : 0;     // batched Winograd, or the direct kernels below
     if (wk) {
         if (db && o.dyp != d->Wout) return DCFP_E_UNSUPPORTED;      // (the bias-gradient kernel reads dense rows; nothing launched yet)
@@ -1121,7 +1133,7 @@ extern "C" int dcfp_conv2d_wgrad_f32_nchw(const DcfpConvDesc* d, const float* dy
                                d->Hout * d->Wout, (int)((d->Hout * d->Wout) % 4 == 0 && o.dyn % 4 == 0 && dcfp_aligned16(dy)));
         DCFP_RETURN_LAUNCH();
     }
-    const Plan pl = make_plan(d);
+    const Plan pl = make_plan(d, quads);
     const int T = d->KH * d->KW;
     const long long wn = (long long)d->Cout * d->Cin * T;
     const size_t need = pl.splits > 1 ? (size_t)pl.splits * wn * sizeof(float) : 0;
@@ -1155,7 +1167,7 @@ extern "C" int dcfp_conv2d_wgrad_f32_nchw(const DcfpConvDesc* d, const float* dy
         const long long blocks = (long long)pl.tiles_m * pl.tiles_n * pl.splits;
         if (blocks > 0x7fffffffLL) return DCFP_E_UNSUPPORTED;
         rc = T == 1 ? launch_dma<1, false, true>(p, blocks, dcfp_s(stream)) : launch_dma<9, false, true>(p, blocks, dcfp_s(stream));
-    } else if (wgrad_dma_ok(d, pl.cfg)) {
+    } else if (quads && wgrad_dma_ok(d, pl.cfg)) {
         const long long blocks = (long long)pl.tiles_m * pl.tiles_n * pl.splits;
         if (blocks > 0x7fffffffLL) return DCFP_E_UNSUPPORTED;
         // (pitched x: every shifted quad reads data or the rows' zero tails - the un-mixed kernel does it all)

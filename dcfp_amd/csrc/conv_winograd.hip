@@ -493,9 +493,17 @@ int dcfp_wino_run(const GemmProblem& g, const float* in, const float* w, float* 
     // DCFP_WINO_FUSED=2 takes it wherever it applies (tests).
     const bool three_ok = dcfp_wino_ok(q);
     const bool fused_wins = wino_fused_mode() == 2 || !three_ok || !(xform_out && Ck > 256);
-    if (fused_wins && dcfp_wino_fused_ok(q) && workspace_bytes >= dcfp_wino_fused_workspace_bytes(q)) {
+    // (the fused kernel copies 16 bytes at a time from `in` into LDS: a source off the 16-byte grid takes the three passes,
+    //  whose input transform reads 4-byte elements then, or - where they do not apply or the caller's workspace is the
+    //  fused kernel's - the register-staged direct kernel, which builds its own permuted copy in the workspace)
+    const bool in_quads = dcfp_quad_operand(in, in_nstride);
+    if (fused_wins && in_quads && dcfp_wino_fused_ok(q) && workspace_bytes >= dcfp_wino_fused_workspace_bytes(q)) {
         if (stat_part && (!dcfp_wino_stat_slots(q) || accumulate)) return DCFP_E_UNSUPPORTED;
         return dcfp_wino_fused_run(g, in, w, out, workspace, workspace_bytes, x, stream);
+    }
+    if (!in_quads && (!three_ok || workspace_bytes < dcfp_wino_workspace_bytes(q))) {
+        if (xform_out || stat_part) return DCFP_E_UNSUPPORTED;      // (both are laid out by Winograd tiles; nothing launched)
+        return dcfp_igemm2_run(g, in, w, out, workspace, workspace_bytes, x, stream);
     }
     if (!three_ok) return DCFP_E_UNSUPPORTED;
     if (workspace_bytes < dcfp_wino_workspace_bytes(q)) return DCFP_E_WORKSPACE;
@@ -522,7 +530,9 @@ int dcfp_wino_run(const GemmProblem& g, const float* in, const float* w, float* 
     gx.wp_nstride = (long long)pl.CkP * pl.Mpad;
     const int rc = dcfp_igemm2_run(batched_gemm(pl, M, Ck), V, /*w=*/nullptr, Mb, U, (size_t)pl.u_floats * sizeof(float), gx, stream);
     if (rc) return rc;
-    const int ovec = wino_vec(d, W, W, out, out_nstride, pl.TW);
+    // (the residual of the inference epilogue is read with the output's vector width)
+    const int rvec = x.residual ? wino_vec(d, W, W, x.residual, out_nstride, pl.TW) : 4;
+    const int ovec0 = wino_vec(d, W, W, out, out_nstride, pl.TW), ovec = ovec0 < rvec ? ovec0 : rvec;
     const unsigned gout = (unsigned)((tpi / ovec + 255) / 256);
 #define DCFP_WINO_OUT(VEC_, ST_) hipLaunchKernelGGL((wino_output_kernel<VEC_, ST_>), dim3(gout, (unsigned)N, (unsigned)M), dim3(256), 0, \
                                                stream, Mb, pl.T16, M, out, out_nstride, H, W, d, pl.TH, pl.TW, accumulate, stat_part, x.scale, x.shift, x.residual, x.relu)

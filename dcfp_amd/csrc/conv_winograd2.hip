@@ -594,6 +594,7 @@ static int fused_mode(const WinoProblem& q) {
 bool dcfp_wino_fused_ok(const WinoProblem& q) {
     if (wino_fused_mode() == 0) return false;
     if (q.M < 48 || q.Ck < 48) return false;       // (the cost model of conv_igemm.hip decides above that)
+    if (q.in_nstride % 4 != 0) return false;       // (the patches are copied into LDS 16 bytes at a time: images whole quads apart)
     const FusedPlan pl = fused_plan(q.N, q.H, q.W, q.d, q.M, q.Ck);
     if (pl.T16 >= (1LL << 30) || pl.tblocks >= (1LL << 30) || pl.tblocks * pl.mblocks + 8 * pl.mblocks >= (1LL << 31)) return false;
     if ((long long)pl.CkP * pl.Mpad * 16 * 4 >= 0x7fffff00LL) return false;
@@ -656,7 +657,7 @@ int dcfp_wino_fused_run(const GemmProblem& g, const float* in, const float* w, f
     p.ragged_c = (Ck % 16) != 0;
     {
         const long long ospan = ((long long)(N - 1) * out_nstride + (long long)M * H * W) * 4;
-        p.vec_epi = W % 4 == 0 && out_nstride % 4 == 0 && dcfp_aligned16(out) && ospan < 0x7fffff00LL &&
+        p.vec_epi = W % 4 == 0 && out_nstride % 4 == 0 && dcfp_aligned16(out) && dcfp_aligned16(x.residual) && ospan < 0x7fffff00LL &&
                     (mode != 4 || d % 4 == 0);
         p.out_bytes = p.vec_epi ? (unsigned)ospan : 0u;
         static const int no_vec = [] { const char* e = getenv("DCFP_WF_SCALAR_EPI"); return e ? atoi(e) : 0; }();

@@ -476,6 +476,9 @@ bool dcfp_wino_wgrad_fused_ok(int N, int H, int W, int d, int M, int C, long lon
     if (M < 48 || C < 48) return false;        // (the cost model of conv_wgrad.hip decides above that)
     if (x_pitch <= 0) x_pitch = W;
     if (dy_pitch <= 0) dy_pitch = W;
+    // (both operands are copied into LDS 16 bytes at a time: images a whole number of quads apart - and 16-byte aligned
+    //  bases, which the entry point checks: dcfp_conv2d_wgrad_f32_nchw)
+    if (x_nstride % 4 != 0 || dy_nstride % 4 != 0) return false;
     if (wg_mode(N, H, W, d, M, C, x_nstride, x_pitch, dy_nstride, dy_pitch) < 0) return false;
     const WgPlan pl = wg_plan(N, H, W, d, M, C);
     if (pl.T16 >= (1LL << 30) || pl.T16 / 2 * 32 >= 0x7fffff00LL) return false;

@@ -100,6 +100,23 @@ def _batch_strided(t):
     return t, Cc * H * W
 
 
+def _on_grid(t, nstride):
+    """True where the 16-byte paths may touch `t`: it starts on the 16-byte grid and its images are whole quads apart.
+    An LDS-DMA conv route needs that of its source, a vector epilogue of its output (include/dcfp_hip.h); a call with an
+    operand off the grid runs other kernels, with another layout of the permuted weight copy."""
+    return t.data_ptr() % 16 == 0 and nstride % 4 == 0
+
+
+def _grid_variant(src_ok, out_ok, src_dense=0, out_dense=0, out_px=0):
+    """Suffix of the kept-copy key of a conv call (_wp_buffer's variant): calls whose operands sit off the 16-byte grid
+    keep a copy of their own, since the kernel they fall back to reads another layout.  src_dense / out_dense / out_px:
+    the dense image strides and the output pixels per channel - where those are no whole quads the call with aligned
+    operands has no 16-byte path either, and an operand off the grid changes nothing."""
+    src_ok = src_ok or src_dense % 4 != 0
+    out_ok = out_ok or out_dense % 4 != 0 or out_px % 4 != 0
+    return "" if (src_ok and out_ok) else f"@{int(src_ok)}{int(out_ok)}"
+
+
 def _pitch_of(t):
     """Row pitch of a [N,C,H,W] tensor whose rows are dense but stride(2) > W (a [..., :W] view of a buffer with
     padded rows, channels H*pitch and images C*H*pitch apart); 0 for anything else (dense included)."""
@@ -357,10 +374,25 @@ def conv2d_fwd(x, w, bias=None, stride=1, pad=0, dil=1, want_stats=False, bn_run
     if bias is not None:
         _require(bias, "bias"); bias = bias.contiguous()
     L = _lib.lib()
+    x_ok = _on_grid(x, d.Cin * d.H * (xp or d.W))
+    y_ok = _on_grid(y, yns or d.Cout * d.Hout * d.Wout)
+    if xp and not (x_ok and y_ok):
+        # only the LDS-DMA kernels read row-pitched sources, and those need both operands on the 16-byte grid
+        x = x.contiguous()
+        xp, d = 0, _desc(x.shape, w.shape, stride, pad, dil, 0, 0)
+        x_ok = _on_grid(x, d.Cin * d.H * d.W)
     # (a 3x3 conv WITH bias never runs as Winograd: where the same descriptor without bias does, the kept buffer holds
     #  transformed filters, not the direct kernel's permuted copy - the biased call gets a copy of its own)
-    variant = "bias" if (bias is not None and d.KH == 3 and conv_kernel_name(d, _lib.CONV_FWD).startswith("winograd")) else ""
+    wino = d.KH == 3 and conv_kernel_name(d, _lib.CONV_FWD).startswith("winograd")
+    variant = ("bias" if (bias is not None and wino) else "") + \
+        _grid_variant(x_ok, y_ok, d.Cin * d.H * (xp or d.W), d.Cout * d.Hout * d.Wout, d.Hout * d.Wout)
     ws, valid = _conv_workspace(w, _lib.CONV_FWD, d, variant)
+    if wino and not x_ok:
+        # (a Winograd conv whose x is off the grid runs a direct kernel: no transformed input to keep, no statistics laid
+        #  out by Winograd tiles - the weight gradient transforms x itself, the BatchNorm runs its own statistics kernel)
+        keep, want_stats, no_stats = None, False, want_stats
+    else:
+        no_stats = False
     if keep is not None and KEEP_XFORM and bias is None:
         # Winograd conv whose weight gradient is Winograd too: leave the transformed input in a buffer that `keep`
         # (a dict living in the autograd context) holds until the backward pass (conv2d_wgrad(..., xform=))
@@ -393,7 +425,7 @@ def conv2d_fwd(x, w, bias=None, stride=1, pad=0, dil=1, want_stats=False, bn_run
     _timed("conv_fwd", d, _conv_flops(d), lambda: check(
         L.dcfp_conv2d_fwd_f32_nchw(C.byref(d), _p(x), _p(w), _p(bias), _p(y), yns, _p(ws), ws.numel(), valid,
                                    _stream()), "conv2d_fwd"))
-    return (y, None) if want_stats else y
+    return (y, None) if (want_stats or no_stats) else y
 
 
 def conv2d_dgrad(dy, w, xshape, stride, pad, dil, out=None, accumulate=False):
@@ -402,10 +434,6 @@ def conv2d_dgrad(dy, w, xshape, stride, pad, dil, out=None, accumulate=False):
     w = w if w.is_contiguous() else w.contiguous()
     dp = _pitch_of(dy)
     d = _desc(xshape, w.shape, stride, pad, dil, 0, dp)
-    if dp:
-        ns = dy.stride(0)
-    else:
-        dy, ns = _batch_strided(dy)
     if out is not None:
         if tuple(out.shape) != tuple(xshape) or not out.is_contiguous():
             raise RuntimeError("conv2d_dgrad: out must be a contiguous tensor of the input shape")
@@ -413,8 +441,17 @@ def conv2d_dgrad(dy, w, xshape, stride, pad, dil, out=None, accumulate=False):
     else:
         dx = torch.empty(xshape, dtype=torch.float32, device=dy.device)
         accumulate = False
+    dx_ok = _on_grid(dx, d.Cin * d.H * d.W)
+    if dp and not (dx_ok and _on_grid(dy, dy.stride(0))):
+        dy, dp = dy.contiguous(), 0         # (as in conv2d_fwd: pitched sources are read by the LDS-DMA kernels only)
+        d = _desc(xshape, w.shape, stride, pad, dil, 0, 0)
+    if dp:
+        ns = dy.stride(0)
+    else:
+        dy, ns = _batch_strided(dy)
     L = _lib.lib()
-    ws, valid = _conv_workspace(w, _lib.CONV_DGRAD, d)
+    ws, valid = _conv_workspace(w, _lib.CONV_DGRAD, d, _grid_variant(
+        _on_grid(dy, ns), dx_ok, d.Cout * d.Hout * (dp or d.Wout), d.Cin * d.H * d.W, d.H * d.W))
     _timed("conv_dgrad", d, _conv_flops(d), lambda: check(
         L.dcfp_conv2d_dgrad_f32_nchw(C.byref(d), _p(dy), ns, _p(w), _p(dx), int(bool(accumulate)),
                                      _p(ws), ws.numel(), valid, _stream()), "conv2d_dgrad"))
@@ -439,6 +476,13 @@ def conv2d_dgrad_fanin(dy, w, xshape, fan_src, fan_mask):
     dy, ns = _batch_strided(dy)
     if tuple(fan_src.shape) != tuple(xshape) or not fan_src.is_contiguous():
         raise RuntimeError("conv2d_dgrad_fanin: fan_src must be a contiguous tensor of the input shape")
+    # the fan-in epilogue exists on the persistent LDS-DMA kernel only, which the library refuses for operands off the
+    # 16-byte grid (nothing in the package produces one here): they are copied onto it
+    if not _on_grid(dy, ns):
+        dy = dy.clone(memory_format=torch.contiguous_format)
+        ns = dy.stride(0)
+    if not _on_grid(fan_src, 4):
+        fan_src = fan_src.clone()
     dx = torch.empty(xshape, dtype=torch.float32, device=dy.device)
     ws, valid = _conv_workspace(w, _lib.CONV_DGRAD, d)
     _timed("conv_dgrad", d, _conv_flops(d), lambda: check(
@@ -2149,6 +2193,7 @@ def conv2d_fused_infer(x, w, scale, shift, stride=1, pad=0, dil=1, residual=None
     x = x.contiguous(); w = w.contiguous()
     d = _desc(x.shape, w.shape, stride, pad, dil)
     y = torch.empty((d.N, d.Cout, d.Hout, d.Wout), dtype=torch.float32, device=x.device)
+    fused = "fused" + _grid_variant(_on_grid(x, d.Cin * d.H * d.W), True, d.Cin * d.H * d.W)
     if residual is not None:
         residual = residual.contiguous()
         if tuple(residual.shape) != tuple(y.shape):
@@ -2157,7 +2202,7 @@ def conv2d_fused_infer(x, w, scale, shift, stride=1, pad=0, dil=1, residual=None
     if L.dcfp_conv2d_workspace_is_scratch(C.byref(d), _lib.CONV_FWD):
         ws, valid = _workspace("conv_scratch", L.dcfp_conv2d_workspace_bytes(C.byref(d), _lib.CONV_FWD), x.device), 0
     else:
-        ws, valid = _wp_buffer(w, _lib.CONV_FWD, d, L.dcfp_conv2d_workspace_bytes(C.byref(d), _lib.CONV_FWD), "fused")
+        ws, valid = _wp_buffer(w, _lib.CONV_FWD, d, L.dcfp_conv2d_workspace_bytes(C.byref(d), _lib.CONV_FWD), fused)
     check(L.dcfp_conv2d_fwd_fused_f32_nchw(C.byref(d), _p(x), _p(w), _p(scale.contiguous()),
                                            _p(shift.contiguous()), _p(residual), int(bool(relu)), _p(y),
                                            _p(ws), ws.numel(), valid, _stream()), "conv2d_fwd_fused")

@@ -198,7 +198,27 @@ double dcfp_conv2d_executed_fraction(const DcfpConvDesc* d, int pass);
  * the components issued over all tiles (dcfp_conv2d_executed_fraction counts 16 per enumerated tile). */
 int dcfp_wino_tile_plan(int N, int H, int W, int d, int ragged, int classes, int64_t* out);
 
-/* y = conv(x, w) (+ bias[co] when bias != NULL).  y_nstride: batch stride of y in
+/* Alignment contract of the fp32 conv entry points (dcfp_conv2d_*_f32_nchw): x, w, bias, y, dy, dx, dw, db, residual,
+ * scale and shift may be ANY 4-byte aligned address, and every image stride any count of floats.  16-byte alignment (with
+ * an image stride that is a multiple of 4 floats) only selects faster kernels: the LDS-DMA families (igemm2_dma*,
+ * the fused Winograd kernels, wgrad_dma_kernel) copy 16 bytes at a time from x / dy and are taken only when that source is
+ * 16-byte aligned; the 16-byte epilogues, the stem kernels and the fused BatchNorm statistics only when y (dy for the
+ * stem's weight gradient, residual for the inference epilogue) is.  Anything else runs the register-staged kernels,
+ * within the same error bounds but - on a shape that would have taken an LDS-DMA kernel - with another summation order.
+ * dcfp_conv2d_kernel_name names the kernel of the call whose operands are all 16-byte aligned.  Consequences and exceptions:
+ *  - `workspace`, `xform` / `xform_out` and `red_part` keep the alignment stated with them (16 / 16 / 8 bytes).
+ *  - wp_valid != 0 vouches for a copy built by a call with the same descriptor, pass AND the same two answers to "is the
+ *    source 16-byte aligned / is the output": a call off the grid may run a kernel with another layout of the copy, so a
+ *    caller keeps one buffer per such class (or passes 0).
+ *  - a row-pitched x / dy (x_pitch / dy_pitch) is read by LDS-DMA kernels only: it and the call's output must be 16-byte
+ *    aligned, else DCFP_E_UNSUPPORTED (nothing is launched).
+ *  - dcfp_conv2d_fwd_stats_f32_nchw / dcfp_conv2d_fwd_keep_f32_nchw on a Winograd descriptor, and the dgrad fan-in
+ *    (dy, fan_src, red_x): the statistics, the kept transform and the fan-in epilogue exist on the LDS-DMA kernels only, so
+ *    x / dy / fan_src / red_x must be 16-byte aligned, else DCFP_E_UNSUPPORTED (nothing is launched);
+ *    dcfp_conv2d_fwd_stat_slots answers 0 for a y the statistics epilogue cannot take.
+ * No call launches anything before it is refused.
+ *
+ * y = conv(x, w) (+ bias[co] when bias != NULL).  y_nstride: batch stride of y in
  * elements (0 => Cout*Hout*Wout), lets a branch write into a channel slice of a
  * wider tensor (ASPP concat, aspp.py:77). */
 int dcfp_conv2d_fwd_f32_nchw(const DcfpConvDesc* d, const float* x, const float* w,
@@ -229,6 +249,13 @@ int dcfp_conv2d_wgrad_f32_nchw(const DcfpConvDesc* d, const float* dy, int64_t d
  * Replaces nn.BatchNorm2d(+ReLU inplace)(+residual add) train fwd/bwd:
  *   resnet.py:9,26-33,41-56; aspp.py:15-16,22-24; deeplabv3.py:26-31,38-39.
  * Statistics over (N,H,W) per channel; biased variance for normalisation.
+ * Alignment: every float tensor (x, y, dy, dx, residual, d_residual, the per-channel vectors) may be any 4-byte aligned
+ * address with any image stride; 16-byte alignment with HW % 4 == 0 and strides of whole quads only selects the 16-byte
+ * kernels (same values: the kernels are per element or add in an order that does not depend on the vector width, except
+ * dcfp_bn_stats_f32 / dcfp_bn_bwd_reduce_f32, whose sums are chunked by the access width).  Exceptions: the bit mask of
+ * dcfp_bn_apply_relu_mask_f32 is 8-byte aligned, workspaces as stated, and dcfp_bn_apply_relu_mask_f32 and
+ * dcfp_bn_bwd_fused_f32 take 16-byte aligned tensors only (DCFP_E_UNSUPPORTED otherwise, nothing launched: run
+ * dcfp_bn_apply_f32 / the two backward kernels).
  */
 /* Module-side bookkeeping of a training-mode nn.BatchNorm2d forward, folded into the kernel that
  * finalises the statistics (resnet.py:9: momentum 0.1): when running_mean != NULL,
@@ -361,6 +388,10 @@ int dcfp_bn_bwd_fused_f32(const float* dy, int64_t dy_nstride, const float* x, c
                           uint32_t spin_limit, int32_t* status, dcfp_stream_t stream);
 
 /* ------------------------------------------------- element-wise / pooling
+ * Alignment of the entry points of this section and of the pyramid pooling below: any 4-byte aligned float tensor, any
+ * image stride; 16-byte alignment (with W % 8 == 0 for the max pool, W % 4 == 0 / HW % 4 == 0 / pitches and strides of
+ * whole quads elsewhere) only selects the 16-byte kernels, which give the same values - the same bits, except the row
+ * sums of dcfp_rowsum_f32, whose order follows the access width.
  * MaxPool2d(3,2,1) (resnet.py:100,149): -inf padding, first-max index. */
 int dcfp_maxpool3x3s2_fwd_f32(const float* x, float* y, int32_t* argmax,
                               int N, int C, int H, int W, int Hout, int Wout,
