@@ -72,6 +72,28 @@ class AdamEntry(C.Structure):
                 ("n", C.c_int64), ("first_chunk", C.c_int64)]
 
 
+class NormEntry(C.Structure):
+    """DcfpNormEntry: one gradient tensor of a dcfp_grad_norm_f32 call."""
+    _fields_ = [("data", C.c_void_p), ("n", C.c_int64), ("first_chunk", C.c_int64)]
+
+
+class GradNorm(C.Structure):
+    """DcfpGradNorm: what dcfp_grad_norm_f32 leaves on the device."""
+    _fields_ = [("sqnorm", C.c_double), ("norm", C.c_float), ("coef", C.c_float)]
+
+
+class SgdExEntry(C.Structure):
+    """DcfpSgdExEntry: DcfpSgdEntry plus the (nullable) EMA pointer."""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("momentum_buf", C.c_void_p), ("ema", C.c_void_p),
+                ("n", C.c_int64), ("first_chunk", C.c_int64), ("weight_decay", C.c_float), ("pad_", C.c_int32)]
+
+
+class AdamExEntry(C.Structure):
+    """DcfpAdamExEntry: DcfpAdamEntry plus the (nullable) EMA pointer."""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("ema", C.c_void_p), ("n", C.c_int64), ("first_chunk", C.c_int64)]
+
+
 class BnRunning(C.Structure):
     """DcfpBnRunning: nn.BatchNorm2d's training-mode bookkeeping folded into the statistics kernels."""
     _fields_ = [("running_mean", C.c_void_p), ("running_var", C.c_void_p), ("num_batches_tracked", C.c_void_p),
@@ -266,6 +288,10 @@ SIGNATURES = {
     "dcfp_fpgm_f32": (_I, [_P, _I, _L, _P, _Z, _P]),
     "dcfp_state_digest_workspace_bytes": (_Z, [_Z]),
     "dcfp_state_digest_u64": (_I, [_P, _Z, C.c_uint64, _P, _Z, _P, _P]),
+    "dcfp_grad_norm_workspace_bytes": (_Z, [_L]),
+    "dcfp_grad_norm_f32": (_I, [_P, _I, _L, _F, _P, _Z, _P, _P, _P]),
+    "dcfp_sgd_momentum_ex_f32": (_I, [_P, _I, _L, _F, _F, _I, _P, _F, _P]),
+    "dcfp_adamw_ex_f32": (_I, [_P, _I, _L, _F, _F, _F, _F, _F, _F, _F, _P, _F, _P]),
     "dcfp_engine_open": (_I, [C.c_char_p, C.POINTER(_P), C.c_char_p, _Z]),
     "dcfp_engine_open_memory": (_I, [_P, _Z, C.POINTER(_P), C.c_char_p, _Z]),
     "dcfp_engine_close": (None, [_P]),

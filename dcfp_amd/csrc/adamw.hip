@@ -2,36 +2,11 @@
 // tensors as ONE launch over a device-resident pointer table, in the manner of sgd_momentum_kernel.
 // Streaming: 16 B read and 12 B written per element; one block per DCFP_SGD_CHUNK elements of one tensor.
 #include "common.h"
+#include "optim_step.h"
 
 namespace {
 
-typedef __attribute__((address_space(1))) float gfloat;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) f32x4 gfloat4;
-
-struct AdamK {
-    float decay;     // float(1 - lr*wd)
-    float step;      // float(lr / bias_correction1)
-    float w1;        // float(1 - beta1): the lerp weight
-    float beta2;
-    float omb2;      // float(1 - beta2)
-    float bc2_sqrt;
-    float eps;
-};
-
-// One element, in the order of torch's _single_tensor_adam (decoupled decay).  Every operation is spelled as an
-// intrinsic with one rounding (no contraction left to the compiler), so the float4 body and the scalar body give
-// the same bits for the same element.
-__device__ __forceinline__ void adamw_one(float& p, const float g, float& m, float& v, const AdamK k) {
-    const float p1 = __fmul_rn(p, k.decay);                                  // p.mul_(1 - lr*wd)
-    const float diff = __fsub_rn(g, m);                                      // m.lerp_(g, 1 - beta1), ATen's two forms
-    const float m1 = (k.w1 < 0.5f) ? fmaf(k.w1, diff, m) : fmaf(-__fsub_rn(1.f, k.w1), diff, g);
-    const float v1 = fmaf(k.omb2, __fmul_rn(g, g), __fmul_rn(k.beta2, v));   // v.mul_(beta2).addcmul_(g, g, 1 - beta2)
-    const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(v1), k.bc2_sqrt), k.eps);
-    p = fmaf(-k.step, __fdiv_rn(m1, denom), p1);                             // p.addcdiv_(m, denom, value=-step)
-    m = m1;
-    v = v1;
-}
+using namespace dcfp_optim;      // AdamK, adamw_one: shared with clip_ema.hip
 
 __device__ __forceinline__ void adamw_four(f32x4& p, const f32x4 g, f32x4& m, f32x4& v, const AdamK k) {
 #pragma unroll

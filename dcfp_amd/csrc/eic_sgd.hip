@@ -4,6 +4,7 @@
 // The reference issues ~10 launches per scored BN layer (113 layers) and ~4 foreach
 // launches per SGD step; here each is ONE launch over a device-resident pointer table.
 #include "common.h"
+#include "optim_step.h"
 
 namespace {
 
@@ -42,14 +43,10 @@ sgd_momentum_kernel(const DcfpSgdEntry* __restrict__ table, int n_tensors, float
     if (end > e.n) end = e.n;
     const float wd = e.weight_decay;
     for (long long i = base + threadIdx.x; i < end; i += 256) {
-        const float p = e.param[i];
-        float g = e.grad[i];
-        if (wd != 0.f) g = fmaf(wd, p, g);          // grad.add(param, alpha=wd)
-        float b;
-        if (first_step) b = g;                        // buf = clone(grad)
-        else b = __fadd_rn(__fmul_rn(e.momentum_buf[i], momentum), g);  // buf.mul_(m).add_(g)
-        e.momentum_buf[i] = b;
-        e.param[i] = fmaf(-lr, b, p);                 // param.add_(buf, alpha=-lr)
+        float p = e.param[i];
+        const float bprev = first_step ? 0.f : e.momentum_buf[i];
+        e.momentum_buf[i] = dcfp_optim::sgd_one(p, e.grad[i], bprev, wd, lr, momentum, first_step);   // shared with clip_ema.hip
+        e.param[i] = p;
     }
 }
 

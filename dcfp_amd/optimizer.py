@@ -6,14 +6,17 @@ device-resident pointer table (the reference issues four foreach launches over ~
 or for `--optim adamw` FusedAdamW: torch.optim.AdamW (optimizer.py:26-31) on the same machinery.
 param_groups / lr / weight_decay keep torch.optim semantics, so adjust_learning_rate works
 unchanged."""
+import contextlib
 import ctypes as C
+import math
 
 import numpy as np
 import torch
 from torch.optim.adamw import adamw as _torch_adamw
+from torch.optim.sgd import sgd as _torch_sgd
 
 from . import _lib
-from ._lib import AdamEntry, SgdEntry, SGD_CHUNK, check
+from ._lib import AdamEntry, AdamExEntry, NormEntry, SgdEntry, SgdExEntry, SGD_CHUNK, check
 from .arena import ParamArena
 
 
@@ -38,16 +41,42 @@ def set_weight_decay(model, skip_list=(), skip_keywords=()):
 class _ArenaOptimizer(torch.optim.Optimizer):
     """What FusedSGD and FusedAdamW share: the parameters adopted into a ParamArena, per-parameter state kept as views
     into the arena's named state buffers (`_ARENA_STATE`: state key -> buffer name), `zero_grad` through the arena and
-    the cache of device pointer tables (`table_rebuilds` counts uploads)."""
+    the cache of device pointer tables (`table_rebuilds` counts uploads).
+
+    Both take `max_grad_norm` and `ema_decay`.  max_grad_norm: torch.nn.utils.clip_grad_norm_ over every
+    parameter that has a gradient, all groups together, inside step(): two norm launches leave the coefficient on the
+    device and the step launches multiply each gradient by it as they read it - no host read, and `p.grad` is NOT
+    scaled (scorers and anything else that reads gradients see the raw ones); the norm is accumulated in fp64.
+    ema_decay (0.5 < decay < 1): an exponential moving average of the weights as per-parameter state "ema" (an arena
+    state buffer, in state_dict()), `ema = lerp(ema, p_new, 1 - decay)` in the step launch's epilogue for the parameters
+    that launch updates; a parameter's average starts as a copy of the parameter.  With both None the optimizers call
+    the plain entry points."""
     _ARENA_STATE = {}
 
-    def _init_arena(self):
+    def _init_arena(self, max_grad_norm=None, ema_decay=None):
+        if max_grad_norm is not None:
+            max_grad_norm = float(max_grad_norm)
+            if not (math.isfinite(max_grad_norm) and max_grad_norm > 0):
+                raise ValueError(f"Invalid max_grad_norm: {max_grad_norm} (a finite value > 0, or None)")
+        if ema_decay is not None:
+            ema_decay = float(ema_decay)
+            if not 0.5 < ema_decay < 1.0:
+                raise ValueError(f"Invalid ema_decay: {ema_decay} (0.5 < decay < 1, or None)")
+            self._ARENA_STATE = dict(type(self)._ARENA_STATE, ema="ema")    # the EMA is per-parameter optimizer state
+        self.max_grad_norm, self.ema_decay = max_grad_norm, ema_decay
+        self._ema_w = 0.0 if ema_decay is None else 1.0 - ema_decay        # a double: rounded once where it is used
+        self._ext = max_grad_norm is not None or ema_decay is not None     # the step goes through the *_ex entry points
+        self._norm = None               # cached norm table: (key, table, n, chunks, workspace, tensor_sq, params)
+        self._norm_result = None        # DcfpGradNorm on the device, as two doubles
+        self._host_norm = None          # (norm, [squared norms], params) of a step that took torch's functions
+        self._swapped = False
         self._drop_tables()
         self._arena = None
         self.table_rebuilds = 0
 
     def _drop_tables(self):
         self._tables = {}
+        self._norm = None
 
     def _all_params(self):
         return [p for g in self.param_groups for p in g["params"] if p.requires_grad]
@@ -72,13 +101,136 @@ class _ArenaOptimizer(torch.optim.Optimizer):
                     old = state.get(key)
                     view = ar.state_view(name, i)
                     if old is None:
-                        if reused[key]:  # no loaded state for this parameter: it starts from zero, as torch.optim's would
+                        if key == "ema":     # no loaded average for this parameter: it starts as the parameter itself
+                            view.copy_(p.detach())
+                        elif reused[key]:  # no loaded state for this parameter: it starts from zero, as torch.optim's would
                             view.zero_()
                     elif old.data_ptr() != view.data_ptr():
                         view.copy_(old)
                     state[key] = view
                 self._adopted(p, state)
         return self._arena
+
+    # ------------------------------------------------------------------ gradient-norm clipping
+    def _clip(self):
+        """The clip coefficient of this step over every parameter that has a gradient, all groups together, as
+        clip_grad_norm_(model.parameters()) takes them; the gradients themselves stay as they are.
+        None: no clipping; an int: the device address of the coefficient (two launches, no host read);
+        a dict {parameter: scaled gradient}: parameters the kernels cannot take, through torch's own functions."""
+        if self.max_grad_norm is None:
+            return None
+        params = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
+        ready = [_kernel_ready(p) for p in params]
+        if not all(ready):
+            if any(ready):
+                raise NotImplementedError("max_grad_norm over a mix of parameters the HIP kernels take and parameters "
+                                          "they do not (CPU or non-contiguous) is not implemented")
+            grads = [p.grad for p in params]
+            total = torch.nn.utils.get_total_norm(grads, 2.0, False, None)        # what clip_grad_norm_ computes ...
+            coef = torch.clamp(self.max_grad_norm / (total + 1e-6), max=1.0)       # ... and scales by
+            self._host_norm = (total, [g.detach().double().pow(2).sum() for g in grads], params)
+            return {p: g * coef.to(g.device) for p, g in zip(params, grads)}
+        self._host_norm = None
+        if self._norm_result is None:
+            if not params:
+                return None
+            self._norm_result = torch.zeros(2, dtype=torch.float64, device=params[0].device)
+        key = tuple((p.grad.data_ptr(), p.numel()) for p in params)
+        if self._norm is None or self._norm[0] != key:
+            self.table_rebuilds += 1
+            entries = (NormEntry * max(1, len(params)))()
+            chunk = 0
+            for e, p in zip(entries, params):
+                e.data, e.n, e.first_chunk = p.grad.data_ptr(), p.numel(), chunk
+                chunk += (p.numel() + SGD_CHUNK - 1) // SGD_CHUNK
+            dev = self._norm_result.device
+            table = torch.frombuffer(bytearray(bytes(entries)), dtype=torch.uint8).to(dev)
+            self._norm = (key, table, len(params), chunk, torch.empty(max(1, chunk), dtype=torch.float64, device=dev),
+                          torch.zeros(max(1, len(params)), dtype=torch.float64, device=dev), params)
+        _, table, n, chunks, ws, sq, _ = self._norm
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        check(_lib.lib().dcfp_grad_norm_f32(C.c_void_p(table.data_ptr()), n, chunks, self.max_grad_norm,
+                                            C.c_void_p(ws.data_ptr()), ws.numel() * 8, C.c_void_p(sq.data_ptr()),
+                                            C.c_void_p(self._norm_result.data_ptr()), stream), "grad_norm")
+        return self._norm_result.data_ptr() + 12                # DcfpGradNorm.coef
+
+    def grad_norm(self):
+        """The global gradient norm of the last step, before clipping: a scalar on the parameters' device (reading it
+        is the caller's sync).  None before the first clipped step."""
+        if self._host_norm is not None:
+            return self._host_norm[0]
+        if self._norm_result is None or self._norm is None:
+            return None
+        return self._norm_result.view(torch.float32)[2]
+
+    def grad_sqnorms(self):
+        """[(parameter, its gradient's squared norm in fp64 - a scalar on the device)] of the last clipped step."""
+        if self._host_norm is not None:
+            return list(zip(self._host_norm[2], self._host_norm[1]))
+        if self._norm is None:
+            return []
+        return list(zip(self._norm[6], self._norm[5][:self._norm[2]].unbind()))
+
+    # ------------------------------------------------------------------ weight EMA
+    def _ema_of(self, p):
+        """The EMA of a parameter outside the arena: a copy of the parameter when it is first needed."""
+        st = self.state[p]
+        if "ema" not in st:
+            st["ema"] = p.detach().clone(memory_format=torch.contiguous_format)
+        return st["ema"]
+
+    def _require_ema(self):
+        if self.ema_decay is None:
+            raise RuntimeError("this optimizer keeps no weight EMA (ema_decay=None)")
+
+    def ema_state_dict(self, model):
+        """model.state_dict() with every parameter this optimizer updates replaced by (a copy of) its EMA; buffers are
+        the live ones.  What tools/evaluate.py --restore-from loads."""
+        self._require_ema()
+        self.arena()
+        sd = model.state_dict()
+        mine = {id(p) for p in self._all_params()}
+        for name, p in model.named_parameters():
+            if id(p) in mine and name in sd:
+                sd[name] = self._ema_of(p).detach().clone()
+        return sd
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Evaluate with the averaged weights in place: parameters and EMA change places (the arenas' contents, so every
+        address stays what it was), the permuted weight copies are refreshed, and on exit everything is swapped back
+        bit for bit.  step() inside the block raises."""
+        self._require_ema()
+        if self._swapped:
+            raise RuntimeError("ema_weights() is already active")
+        self._swap_ema()
+        self._swapped = True
+        try:
+            yield self
+        finally:
+            self._swap_ema()
+            self._swapped = False
+
+    @torch.no_grad()
+    def _swap_ema(self):
+        ar = self.arena()
+        if ar is not None:
+            pairs = [(ar.flat_param, ar.state_buffer("ema"))]
+        else:
+            pairs = [(p.data, self._ema_of(p)) for p in self._all_params()]
+        for a, b in pairs:
+            tmp = a.clone()
+            a.copy_(b)
+            b.copy_(tmp)
+        if ar is not None:
+            self._weights_changed()
+        else:
+            from . import ops
+            ops.WEIGHT_EPOCH[0] += 1
+
+    def _check_may_step(self):
+        if self._swapped:
+            raise RuntimeError("step() inside ema_weights(): the parameters hold the averaged weights")
 
     def zero_grad(self, set_to_none: bool = True):
         """Same contract as torch.optim.Optimizer.zero_grad.  With the arena: set_to_none detaches the gradient
@@ -113,22 +265,25 @@ class FusedSGD(_ArenaOptimizer):
     counts uploads) and a step is one kernel launch per non-empty group; `zero_grad()` launches nothing."""
     _ARENA_STATE = {"momentum_buffer": "momentum"}
 
-    def __init__(self, params, lr=1e-3, momentum=0.0, weight_decay=0.0):
+    def __init__(self, params, lr=1e-3, momentum=0.0, weight_decay=0.0, *, max_grad_norm=None, ema_decay=None):
         super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay))
-        self._init_arena()
+        self._init_arena(max_grad_norm, ema_decay)
 
     def _table(self, gi, group, params):
-        key = tuple((p.data_ptr(), p.grad.data_ptr(), self.state[p]["momentum_buffer"].data_ptr()) for p in params) \
-            + (group["weight_decay"],)
+        ema = self.ema_decay is not None
+        key = tuple((p.data_ptr(), p.grad.data_ptr(), self.state[p]["momentum_buffer"].data_ptr()) +
+                    ((self.state[p]["ema"].data_ptr(),) if ema else ()) for p in params) + (group["weight_decay"],)
         cached = self._tables.get(gi)
         if cached is not None and cached[0] == key:
             return cached[1], cached[2], cached[3]
         self.table_rebuilds += 1
-        entries = (SgdEntry * len(params))()
+        entries = ((SgdExEntry if self._ext else SgdEntry) * len(params))()
         chunk = 0
         for i, p in enumerate(params):
             e = entries[i]
             e.param, e.grad, e.momentum_buf = p.data_ptr(), p.grad.data_ptr(), self.state[p]["momentum_buffer"].data_ptr()
+            if ema:
+                e.ema = self.state[p]["ema"].data_ptr()
             e.n, e.first_chunk, e.weight_decay = p.numel(), chunk, group["weight_decay"]
             chunk += (p.numel() + SGD_CHUNK - 1) // SGD_CHUNK
         host = torch.frombuffer(bytearray(bytes(entries)), dtype=torch.uint8)
@@ -136,17 +291,39 @@ class FusedSGD(_ArenaOptimizer):
         self._tables[gi] = (key, dev, len(params), chunk)
         return dev, len(params), chunk
 
+    def _step_torch(self, group, params, scaled):
+        """torch's own SGD, on the same state, for parameters the kernels cannot take (a CPU model)."""
+        bufs = []
+        for p in params:
+            st = self.state[p]
+            if "momentum_buffer" not in st:
+                st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            bufs.append(st["momentum_buffer"])
+        emas = [self._ema_of(p) for p in params] if self.ema_decay is not None else []      # (before the update)
+        _torch_sgd(params, [scaled.get(p, p.grad) for p in params], bufs, weight_decay=group["weight_decay"],
+                   momentum=group["momentum"], lr=group["lr"], dampening=0.0, nesterov=False, maximize=False)
+        for p, e in zip(params, emas):
+            e.lerp_(p, self._ema_w)
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        L = _lib.lib()
+        self._check_may_step()
         self.arena()
+        clip = self._clip()
+        launched = not self._ext
         for gi, group in enumerate(self.param_groups):
             params = [p for p in group["params"] if p.grad is not None]
             if not params:
+                continue
+            if self._ext and not all(_kernel_ready(p) for p in params):
+                if any(_kernel_ready(p) for p in params):
+                    raise NotImplementedError("FusedSGD: a param group mixing parameters the HIP kernel takes with "
+                                              "others, with max_grad_norm or ema_decay set")
+                self._step_torch(group, params, clip if isinstance(clip, dict) else {})
                 continue
             for p in params:
                 if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous() \
@@ -154,11 +331,21 @@ class FusedSGD(_ArenaOptimizer):
                     raise RuntimeError("FusedSGD: parameters and grads must be contiguous CUDA fp32")
                 if "momentum_buffer" not in self.state[p]:     # parameter outside the arena
                     self.state[p]["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                if self.ema_decay is not None:
+                    self._ema_of(p)
             table, n, chunks = self._table(gi, group, params)
             stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            check(L.dcfp_sgd_momentum_f32(C.c_void_p(table.data_ptr()), n, chunks, float(group["lr"]),
-                                          float(group["momentum"]), 0, stream), "sgd_momentum")
-        self._weights_changed()
+            L = _lib.lib()
+            launched = True
+            if self._ext:
+                check(L.dcfp_sgd_momentum_ex_f32(C.c_void_p(table.data_ptr()), n, chunks, float(group["lr"]),
+                                                 float(group["momentum"]), 0, C.c_void_p(clip), self._ema_w, stream),
+                      "sgd_momentum_ex")
+            else:
+                check(L.dcfp_sgd_momentum_f32(C.c_void_p(table.data_ptr()), n, chunks, float(group["lr"]),
+                                              float(group["momentum"]), 0, stream), "sgd_momentum")
+        if launched:
+            self._weights_changed()
         return loss
 
 
@@ -192,7 +379,7 @@ class FusedAdamW(_ArenaOptimizer):
     _TABLES_PER_GROUP = 8        # partitions seen lately (steady state: 1; a late gradient adds one)
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *,
-                 maximize=False, capturable=False):
+                 maximize=False, capturable=False, max_grad_norm=None, ema_decay=None):
         b1, b2 = betas
         if not 0.0 <= lr:
             raise ValueError(f"Invalid learning rate: {lr}")
@@ -205,7 +392,7 @@ class FusedAdamW(_ArenaOptimizer):
         super().__init__(params, dict(lr=lr, betas=(b1, b2), eps=eps, weight_decay=weight_decay, amsgrad=amsgrad,
                                       maximize=maximize))
         self._unsupported(self.param_groups, capturable)
-        self._init_arena()
+        self._init_arena(max_grad_norm, ema_decay)
 
     @staticmethod
     def _unsupported(groups, capturable=False):
@@ -242,10 +429,13 @@ class FusedAdamW(_ArenaOptimizer):
         if cached is not None:
             return cached
         self.table_rebuilds += 1
-        entries = (AdamEntry * len(params))()
+        entries = ((AdamExEntry if self._ext else AdamEntry) * len(params))()
         chunk = 0
         for e, p, k in zip(entries, params, key):
-            e.param, e.grad, e.exp_avg, e.exp_avg_sq = k
+            if self._ext:
+                e.param, e.grad, e.exp_avg, e.exp_avg_sq, e.ema = k        # (ema 0: none)
+            else:
+                e.param, e.grad, e.exp_avg, e.exp_avg_sq = k
             e.n, e.first_chunk = p.numel(), chunk
             chunk += (p.numel() + SGD_CHUNK - 1) // SGD_CHUNK
         host = torch.frombuffer(bytearray(bytes(entries)), dtype=torch.uint8)
@@ -264,13 +454,18 @@ class FusedAdamW(_ArenaOptimizer):
                 st["step"] = self._new_step()
                 st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        ema = self.ema_decay is not None
+        if ema:
+            for p in params:
+                self._ema_of(p)                               # (a parameter outside the arena: its value before the step)
         ready = [_kernel_ready(p) and state[p]["exp_avg"].is_contiguous() and state[p]["exp_avg_sq"].is_contiguous()
-                 for p in params]
+                 and (not ema or self._ema_of(p).is_contiguous()) for p in params]
         fused = [p for p, ok in zip(params, ready) if ok]
         rest = [p for p, ok in zip(params, ready) if not ok]
         plan = {"key": key, "fused": fused, "rest": rest, "steps": [state[p]["step"] for p in fused],
                 "records": tuple((p.data_ptr(), p.grad.data_ptr(), state[p]["exp_avg"].data_ptr(),
-                                  state[p]["exp_avg_sq"].data_ptr()) for p in fused)}
+                                  state[p]["exp_avg_sq"].data_ptr()) +
+                                 (((state[p]["ema"].data_ptr() if ema else 0),) if self._ext else ()) for p in fused)}
         self._plans[gi] = plan
         return plan
 
@@ -280,7 +475,10 @@ class FusedAdamW(_ArenaOptimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        self._check_may_step()
         self.arena()
+        clip = self._clip()
+        scaled = clip if isinstance(clip, dict) else {}
         launched = False
         for gi, group in enumerate(self.param_groups):
             params = [p for p in group["params"] if p.grad is not None]
@@ -294,10 +492,13 @@ class FusedAdamW(_ArenaOptimizer):
             rest, fused, steps = plan["rest"], plan["fused"], plan["steps"]
             if rest:                                          # torch's own update, on the same state
                 state = self.state
-                _torch_adamw(rest, [p.grad for p in rest], [state[p]["exp_avg"] for p in rest],
+                _torch_adamw(rest, [scaled.get(p, p.grad) for p in rest], [state[p]["exp_avg"] for p in rest],
                              [state[p]["exp_avg_sq"] for p in rest], [], [state[p]["step"] for p in rest],
                              amsgrad=False, beta1=beta1, beta2=beta2, lr=group["lr"],
                              weight_decay=group["weight_decay"], eps=group["eps"], maximize=False)
+                if self.ema_decay is not None:
+                    for p in rest:
+                        self._ema_of(p).lerp_(p, self._ema_w)
             if not fused:
                 continue
             torch._foreach_add_(steps, 1)                     # host tensors: no launch
@@ -316,8 +517,14 @@ class FusedAdamW(_ArenaOptimizer):
                 table, n, chunks = self._table(gi, part, records)
                 bc1 = 1 - beta1 ** t                          # Python doubles, as torch's _single_tensor_adam
                 bc2_sqrt = (1 - beta2 ** t) ** 0.5
-                check(L.dcfp_adamw_f32(C.c_void_p(table.data_ptr()), n, chunks, float(group["lr"]), beta1, beta2,
-                                       group["eps"], group["weight_decay"], bc1, bc2_sqrt, stream), "adamw")
+                if self._ext:
+                    check(L.dcfp_adamw_ex_f32(C.c_void_p(table.data_ptr()), n, chunks, float(group["lr"]), beta1, beta2,
+                                              group["eps"], group["weight_decay"], bc1, bc2_sqrt,
+                                              C.c_void_p(None if isinstance(clip, dict) else clip), self._ema_w, stream),
+                          "adamw_ex")
+                else:
+                    check(L.dcfp_adamw_f32(C.c_void_p(table.data_ptr()), n, chunks, float(group["lr"]), beta1, beta2,
+                                           group["eps"], group["weight_decay"], bc1, bc2_sqrt, stream), "adamw")
             launched = True
         if launched:
             self._weights_changed()
@@ -327,12 +534,14 @@ class FusedAdamW(_ArenaOptimizer):
 def build_optimizer(config, model):
     skip_keywords = config.no_decay.split(",") if getattr(config, "no_decay", None) is not None else []
     parameters = set_weight_decay(model, [], skip_keywords)
+    extras = dict(max_grad_norm=getattr(config, "clip_grad_norm", None), ema_decay=getattr(config, "ema_decay", None))
     if config.optim == "sgd":
         return FusedSGD(parameters, momentum=config.momentum, lr=config.learning_rate,
-                        weight_decay=config.weight_decay)
+                        weight_decay=config.weight_decay, **extras)
     if config.optim == "adamw":
         b1, b2 = map(float, config.betas.split(","))
-        return FusedAdamW(parameters, betas=(b1, b2), lr=config.learning_rate, weight_decay=config.weight_decay)
+        return FusedAdamW(parameters, betas=(b1, b2), lr=config.learning_rate, weight_decay=config.weight_decay,
+                          **extras)
     return None
 
 

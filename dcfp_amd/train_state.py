@@ -46,7 +46,11 @@ ARG_FIELDS = (
     ("random_mirror", "random_mirror"), ("random_brightness", "random_brightness"), ("balance", "balance"),
     ("longsize", "longsize"), ("shortsize", "shortsize"), ("ignore_label", "ignore_label"),
     ("input_size", "input_size"), ("random_seed", "random_seed"),
+    ("clip_grad_norm", "clip_grad_norm"), ("ema_decay", "ema_decay"),
 )
+# fields younger than the format: a state file written before they existed was written without them, which is what
+# None says - such a file continues in a run that sets neither, and is refused by name in a run that sets one
+ABSENT_IS_NONE = ("clip_grad_norm", "ema_decay")
 
 
 def fingerprint(args, seg_model, num_classes, world_size):
@@ -64,7 +68,8 @@ def check_fingerprint(saved, current):
     for field in list(saved) + [f for f in current if f not in saved]:
         if field == "params":
             continue
-        a, b = saved.get(field, "<absent>"), current.get(field, "<absent>")
+        absent = None if field in ABSENT_IS_NONE else "<absent>"
+        a, b = saved.get(field, absent), current.get(field, absent)
         if a != b:
             raise ValueError("cannot continue: %s differs - the state file has %r, this run %r" % (field, a, b))
     sp, cp = saved.get("params", []), current.get("params", [])

@@ -781,6 +781,71 @@ int dcfp_adamw_f32(const DcfpAdamEntry* table, int n_tensors, int64_t total_chun
                    float lr, float beta1, float beta2, float eps, float weight_decay,
                    float bias_correction1, float bias_correction2_sqrt, dcfp_stream_t stream);
 
+/* ------------------------------------- gradient-norm clipping and weight EMA (csrc/clip_ema.hip)
+ * dcfp_grad_norm_f32: the global L2 norm of n_tensors gradient tensors and torch.nn.utils.clip_grad_norm_'s
+ * coefficient, on the device.  table: DEVICE array of records, first_chunk the prefix sum of ceil(n / DCFP_SGD_CHUNK)
+ * as in the step tables; data at any 4-byte aligned address (16-byte loads from the first 16-byte boundary on).
+ * Every element is converted to double, squared (exact) and accumulated in double: launch 1 leaves one partial per
+ * chunk in the workspace (dcfp_grad_norm_workspace_bytes(total_chunks) bytes, 8-byte aligned), launch 2 - one block -
+ * adds each tensor's partials in ascending chunk order (tensor_sq[i], device, nullable; the workspace is scratch and
+ * is overwritten), then the tensors in ascending order, and writes
+ *   result->sqnorm ; result->norm = (float)sqrt(sqnorm) ;
+ *   c = max_norm / (norm + 1e-6f), each operation rounded once ; result->coef = c > 1 ? 1 : c
+ * so a NaN norm gives a NaN coefficient and an infinite one 0 (error_if_nonfinite=False).  No atomics: two calls on
+ * the same inputs leave the same bits.  n_tensors == 0 writes {0, 0, 1}.  DCFP_E_BADDESC: null table with a positive
+ * count, negative counts, total_chunks > 2^31-1, max_norm not > 0 (NaN included), result null or result / tensor_sq
+ * not 8-byte aligned; DCFP_E_WORKSPACE: a workspace that is needed and null, not 8-byte aligned or too small.  All of
+ * it is checked before any HIP call.
+ *
+ * dcfp_sgd_momentum_ex_f32 / dcfp_adamw_ex_f32: dcfp_sgd_momentum_f32 / dcfp_adamw_f32 (the same per-element code)
+ * with two optional additions in the same launch:
+ *   coef (device, nullable): the gradient enters as g * *coef, rounded once - torch's g.mul_(clip_coef); grad itself
+ *     is only read;
+ *   ema (per entry, nullable) and ema_w = float(1.0 - double(decay)), 0 <= ema_w < 0.5: after the new parameter value
+ *     is formed, ema = ema + ema_w * (p_new - ema) with torch.lerp's bits (one subtraction, one fma).
+ * Entries whose pointers (ema included) are all 16-byte aligned take 16-byte loads and stores, the others (and the
+ * last n % 4 elements) a scalar path with the same bits per element; nothing is written past n.  With coef null and
+ * no ema pointers the results equal the plain entry points' bit for bit.  DCFP_E_BADDESC: negative counts,
+ * total_chunks > 2^31-1, ema_w outside [0, 0.5), null table; n_tensors == 0 or total_chunks == 0: DCFP_OK, no launch. */
+typedef struct DcfpNormEntry {
+    const float* data;
+    int64_t n;
+    int64_t first_chunk; /* prefix sum of ceil(n / DCFP_SGD_CHUNK) over earlier entries */
+} DcfpNormEntry;
+typedef struct DcfpGradNorm {
+    double sqnorm;
+    float norm;
+    float coef;
+} DcfpGradNorm;
+size_t dcfp_grad_norm_workspace_bytes(int64_t total_chunks);
+int dcfp_grad_norm_f32(const DcfpNormEntry* table, int n_tensors, int64_t total_chunks, float max_norm,
+                       void* workspace, size_t workspace_bytes, double* tensor_sq, DcfpGradNorm* result,
+                       dcfp_stream_t stream);
+typedef struct DcfpSgdExEntry {
+    float* param;
+    const float* grad;
+    float* momentum_buf;
+    float* ema;          /* nullable */
+    int64_t n;
+    int64_t first_chunk;
+    float weight_decay;
+    int32_t pad_;
+} DcfpSgdExEntry;
+int dcfp_sgd_momentum_ex_f32(const DcfpSgdExEntry* table, int n_tensors, int64_t total_chunks, float lr,
+                             float momentum, int first_step, const float* coef, float ema_w, dcfp_stream_t stream);
+typedef struct DcfpAdamExEntry {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    float* ema;          /* nullable */
+    int64_t n;
+    int64_t first_chunk;
+} DcfpAdamExEntry;
+int dcfp_adamw_ex_f32(const DcfpAdamExEntry* table, int n_tensors, int64_t total_chunks, float lr, float beta1,
+                      float beta2, float eps, float weight_decay, float bias_correction1,
+                      float bias_correction2_sqrt, const float* coef, float ema_w, dcfp_stream_t stream);
+
 /* ------------------------------------------------- fp16 deployment engine
  * The frozen half-precision inference path (dcfp_amd/deploy.py; the reference's totrt.py stage).  Activations are
  * NHWC fp16 with a channel pitch that is a multiple of 8; weights are packed once as [Cout8][KH][KW][Cin8] fp16 with

@@ -17,7 +17,16 @@ device time; in training it hides behind the backward pass), so each phase is al
 a few large matrix products are enqueued first, the steps are queued behind them, and two device events bracket the
 steps ("device" ms; `ahead` says that the host had queued every step before the first one started).  GB/s =
 algorithmic bytes of the update (AdamW 28 B/element: p, g, m, v read, p, m, v written; SGD 20 B/element) over the
-device time of the "update" phase."""
+device time of the "update" phase.
+
+Then gradient-norm clipping and the weight EMA, "update" phase only, device time with the queue
+kept full:
+
+  fused_sgd+clip, fused_adamw+clip           max_grad_norm set: the two norm launches, then the step launches
+  fused_sgd+clip+ema, fused_adamw+clip+ema   ... and ema_decay set (8 B/element more in the step launch)
+  grad_norm                                  the two norm launches alone (4 B/element), beside ops.state_digest_device
+                                             over the same gradient arena (the read-only pass it is modelled on)
+  torch_sgd+clip+ema, torch_adamw+clip+ema   clip_grad_norm_(foreach=True), the foreach optimizer, torch._foreach_lerp_"""
 import argparse
 import ctypes as C
 import gc
@@ -121,6 +130,74 @@ def device_ms(fn, steps, busy):
     return e0.elapsed_time(e1) / steps, ahead
 
 
+def clip_ema_rows(result, layout, dev, args, busy):
+    """The rows of the module docstring's second table.  max_grad_norm is small enough that the coefficient is < 1."""
+    CLIP, DECAY = 1e-2, 0.999
+
+    def torch_step(make):
+        def build(groups):
+            opt = make(groups)
+            params = [p for g in groups for p in g["params"]]
+            emas = [p.detach().clone() for p in params]
+
+            def step():
+                torch.nn.utils.clip_grad_norm_(params, CLIP, foreach=True)
+                opt.step()
+                torch._foreach_lerp_(emas, [p.detach() for p in params], 1.0 - DECAY)
+            return opt, step
+        return build
+
+    def fused(make, **kw):
+        def build(groups):
+            opt = make(groups, **kw)
+            return opt, opt.step
+        return build
+    sgd = lambda g, **kw: FusedSGD(g, lr=0.01, momentum=0.9, weight_decay=5e-4, **kw)          # noqa: E731
+    adamw = lambda g, **kw: FusedAdamW(g, lr=1e-3, weight_decay=1e-2, **kw)                    # noqa: E731
+    rows = {
+        "fused_sgd+clip": (fused(sgd, max_grad_norm=CLIP), 24),
+        "fused_sgd+clip+ema": (fused(sgd, max_grad_norm=CLIP, ema_decay=DECAY), 32),
+        "fused_adamw+clip": (fused(adamw, max_grad_norm=CLIP), 32),
+        "fused_adamw+clip+ema": (fused(adamw, max_grad_norm=CLIP, ema_decay=DECAY), 40),
+        "torch_sgd+clip+ema": (torch_step(lambda g: torch.optim.SGD(g, lr=0.01, momentum=0.9, weight_decay=5e-4,
+                                                                    foreach=True)), None),
+        "torch_adamw+clip+ema": (torch_step(lambda g: torch.optim.AdamW(g, lr=1e-3, weight_decay=1e-2, foreach=True)),
+                                 None),
+    }
+    numel = result["elements"]
+    for seed, (name, (build, nbytes)) in enumerate(rows.items()):
+        params, groups = make_params(layout, dev, 100 + seed)
+        opt, step = build(groups)
+        wall, med = timed(step, args.warmup, args.steps)
+        dms, ahead = device_ms(step, args.device_steps, busy)
+        row = {"update_ms": wall, "update_median_ms": med, "update_device_ms": dms, "ahead": bool(ahead),
+               "bytes_per_element": nbytes, "table_rebuilds": getattr(opt, "table_rebuilds", None)}
+        if nbytes:
+            row["update_GBps"] = nbytes * numel / (dms * 1e-3) / 1e9
+        if name == "fused_sgd+clip":              # the norm launches alone, and the digest of the same arena beside them
+            row["grad_norm"] = float(opt.grad_norm())
+            n_ms, n_ahead = device_ms(opt._clip, args.device_steps, busy)
+            flat = opt.arena().flat_grad
+            ops.state_digest_device(flat)
+            d_ms, d_ahead = device_ms(lambda: ops.state_digest_device(flat), args.device_steps, busy)
+            result["rows"]["grad_norm"] = {
+                "device_ms": n_ms, "GBps": 4 * numel / (n_ms * 1e-3) / 1e9, "ahead": bool(n_ahead),
+                "digest_device_ms": d_ms, "digest_GBps": 4 * flat.numel() / (d_ms * 1e-3) / 1e9,
+                "digest_ahead": bool(d_ahead), "arena_elements": flat.numel()}
+            print("%-22s device %.3f ms = %.0f GB/s over %.1f M elements | state digest of the gradient arena "
+                  "(%.1f M elements) %.3f ms = %.0f GB/s" % ("grad_norm", n_ms, result["rows"]["grad_norm"]["GBps"],
+                                                            numel / 1e6, flat.numel() / 1e6, d_ms,
+                                                            result["rows"]["grad_norm"]["digest_GBps"]))
+        result["rows"][name] = row
+        print("%-22s update: loop %.3f ms (median %.3f), device %.3f ms%s%s"
+              % (name, wall, med, dms, (" = %.0f GB/s at %d B/element" % (row["update_GBps"], nbytes)) if nbytes else "",
+                 "" if ahead else "  [host did not stay ahead: device figures include host gaps]"))
+        del opt, step, params, groups
+        gc.collect()
+        ops._WP_TABLE["version"] += 1
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--backbone", default="resnet101")
@@ -175,6 +252,7 @@ def main():
         gc.collect()
         ops._WP_TABLE["version"] += 1
         torch.cuda.empty_cache()
+    clip_ema_rows(result, layout, dev, args, busy)
     print(json.dumps(result))
 
 

@@ -16,6 +16,7 @@ file, leaving the bits the uninterrupted run leaves (dcfp_amd/train_state.py, DE
 One process per GPU: `python -m torch.distributed.run --nproc-per-node N tools/train.py ...`."""
 import argparse
 import json
+import math
 import os
 import os.path as osp
 import sys
@@ -76,6 +77,12 @@ def get_parser():
     p.add_argument("--prune-type", type=str, default=None,
                    help="score while training and write score.pth: dcfp (the EIC score), taylor (first-order Taylor on "
                         "the BN gate) or taylor_w (on the filters); DESIGN §17")
+    p.add_argument("--clip-grad-norm", type=float, default=None,
+                   help="clip the global gradient norm to this value inside the optimizer launch (the gradients "
+                        "themselves stay unscaled); the log line gains gnorm=")
+    p.add_argument("--ema-decay", type=float, default=None,
+                   help="keep an exponential moving average of the weights (0.5 < decay < 1) as optimizer state; every "
+                        "CS_scenes_<k>.pth gets a CS_scenes_<k>_ema.pth beside it")
     p.add_argument("--slim-lambda", type=float, default=0.0,
                    help="Network Slimming: add lambda * sign(gamma) to the BN weight gradients before every optimizer "
                         "step (0 = off), in any --prune-type")
@@ -138,6 +145,11 @@ def check_args(args):
         raise ValueError("--prune-type %s: the Taylor scorers are %s" % (args.prune_type, ", ".join(sorted(TAYLOR_TYPES))))
     if not args.slim_lambda >= 0.0:
         raise ValueError("--slim-lambda %r: the sparsity weight is >= 0 (0 = off)" % args.slim_lambda)
+    clip, decay = getattr(args, "clip_grad_norm", None), getattr(args, "ema_decay", None)
+    if clip is not None and not (math.isfinite(clip) and clip > 0):
+        raise ValueError("--clip-grad-norm %r: the largest gradient norm is finite and > 0" % clip)
+    if decay is not None and not 0.5 < decay < 1.0:
+        raise ValueError("--ema-decay %r: the decay lies in (0.5, 1)" % decay)
     if getattr(args, "continue_fpath", None):
         if args.resume:
             raise ValueError("-c/--continue restores the weights itself: give it without --resume")
@@ -156,6 +168,16 @@ def build_teacher(args, num_classes, device):
     if args.teacher_channel_cfg is not None:
         pruners.init_pruned_model(net, torch.load(args.teacher_channel_cfg, weights_only=False))
     return Teacher.from_checkpoint(net, args.teacher_from, engine=args.teacher_engine).to(device)
+
+
+def raise_nonfinite_gradient(optimizer, seg_model, gnorm):
+    """The gradient norm of the step is not finite: name the first parameter whose squared norm is not."""
+    names = {id(p): n for n, p in seg_model.named_parameters()}
+    for p, sq in optimizer.grad_sqnorms():
+        if not math.isfinite(float(sq)):
+            raise FloatingPointError("gradient norm is %r: the gradient of %s is not finite (squared norm %r)"
+                                     % (gnorm, names.get(id(p), "<unnamed>"), float(sq)))
+    raise FloatingPointError("gradient norm is %r (every per-parameter squared norm is finite)" % gnorm)
 
 
 def main(argv=None):
@@ -286,10 +308,20 @@ def main(argv=None):
                 if main_flag:
                     print("  step %.1f ms  %.2f images/s/GPU" % (ms, per_rank / ms * 1e3), flush=True)
             if main_flag:
-                print("Iters%d/%d lr=%.2e loss=%.4f" % (it + 1, args.num_steps, lr, reduce_loss.item()), flush=True)
+                gnorm = ""
+                if args.clip_grad_norm is not None:
+                    gn = float(optimizer.grad_norm())      # (the loss read below syncs anyway)
+                    if not math.isfinite(gn):
+                        raise_nonfinite_gradient(optimizer, seg_model, gn)
+                    gnorm = " gnorm=%.4e" % gn
+                print("Iters%d/%d lr=%.2e loss=%.4f%s" % (it + 1, args.num_steps, lr, reduce_loss.item(), gnorm),
+                      flush=True)
                 done = it + 1
                 if done >= args.save_steps and ((args.num_steps - done) % args.save_pred_every == 0 or done >= args.num_steps):
                     torch.save(seg_model.state_dict(), osp.join(args.snapshot_dir, "CS_scenes_%d.pth" % done))
+                    if args.ema_decay is not None:
+                        torch.save(optimizer.ema_state_dict(seg_model),
+                                   osp.join(args.snapshot_dir, "CS_scenes_%d_ema.pth" % done))
             if args.log_digest > 0 and (it + 1) % args.log_digest == 0 and main_flag:
                 from dcfp_amd import ops as _ops
                 print("digest it=%d params=%s" % (it + 1, train_state.format_digest(
